@@ -20,6 +20,11 @@ open3d_slam_amd/sharded.py).  Weak scaling: per-GPU work is fixed.  `value` = th
 BASELINE.json's -- one ICP iteration of the 64k scan against one 1M-point submap -- i.e. N per iteration of the joint registration;
 `joint_registration_iterations_per_sec` (= value / N: the registration over N submaps is ONE registration, not N) and
 `point_queries_per_sec` (source points searched per second over all ranks) stand beside it.
+
+A plain run (`--steps K --warmup W`) sets up, warms up, times the K steps of M1 with f32 storage and prints the line: nothing else runs.
+`--full` adds everything above that takes runs of its own -- the roofline re-runs, the f64 / 8 M-point map / in-library / GeneralizedIcp /
+concurrent legs, the copy bandwidth, M2 and its tables, the CPU baselines and, at N > 1, configs 3u and 4.  `--dump-outputs DIR` writes the
+result of the last timed step as DIR/<field>.npy (float64).
 """
 from __future__ import annotations
 
@@ -757,8 +762,18 @@ def emit(out):
         print(line, flush=True)
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the registration result the last timed step returned, one float64 array per numeric field (transformation,
+    fitness, inlier_rmse, iterations, ...), so that two builds run on the same seeded inputs can be compared output for output"""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in res.items():
+        a = np.asarray(v)
+        if a.dtype.kind in "biuf":
+            np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ M1
-def run_m1(be, world, s_id, t_id, steps, warmup, barrier, drv):
+def run_m1(be, world, s_id, t_id, steps, warmup, barrier, drv, profile):
     if drv is not None:
         def step():
             return drv.register(s_id, t_id, N_SRC, MAX_CORR, max_iter=ICP_ITERS, rel_fitness=0.0, rel_rmse=0.0, check_every=ICP_ITERS + 2)
@@ -788,6 +803,8 @@ def run_m1(be, world, s_id, t_id, steps, warmup, barrier, drv):
     gc.callbacks.remove(on_gc)
     step_us = np.diff(np.array(marks)) * 1e6
     collections = [(g, round((b - a) * 1e3, 2), round((a - t0) * 1e3, 2)) for (p0, g, a), (p1, _, b) in zip(gc_log[::2], gc_log[1::2])]
+    if not profile:
+        return res, elapsed, None, None, step_us, collections, None
     # roofline of the dominant kernel (icp_fused_kernel: one ICP pass + the previous pass's solve/update in its prologue): the same
     # steps re-run with hipEvent brackets around every launch on the launch stream (outside the timed region above)
     be.profile_enable(True)
@@ -890,7 +907,16 @@ def main():
                          "auto = 1 at N = 1, 3 at N > 1")
     ap.add_argument("--dry-line", metavar="DETAIL_JSON", default=None,
                     help="no GPU work: assemble and print the compact line from a detail file of an earlier run (tests/test_bench_line.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline re-runs, the f64 / 8 M-point map / in-library / GeneralizedIcp / concurrent "
+                         "legs, the copy bandwidth, M2 and its tables, the CPU baselines, and at N > 1 configs 3u and 4 beside configs[3]. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last timed registration (what icp_point_to_plane_dev returns) "
+                         "as DIR/<field>.npy, float64; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == "4":
+        ap.error("--dump-outputs: configs[1] / [3] only")
     if args.dry_line:
         print(compact_line(json.load(open(args.dry_line)), os.path.relpath(args.dry_line, ROOT)), flush=True)
         return
@@ -898,7 +924,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    all_configs = args.config == "auto" and world > 1  # the driver's N > 1 command: configs[3] is the line, 3u and 4 ride along in it
+    all_configs = args.full and args.config == "auto" and world > 1  # configs[3] is the line, 3u and 4 ride along in it
     if world != args.gpus:
         if world == 1 and args.gpus > 1:
             # started bare (`python bench.py --gpus N`): become the launcher -- one rank per GPU through torch.distributed.run, same
@@ -925,7 +951,7 @@ def main():
     if args.config == "auto":
         args.config = "1" if world == 1 else "3"
     claim_stdout()
-    do_m2 = world == 1 and args.m2_frames > 1 and args.config == "1"
+    do_m2 = args.full and world == 1 and args.m2_frames > 1 and args.config == "1"
     scans32 = make_stream(args.m2_frames) if do_m2 else None  # before the GPU runtime exists in this process (fork)
 
     import torch
@@ -986,27 +1012,31 @@ def main():
         # library: o3ds_icp_register_sharded -- the loop, the kernels and the ncclAllReduce calls inside libo3ds_backend.so (its own RCCL
         # communicator); else open3d_slam_amd/sharded.py: the same kernels driven from Python with torch.distributed collectives in between
         drv = (sharded.LibraryShardedIcp(be, mode=mode) if library else sharded.ShardedIcp(be, mode=mode)) if (world > 1 or args.config == "3u" or library) else None
-        res, elapsed, n_launch, kern_ms, su, collections, (n_span, span_ms) = run_m1(be, world, s_id, t_id, steps, warmup, barrier, drv)
-        # what a hipEvent bracket costs by itself on this stream (two records back to back): the brackets around the pass launches include it
-        be.profile_enable(True)
-        for _ in range(200):
-            with be.span(0):
-                pass
-        n_br, br_ms = be.span_read(0)
-        be.profile_enable(False)
-        bracket_s = br_ms * 1e-3 / max(n_br, 1)
+        res, elapsed, n_launch, kern_ms, su, collections, spans = run_m1(be, world, s_id, t_id, steps, warmup, barrier, drv, profile=args.full)
+        if args.full:
+            # what a hipEvent bracket costs by itself on this stream (two records back to back): the brackets around the pass launches include it
+            be.profile_enable(True)
+            for _ in range(200):
+                with be.span(0):
+                    pass
+            n_br, br_ms = be.span_read(0)
+            be.profile_enable(False)
+            bracket_s = br_ms * 1e-3 / max(n_br, 1)
         if world > 1:
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
         be.close()
+        spread = {"median": float(np.median(su)), "p10": float(np.percentile(su, 10)), "p90": float(np.percentile(su, 90)), "max": float(su.max()),
+                  "host_cpu": host_cpu(), "argmax": int(np.argmax(su)), "gc": collections}
+        if not args.full:
+            return dict(res=res, elapsed=elapsed, index_build_ms=index_build_ms, step_us=spread)
+        n_span, span_ms = spans
         avg_bracket_s = kern_ms * 1e-3 / max(n_launch, 1)
         bracket_kernel_s = max(avg_bracket_s - bracket_s, 1e-9)  # a bracket minus an empty one: over-subtracts; kept as a second figure
         passes = ICP_ITERS + 1
         avg_kernel_s = span_ms * 1e-3 / max(n_span, 1) / passes  # device span of a whole registration / its correspondence passes
         gbs = algo_bytes / avg_kernel_s / 1e9
-        spread = {"median": float(np.median(su)), "p10": float(np.percentile(su, 10)), "p90": float(np.percentile(su, 90)), "max": float(su.max()),
-                  "host_cpu": host_cpu(), "argmax": int(np.argmax(su)), "gc": collections}
         # (the pass launches of a step must fit inside the step they are part of: a roofline figure that does not invites distrust of the rest)
         # (the passes of a step must fit inside the step they are part of; the span is measured in a re-run of the steps, so a disturbed box --
         # or a profiler that serialises the kernels of one run differently from the other -- can break that by a few per cent: reported, not fatal)
@@ -1015,8 +1045,10 @@ def main():
                     avg_bracket_s=avg_bracket_s, bracket_overhead_s=bracket_s, bracket_kernel_s=bracket_kernel_s, span_fits=bool(span_fits))
 
     r32 = m1(backend.PRECISION_F32, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r32["res"])
     r64 = None
-    if not args.no_f64:
+    if args.full and not args.no_f64:
         try:
             r64 = m1(backend.PRECISION_F64, max(args.steps // 2, 1), args.warmup)
         except Exception as e:  # noqa: BLE001 -- a secondary leg: reported, never fatal to the line
@@ -1025,7 +1057,7 @@ def main():
     # as much again in cloud order, 36 MB of grid): configs[1]'s own working set (32 MB + 9 MB) is cache resident, so its counter readings
     # and its rate say nothing about HBM -- this line does
     r_big = None
-    if world == 1 and args.config == "1" and args.large_map > 0:
+    if args.full and world == 1 and args.config == "1" and args.large_map > 0:
         try:
             big = syn.sample_map(scene, args.large_map, seed=syn.SEED_MAP + 17)
             r_big = m1(backend.PRECISION_F32, max(args.steps // 4, 5), 3, target=big)
@@ -1036,7 +1068,7 @@ def main():
             r_big = None
 
     r_lib = None
-    if world == 1 and args.config == "1" and not args.no_f64:
+    if args.full and world == 1 and args.config == "1" and not args.no_f64:
         try:
             r_lib = m1(backend.PRECISION_F32, max(args.steps // 4, 5), 3, mode="source", library=True)
         except Exception as e:  # noqa: BLE001 -- an extra leg: it must not take the line down
@@ -1045,7 +1077,7 @@ def main():
     # (odometry, mapping and loop-closure workers register concurrently, SlamWrapper.cpp:258-347).  One 64k-query grid is a single wave of
     # workgroups and a registration is a chain of dependent launches, so one stream leaves most of the chip idle most of the time.
     conc = None
-    if world == 1 and args.config == "1" and args.concurrent > 1:
+    if args.full and world == 1 and args.config == "1" and args.concurrent > 1:
         import threading
 
         K = args.concurrent
@@ -1080,7 +1112,7 @@ def main():
             b.close()
     # measured device copy bandwidth on this box (report against the vendor peak AND a measured copy kernel)
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         nb = 1 << 30
         a_, b_ = torch.empty(nb, dtype=torch.uint8, device=f"cuda:{local_rank}"), torch.empty(nb, dtype=torch.uint8, device=f"cuda:{local_rank}")
         b_.copy_(a_)
@@ -1335,9 +1367,10 @@ def main():
             "joint_registration_iterations_per_sec": ICP_ITERS * steps / elapsed,
             "registrations_per_sec": steps / elapsed,
             "pose_error_vs_truth": {"dt_m": dt_gt, "dr_rad": dr_gt, "fitness": res["fitness"], "inlier_rmse": res["inlier_rmse"]},
-            "roofline": roof(r32),
             "step_us": r32["step_us"],  # spread of the timed steps on the host clock: a wide one means the enqueueing host thread was disturbed
         }
+        if args.full:
+            out["roofline"] = roof(r32)
         if r64 is not None:
             s64 = max(args.steps // 2, 1)
             d64 = syn.se3_error(r64["res"]["transformation"], res["transformation"])
@@ -1350,7 +1383,7 @@ def main():
                                    "n_map": r_big["n_map"], "index_build_ms": r_big["index_build_ms"], "roofline": roof(r_big, "icp_fused_kernel<P4f> 8 M-point map"),
                                    "pose_error_vs_truth": dict(zip(("dt_m", "dr_rad"), syn.se3_error(r_big["res"]["transformation"], T_gt))),
                                    "what": "the configs[1] scan against a map whose index (256 MB cell-sorted + 36 MB grid) exceeds the Infinity Cache"}
-        if world == 1 and args.config == "1" and not args.no_gicp:
+        if args.full and world == 1 and args.config == "1" and not args.no_gicp:
             try:
                 out["m1_gicp"] = run_m1_gicp(local_rank, src, tgt, nrm, max(args.steps // 2, 1), args.warmup, with_oracle=not args.no_cpu_baseline)
             except Exception as e:  # noqa: BLE001
@@ -1389,7 +1422,7 @@ def main():
                         calls_[row_name]["traffic"] = tsum(*pats)
                         calls_[row_name]["traffic_what"] = "sum over one launch each of: " + ", ".join(pats) + " (scans excluded)"
         cres, best_t = None, min(32, os.cpu_count() or 1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, cres, best_t = cpu_baseline_m1(src, tgt, nrm, args.cpu_budget)
             out["cpu_baseline"] = cb
             dt, dr = syn.se3_error(res["transformation"], cres["transformation"])

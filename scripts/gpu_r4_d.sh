@@ -12,7 +12,7 @@ for n in ("shared","unshared"):
     d=json.load(open("$OUT/patched_%s.json"%n)); print("patched reference", n, round(d["serial"]["scans_per_sec"]), round(d["two_threads"]["scans_per_sec"]))
 PY
 cp $OUT/patched_shared.json gpurun_out/patched_reference_stream.json
-for v in 1 0; do O3DS_SHARE_PREPROCESS=$v timeout 600 python bench.py --no-cpu-baseline --no-f64 --large-map 0 --concurrent 0 2>/dev/null | tail -1 > $OUT/bench_share$v.json; python - <<PY
+for v in 1 0; do O3DS_SHARE_PREPROCESS=$v timeout 600 python bench.py --full --no-cpu-baseline --no-f64 --large-map 0 --concurrent 0 2>/dev/null | tail -1 > $OUT/bench_share$v.json; python - <<PY
 import json
 d=json.load(open("$OUT/bench_share$v.json")); s=d["scans_per_sec"]; print("share=$v", round(d["value"]), round(s["scans_per_sec"]), s.get("host_seam"))
 PY

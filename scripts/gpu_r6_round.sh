@@ -14,12 +14,12 @@ if [ -z "$SKIP_TESTS" ]; then
   echo "pytest rc=${PIPESTATUS[0]}" >> $OUT/pytest_gpu.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" >> $OUT/smoke.log
 fi
-O3DS_BENCH_DETAIL=$OUT/bench_detail.json timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+O3DS_BENCH_DETAIL=$OUT/bench_detail.json timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?" >> $OUT/bench.err
-O3DS_BENCH_DETAIL=$OUT/bench_n2_gloo_detail.json O3DS_BENCH_BACKEND=gloo timeout 400 python bench.py --gpus 2 --steps 8 --warmup 2 2>/dev/null | grep '^{' | tail -1 > $OUT/bench_n2_gloo_all_configs.json
+O3DS_BENCH_DETAIL=$OUT/bench_n2_gloo_detail.json O3DS_BENCH_BACKEND=gloo timeout 400 python bench.py --full --gpus 2 --steps 8 --warmup 2 2>/dev/null | grep '^{' | tail -1 > $OUT/bench_n2_gloo_all_configs.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof
-O3DS_BENCH_DETAIL=$OUT/rocprof_bench_detail.json timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python $R/bench.py --no-cpu-baseline --no-host-seam > $OUT/rocprof_bench.json 2> $OUT/rocprof.err
+O3DS_BENCH_DETAIL=$OUT/rocprof_bench_detail.json timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python $R/bench.py --full --no-cpu-baseline --no-host-seam > $OUT/rocprof_bench.json 2> $OUT/rocprof.err
 echo "rocprof rc=$?" >> $OUT/rocprof.err
 python $R/scripts/prof_summary.py $OUT/prof/bench_results.db $OUT/rocprof_stats.txt > /dev/null
 # the stream alone: which kernels a frame is made of, and the order and timing of its dispatches (GPU-busy fraction of a frame)
@@ -29,7 +29,7 @@ python $R/scripts/prof_summary.py $OUT/prof_stream/s_results.db $OUT/rocprof_sta
 python $R/scripts/prof_sequence.py $OUT/prof_stream/s_results.db $OUT/stream_frame_sequence.txt 65 > /dev/null
 # configs[1] alone (the registrations `value` and `roofline` are quoted on): the fused kernel's average here is the bench line's avg_launch_us
 cd /tmp; rm -rf $OUT/prof_m1
-O3DS_BENCH_DETAIL=$OUT/rocprof_m1_detail.json timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m1 -o m1 -- python $R/bench.py --no-cpu-baseline --no-f64 --concurrent 0 --m2-frames 0 --large-map 0 --no-gicp > $OUT/rocprof_m1.json 2> /dev/null
+O3DS_BENCH_DETAIL=$OUT/rocprof_m1_detail.json timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m1 -o m1 -- python $R/bench.py --full --no-cpu-baseline --no-f64 --concurrent 0 --m2-frames 0 --large-map 0 --no-gicp > $OUT/rocprof_m1.json 2> /dev/null
 python $R/scripts/prof_summary.py $OUT/prof_m1/m1_results.db $OUT/rocprof_stats_m1.txt > /dev/null
 cd $R
 rm -rf $OUT/prof/*.db $OUT/prof_m1/*.db $OUT/prof_stream/*.db  # the summaries are what travels back

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_preprocess_map_gpu.py tests/test_pipelin
 echo "pytest rc=${PIPESTATUS[0]}" >> $OUT/voxel_ab_pytest.log
 for v in hash sort; do
   if [ $v = sort ]; then export O3DS_VOXEL_SORT=1; else unset O3DS_VOXEL_SORT; fi
-  timeout 400 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-f64 --concurrent 0 2>/dev/null | tail -1 > $OUT/voxel_ab_$v.json
+  timeout 400 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-f64 --concurrent 0 2>/dev/null | tail -1 > $OUT/voxel_ab_$v.json
 done
 tail -3 $OUT/voxel_ab_pytest.log
 python - <<'PY'

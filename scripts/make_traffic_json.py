@@ -3,7 +3,7 @@
 what bench.py quotes as roofline.traffic.  The calibration behind the byte-per-request figures is profiles/r03_pmc_calibration*.txt."""
 import collections, csv, glob, hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = {"source": "rocprofv3 --kernel-trace --pmc, one counter set per run, `python bench.py --steps 20 --warmup 3 --m2-frames 0 --no-cpu-baseline --concurrent 0 --no-gicp --no-host-seam` "
+out = {"source": "rocprofv3 --kernel-trace --pmc, one counter set per run, `python bench.py --full --steps 20 --warmup 3 --m2-frames 0 --no-cpu-baseline --concurrent 0 --no-gicp --no-host-seam` "
                  "(scripts/gpu_pmc_traffic.sh); per-launch means over the pass launches (the one-workgroup tail launches of the fused loop dropped)",
        "calibration": {"file": "profiles/r03_pmc_calibration_and_m1_traffic.txt",
                        "read_request_bytes": "TCC_EA0_RDREQ counts ONE request per 128-B line for coalesced / fully used lines (stream, aligned 128-B runs: requested bytes / "
@@ -42,7 +42,7 @@ def kernel_key(name):
     return name.split("(")[0][:60]
 
 
-# launches of the legs of `bench.py --steps 20 --warmup 3` in the order they run (12 per registration: 11 passes + the fold launch): a leg is
+# launches of the legs of `bench.py --full --steps 20 --warmup 3` in the order they run (12 per registration: 11 passes + the fold launch): a leg is
 # warm-up + timed steps + the bracketed re-run + the span re-run (round 6) registrations
 STEPS, WARMUP = 20, 3
 N32 = (WARMUP + STEPS + 2 * min(STEPS, 100)) * 12
