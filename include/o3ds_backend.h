@@ -141,6 +141,10 @@ int o3ds_cloud_free(o3ds_handle h, o3ds_cloud c);
  * number usually arrived with the next registration result and then costs nothing); n == NULL asks for has_normals only and never
  * waits.  Every call that sizes a host buffer or another cloud by the number (download, crop, select, transform, append ...) asks. */
 int o3ds_cloud_size(o3ds_handle h, o3ds_cloud c, size_t* n, int* has_normals);
+/* Elements of the neighbourhood-major replica of the cloud's nearest-neighbour index (9 per point), 0 if it has none.  The replica is
+ * built by the registration that is the fourth against the same index (an index a stream rebuilds every frame never gets one); it
+ * changes no result, only how fast the search runs. */
+int o3ds_cloud_index_replica(o3ds_handle h, o3ds_cloud c, size_t* elements);
 /* What is known of the size without waiting: lower <= n <= upper (equal once the number has arrived).  The reference's emptiness checks
  * (assert_gt(cloud.size(), 0), ScanToMapRegistration.cpp:51-52; preProcessedScan.IsEmpty(), Submap.cpp:41) are decided by the bounds:
  * a VoxelDownSample result whose input had a point inside the volume has lower = 1. */

@@ -80,6 +80,7 @@ SIGNATURES = {
     "o3ds_cloud_size_bound": (C.c_int, [_H, _CL, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "o3ds_cloud_free": (C.c_int, [_H, _CL]),
     "o3ds_cloud_size": (C.c_int, [_H, _CL, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "o3ds_cloud_index_replica": (C.c_int, [_H, _CL, C.POINTER(C.c_size_t)]),
     "o3ds_cloud_download": (C.c_int, [_H, _CL, _dp, _dp, C.c_size_t]),
     "o3ds_cloud_set_colors": (C.c_int, [_H, _CL, _dp]),
     "o3ds_cloud_has_colors": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
@@ -359,6 +360,12 @@ class Backend:
 
     def build_index(self, cid: int, max_corr_hint: float, cell_size: float = 0.0):
         self._ck(self.lib.o3ds_cloud_build_index(self.h, cid, max_corr_hint, cell_size))
+
+    def index_replica(self, cid: int) -> int:
+        """elements of the neighbourhood-major replica of the cloud's index (9 per point), 0 = none"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.o3ds_cloud_index_replica(self.h, cid, C.byref(n)))
+        return int(n.value)
 
     # -- ICP
     @staticmethod

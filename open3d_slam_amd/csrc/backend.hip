@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <climits>
 #include <cstring>
 #include <initializer_list>
 #include <map>
@@ -57,6 +58,10 @@ struct CloudRec {
   int* cell_start = nullptr;
   void* spts = nullptr;
   void* snrm = nullptr;
+  void* rpts = nullptr;     // the neighbourhood-major replica of spts (GridDev::rpts) and its tables; null: none
+  int* rstart = nullptr;
+  int* rpos = nullptr;
+  int index_regs = 0;       // registrations against this index so far (maybe_build_replica)
   // A box that is known to contain every point (not necessarily tight): set where a bounding box has been computed anyway
   // (VoxelDownSample, an index build) and carried to clouds derived from it (subsets, voxel means, rigid placements, unions), so
   // that the next index build of the per-scan pipeline does not pay a reduction kernel + read-back + host sync for it again.
@@ -145,6 +150,11 @@ struct PMapRec {
 
 constexpr int kMaxPassBlocks = 4096;  // capacity of the partial-record buffer (rows per pass <= pass_rows <= this)
 constexpr size_t kMaxCells = (size_t)1 << 27;  // 512 MiB of cell_start at most
+// The neighbourhood-major replica of a registration target's index (GridDev::rpts) is built when its points, their position map and its
+// table of super-row starts fit in this many bytes, the Infinity Cache, and the table has at most kMaxCells entries.  9 copies of every point: 180 MB
+// for the 1 M-point map with f32 storage (built: configs[1] +8 %); 1.44 GB for an 8 M-point map, whose stage-1 gathers then come from HBM
+// and lost 3 % (not built), 324 MB with f64 storage (no gain measured: not built).
+constexpr size_t kReplicaMaxBytes = (size_t)256 << 20;
 
 }  // namespace
 
@@ -603,8 +613,13 @@ void free_index(o3ds_handle h, CloudRec& c) {
   if (c.cell_start) dev_free(h, c.cell_start);
   if (c.spts) dev_free(h, c.spts);
   if (c.snrm) dev_free(h, c.snrm);
+  if (c.rpts) dev_free(h, c.rpts);
+  if (c.rstart) dev_free(h, c.rstart);
+  if (c.rpos) dev_free(h, c.rpos);
   c.cell_start = nullptr;
-  c.spts = c.snrm = nullptr;
+  c.spts = c.snrm = c.rpts = nullptr;
+  c.rstart = c.rpos = nullptr;
+  c.index_regs = 0;
   c.has_index = false;
   c.index_byproduct = false;
 }
@@ -933,6 +948,76 @@ double index_cell_div() {
 
 int build_index(o3ds_handle h, CloudRec& c, double cell) {
   return c.precision == O3DS_PRECISION_F64 ? build_index_t<P4d>(h, c, cell) : build_index_t<P4f>(h, c, cell);
+}
+
+// The neighbourhood-major replica of an index (GridDev::rpts), built from its cell-sorted points: one count, one scan and one scatter
+// (replica_count_kernel / replica_scatter_kernel).  Not built when it does not fit (kReplicaMaxBytes, kMaxCells) or the memory is not there:
+// the index then stays without one and the search takes the rows of cell_start.
+template <typename P4>
+int build_replica_t(o3ds_handle h, CloudRec& c) {
+  GridDev g = c.grid;
+  const size_t n = c.n, rcell = (size_t)g.nx * (size_t)(g.ny + 2) * (size_t)(g.nz + 2);  // super-row cells
+  if (rcell > kMaxCells || 9 * n > (size_t)INT_MAX || 9 * n * (sizeof(P4) + sizeof(int)) + sizeof(int) * (rcell + 1) > kReplicaMaxBytes) return O3DS_OK;
+  void* rpts = nullptr;
+  int *rstart = nullptr, *rpos = nullptr;
+  if (dev_alloc(h, (void**)&rstart, sizeof(int) * (rcell + 1)) != hipSuccess || dev_alloc(h, &rpts, sizeof(P4) * 9 * n) != hipSuccess ||
+      dev_alloc(h, (void**)&rpos, sizeof(int) * 9 * n) != hipSuccess) {
+    (void)hipGetLastError();
+    if (rstart) dev_free(h, rstart);
+    if (rpts) dev_free(h, rpts);
+    return O3DS_OK;
+  }
+  // counters: the handle's block of zeros, as in build_grid_t (counted up, scanned, counted back down to zero by the scatter)
+  if (h->cells_cap < rcell + 1) {
+    if (h->d_cells) {
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      (void)hipFree(h->d_cells);
+      h->d_cells = nullptr;
+      h->cells_cap = 0;
+    }
+    const size_t cap = rcell + 1 + rcell / 4;
+    if (hipMalloc((void**)&h->d_cells, sizeof(int) * cap) != hipSuccess) {
+      (void)hipGetLastError();
+      dev_free(h, rstart), dev_free(h, rpts), dev_free(h, rpos);
+      return O3DS_OK;
+    }
+    h->cells_cap = cap;
+    h->cells_clean = false;
+  }
+  static const bool always_clear = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;
+  if (!h->cells_clean || always_clear) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
+  h->cells_clean = false;
+  int* rcounts = h->d_cells;
+  const int* n_dev = c.lazy_slot >= 0 ? cnt_word(h, c.lazy_slot) : nullptr;
+  replica_count_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)c.spts, n, g, rcounts, n_dev);
+  const int rc = exclusive_scan_int(h, rcounts, rstart, rcell + 1);
+  if (rc) {
+    dev_free(h, rstart), dev_free(h, rpts), dev_free(h, rpos);
+    return rc;
+  }
+  replica_scatter_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)c.spts, n, g, rstart, rcounts, (P4*)rpts, rpos, n_dev);
+  HIP_TRY(hipGetLastError());
+  h->cells_clean = true;
+  c.rpts = rpts;
+  c.rstart = rstart;
+  c.rpos = rpos;
+  c.grid.rpts = rpts;
+  c.grid.rstart = rstart;
+  c.grid.rpos = rpos;
+  return O3DS_OK;
+}
+
+// The replica pays for itself only over repeated registrations against one index (its build costs about what seven or eight 10-pass
+// registrations of configs[1] save), so it is built at the kReplicaAfterRegs-th registration against an index, not with the index: the
+// indexes a stream rebuilds every frame (the scan a registration targets, a submap after each insertion) are registered against once and
+// never pay for it.  Row-paged (persistent-map) indexes have none.  O3DS_NN_REPLICA_AFTER=<k> (A/B library): at the k-th registration.
+constexpr int kReplicaAfterRegs = 4;
+int maybe_build_replica(o3ds_handle h, CloudRec& c) {
+  if (!c.has_index || c.rpts || c.pm || c.index_positions) return O3DS_OK;
+  const char* e = ab_getenv("O3DS_NN_REPLICA_AFTER");
+  const int after = e ? std::max(1, atoi(e)) : kReplicaAfterRegs;
+  if (++c.index_regs < after) return O3DS_OK;
+  return c.precision == O3DS_PRECISION_F64 ? build_replica_t<P4d>(h, c) : build_replica_t<P4f>(h, c);
 }
 
 // f32 storage: the caller's doubles are narrowed on their way into the pinned ring (the narrowing the device would do: round to nearest
@@ -1365,7 +1450,13 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   a.count = src->n;
   a.tpts = tgt->spts;
   a.tnrm = tgt->snrm;
+  rc = maybe_build_replica(h, *tgt);
+  if (rc) return rc;
   a.grid = tgt->grid;
+  {  // A/B switch: O3DS_NN_REPLICA=0 searches the rows of cell_start although the index has a replica (read at every registration)
+    const char* e = ab_getenv("O3DS_NN_REPLICA");
+    if (e && atoi(e) == 0) a.grid.rpts = nullptr, a.grid.rstart = a.grid.rpos = nullptr;
+  }
   a.crop = to_dev(crop);
   const double r = params->max_correspondence_distance;
   a.r2max = r * r;
@@ -1843,6 +1934,15 @@ int o3ds_cloud_size(o3ds_handle h, o3ds_cloud id, size_t* n, int* has_normals) {
   }
   if (n) *n = c->n;
   if (has_normals) *has_normals = c->nrm != nullptr;
+  return O3DS_OK;
+}
+
+int o3ds_cloud_index_replica(o3ds_handle h, o3ds_cloud id, size_t* elements) {
+  CHECK_HANDLE(h);
+  CloudRec* c = find_cloud_lazy(h, id);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_index_replica: unknown cloud id");
+  if (!elements) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_index_replica: null output");
+  *elements = c->rpts ? 9 * c->n : 0;
   return O3DS_OK;
 }
 

@@ -132,6 +132,13 @@ struct GridDev {
   const int* cell_start;  // nx*ny*nz + 1 entries (exclusive scan of per-cell counts)
   int sx;                 // entries per row of cell_start: nx (the classic table), or nx + 1 for the row-paged table of a persistent map
                           // (map_kernels.hpp: every row owns a region with room to spare, the extra entry is the end of its last cell)
+  // Optional neighbourhood-major replica of the cell-sorted points (icp_kernels.hpp, "super-rows"): super-row (y, z), y in [-1, ny],
+  // z in [-1, nz], holds every point of the rows (y + dy, z + dz), dy, dz in {-1, 0, 1}, sorted by cell x, so that the 3x3x3 block of
+  // any cell is ONE range [rstart(x - 1), rstart(x + 2)).  Elements keep the original index in .i; rpos maps a replica position to the
+  // position of the same point in the cell-sorted arrays.  Null: no replica (every search takes the rows of cell_start).
+  const void* rpts;       // P4[9 n]
+  const int* rstart;      // (nz + 2) (ny + 2) nx + 1 entries
+  const int* rpos;        // [9 n]
 };
 
 // ---- counts the host has not seen yet ---------------------------------------------------------------------------------------------

@@ -242,6 +242,60 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(const P4* __restrict__ 
   }
 }
 
+// ---- the neighbourhood-major replica (GridDev::rpts): every point goes into the 9 super-rows (y - dy, z - dz), dy, dz in {-1, 0, 1}, at
+// its own cell x.  Both kernels walk the CELL-SORTED points, so a run of equal cells is a whole cell (one atomic per super-row and run)
+// and the canonical position of a point is its index.  Super-row (Y, Z) is row (Y + 1, Z + 1) of a table with ny + 2 rows per plane.
+__device__ __forceinline__ int replica_cell(const GridDev& g, int c, int k /* image 0..8 */) {
+  const int x = c % g.nx, yz = c / g.nx, y = yz % g.ny, z = yz / g.ny;
+  const int Y1 = y + 1 - (k % 3 - 1), Z1 = z + 1 - (k / 3 - 1);  // (Y + 1, Z + 1), in [0, ny + 1] x [0, nz + 1]
+  return (Z1 * (g.ny + 2) + Y1) * g.nx + x;
+}
+template <typename P4>
+__global__ __launch_bounds__(kBlock) void replica_count_kernel(const P4* __restrict__ spts, size_t n, GridDev g, int* __restrict__ rcounts,
+                                                               const int* __restrict__ n_dev = nullptr) {
+  if (n_dev) n = (size_t)*n_dev;
+  const int lane = threadIdx.x & 63;
+  for (size_t i0 = (size_t)blockIdx.x * kBlock; i0 < n; i0 += (size_t)gridDim.x * kBlock) {
+    const size_t j = i0 + threadIdx.x;
+    const int c = j < n ? cell_of(g, spts[j]) : -1;
+    int len, lead_lane;
+    if (cell_run(c, lane, &len, &lead_lane)) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) atomicAdd(&rcounts[replica_cell(g, c, k)], len);
+    }
+  }
+}
+template <typename P4>
+__global__ __launch_bounds__(kBlock) void replica_scatter_kernel(const P4* __restrict__ spts, size_t n, GridDev g, const int* __restrict__ rstart,
+                                                                 int* __restrict__ rcounts, P4* __restrict__ rpts, int* __restrict__ rpos,
+                                                                 const int* __restrict__ n_dev = nullptr) {
+  if (n_dev) n = (size_t)*n_dev;
+  const int lane = threadIdx.x & 63;
+  for (size_t i0 = (size_t)blockIdx.x * kBlock; i0 < n; i0 += (size_t)gridDim.x * kBlock) {
+    const size_t j = i0 + threadIdx.x;
+    P4 p{};
+    int c = -1;
+    if (j < n) {
+      p = spts[j];
+      c = cell_of(g, p);
+    }
+    int len, lead_lane;
+    const bool lead = cell_run(c, lane, &len, &lead_lane);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int rc = c >= 0 ? replica_cell(g, c, k) : 0;
+      int old = 0;
+      if (lead) old = atomicSub(&rcounts[rc], len);
+      old = __shfl(old, lead_lane, 64);
+      if (j < n) {
+        const int q = rstart[rc] + old - 1 - (lane - lead_lane);
+        rpts[q] = p;
+        rpos[q] = (int)j;
+      }
+    }
+  }
+}
+
 // ----------------------------------------------------------------------------------------------
 // exact 1-NN within radius on the grid ([O3D] KDTreeFlann::SearchHybrid(q, r, 1)), G lanes per query
 // ----------------------------------------------------------------------------------------------
@@ -311,7 +365,9 @@ __device__ __forceinline__ void collect_push(const Collect<R>& c, int p) {
 // candidates s+lane, s+lane+stride, ... of [s,e): four loads issued before the first is consumed (two with f64 storage: a
 // candidate is eight registers there, and four in flight pushed the kernel over its register budget -- spills that the compiler
 // places inside divergent regions, which is not safe: a value stored under a narrow EXEC mask and reloaded under a wider one)
-template <typename P4, bool kCrop, bool kCollect>
+// kRep: [s, e) is a range of the replica (GridDev::rpts); a listed candidate then goes into the list as -2 - (replica position), which the
+// writer of the set maps to the canonical position (rpos) -- one lookup per kept set instead of one per listed candidate
+template <typename P4, bool kCrop, bool kCollect, bool kRep = false>
 __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, int e, int lane, int stride, typename Scalar<P4>::type qx,
                                              typename Scalar<P4>::type qy, typename Scalar<P4>::type qz, const CropDev& crop,
                                              NNBest<P4>& best, const Collect<typename Scalar<P4>::type>& col) {
@@ -339,7 +395,7 @@ __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, i
       if (dmin < col.tau2) {
 #pragma unroll
         for (int k = 0; k < kInFlight; ++k)
-          if (vk[k] & (dk[k] < col.tau2)) collect_push(col, pk[k]);
+          if (vk[k] & (dk[k] < col.tau2)) collect_push(col, kRep ? -2 - pk[k] : pk[k]);
       }
     }
   }
@@ -369,7 +425,8 @@ __device__ __forceinline__ void lanes_min(NNBest<P4>& b) {
 //            millimetres near convergence, so the ball usually covers one or two cells.  Any target point is a valid
 //            bound, so a stale entry can cost time but never correctness; pass 0 of a registration starts from r;
 //   stage 1  the 3x3x3 block, every row trimmed to the x-extent of the ball at that row (rows out of reach vanish).
-//            Proven exact if best <= cell * (1 + distance to the nearest face);
+//            Proven exact if best <= cell * (1 + distance to the nearest face).  With the index's replica (GridDev::rpts) the
+//            block is ONE range of a super-row instead: no per-row geometry, no segment list, ceil(candidates / 16) rounds;
 //   stage 2  (only if not proven) the 5x5x5 shell, trimmed the same way.  Proven if best <= cell * (2 + face distance);
 //   stage 3  (nearest neighbour farther than two cells) the whole wavefront serves the query, nn_search_wave_far.
 // All cell_start values stage 1 can need (9 rows x 4) are fetched in ONE batch together with the cached match; stage 2
@@ -474,52 +531,83 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
   // ---- one batch, issued before the bound is even computed: the 4 cell_start values of each of this lane's rows of the 3x3
   // cross-section (fetching only the rows in reach, after the bound, measured slower: the ALU chain delays the loads)
   const int xlo = max(c.ix - 1, 0), xhi = min(c.ix + 1, g.nx - 1);
-  constexpr int kOwn = (9 + G - 1) / G;
-  int v[kOwn][4];
-  bool rv[kOwn];
+  if (g.rpts) {
+    // ---- stage 1 on the replica: the 3x3x3 block is ONE range of super-row (iy, iz), trimmed by the x-extent of the ball at its
+    // widest row (distance 0).  The cells this keeps beyond today's per-row trim hold points farther than the bound + m, so they can
+    // neither win nor enter the candidate set (tau = bound + m at this point).  Its cell_start pair is fetched before the bound.
+    const P4* __restrict__ rp = (const P4*)g.rpts;
+    const bool sv = xlo <= xhi && (unsigned)(c.iy + 1) < (unsigned)(g.ny + 2) && (unsigned)(c.iz + 1) < (unsigned)(g.nz + 2);
+    const int srow = sv ? ((c.iz + 1) * (g.ny + 2) + (c.iy + 1)) * g.nx : 0;
+    int v[4];
 #pragma unroll
-  for (int k = 0; k < kOwn; ++k) {
-    const int r = gl + k * G;
-    const int y = c.iy + (r % 3) - 1, z = c.iz + (r / 3) - 1;
-    rv[k] = r < 9 && xlo <= xhi && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz;
-    const int row = rv[k] ? (z * g.ny + y) * g.sx : 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[k][j] = rv[k] ? cs[row + min(xlo + j, xhi + 1)] : 0;
-  }
-  // ---- stage 1: the 3x3x3 block, trimmed by the bound
-  {
+    for (int j = 0; j < 4; ++j) v[j] = sv ? g.rstart[srow + min(xlo + j, xhi + 1)] : 0;
+    // the starting bound is made group-uniform, so that every lane can tell whether the winner is still it (a canonical position) or a
+    // replica element (mapped back through rpos below)
+    lanes_min<P4, G>(best);
+    const int pos0 = best.pos;
+    const auto idx0 = best.idx;
     const float b2 = bound_cells2(best.d2, m, g);
-    int ss[kOwn], ee[kOwn];
-    int cnt = 0;
+    int s = 0, e = 0, xa, xb;
+    if (sv && row_extent(b2, 0.0f, c.ux, &xa, &xb)) {
+      xa = max(c.ix + xa, xlo);
+      xb = min(c.ix + xb, xhi);
+      if (xa <= xb) {
+        const int ja = xa - xlo, jb = xb - xlo + 1;
+        s = ja == 0 ? v[0] : (ja == 1 ? v[1] : v[2]);
+        e = jb == 1 ? v[1] : (jb == 2 ? v[2] : v[3]);
+      }
+    }
+    scan_strided<P4, kCrop, kCollect, true>(rp, s, e, gl, G, qx, qy, qz, crop, best, col);
+    lanes_min<P4, G>(best);
+    if (best.pos != -1 && !(pos0 != -1 && best.idx == idx0)) best.pos = g.rpos[best.pos];
+  } else {
+    constexpr int kOwn = (9 + G - 1) / G;
+    int v[kOwn][4];
+    bool rv[kOwn];
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) {
       const int r = gl + k * G;
-      const float ddy = slab_dist((r % 3) - 1, c.uy), ddz = slab_dist((r / 3) - 1, c.uz);
-      int xa, xb;
-      ss[k] = ee[k] = 0;
-      if (rv[k] && row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb)) {
-        xa = max(c.ix + xa, xlo);
-        xb = min(c.ix + xb, xhi);
-        if (xa <= xb) {
-          const int ja = xa - xlo, jb = xb - xlo + 1;
-          ss[k] = ja == 0 ? v[k][0] : (ja == 1 ? v[k][1] : v[k][2]);
-          ee[k] = jb == 1 ? v[k][1] : (jb == 2 ? v[k][2] : v[k][3]);
-        }
-      }
-      cnt += ee[k] > ss[k] ? 1 : 0;
-    }
-    int total;
-    int off = group_exclusive_sum<G>(cnt, gl, &total);
+      const int y = c.iy + (r % 3) - 1, z = c.iz + (r / 3) - 1;
+      rv[k] = r < 9 && xlo <= xhi && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz;
+      const int row = rv[k] ? (z * g.ny + y) * g.sx : 0;
 #pragma unroll
-    for (int k = 0; k < kOwn; ++k)
-      if (ee[k] > ss[k]) seg[off++] = make_int2(ss[k], ee[k]);
-    lds_wave_sync();
-    for (int t = 0; t < total; ++t) {
-      const int2 se = seg[t];
-      scan_strided<P4, kCrop, kCollect>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
+      for (int j = 0; j < 4; ++j) v[k][j] = rv[k] ? cs[row + min(xlo + j, xhi + 1)] : 0;
     }
-    lds_wave_sync();  // the list is rewritten by stage 2
-    lanes_min<P4, G>(best);
+    // ---- stage 1: the 3x3x3 block, trimmed by the bound
+    {
+      const float b2 = bound_cells2(best.d2, m, g);
+      int ss[kOwn], ee[kOwn];
+      int cnt = 0;
+#pragma unroll
+      for (int k = 0; k < kOwn; ++k) {
+        const int r = gl + k * G;
+        const float ddy = slab_dist((r % 3) - 1, c.uy), ddz = slab_dist((r / 3) - 1, c.uz);
+        int xa, xb;
+        ss[k] = ee[k] = 0;
+        if (rv[k] && row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb)) {
+          xa = max(c.ix + xa, xlo);
+          xb = min(c.ix + xb, xhi);
+          if (xa <= xb) {
+            const int ja = xa - xlo, jb = xb - xlo + 1;
+            ss[k] = ja == 0 ? v[k][0] : (ja == 1 ? v[k][1] : v[k][2]);
+            ee[k] = jb == 1 ? v[k][1] : (jb == 2 ? v[k][2] : v[k][3]);
+          }
+        }
+        cnt += ee[k] > ss[k] ? 1 : 0;
+      }
+      int total;
+      int off = group_exclusive_sum<G>(cnt, gl, &total);
+#pragma unroll
+      for (int k = 0; k < kOwn; ++k)
+        if (ee[k] > ss[k]) seg[off++] = make_int2(ss[k], ee[k]);
+      lds_wave_sync();
+      for (int t = 0; t < total; ++t) {
+        const int2 se = seg[t];
+        scan_strided<P4, kCrop, kCollect>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
+      }
+      lds_wave_sync();  // the list is rewritten by stage 2
+      lanes_min<P4, G>(best);
+    }
   }
   // proven exact if nothing outside the scanned block can be nearer: best <= (cell * (k + face distance))^2, tested with margin
   // (with a candidate-set margin: if the ball of best + m lies inside the block)
@@ -1172,6 +1260,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
       const int n_listed = my_set[0];
       const bool have = m > (R)0 && n_listed <= kSetCap;
       int pos_out = have ? (gl < n_listed ? my_set[1 + gl] : -1) : (gl == 0 ? nn.pos : -1);
+      if (pos_out < -1) pos_out = a.grid.rpos[-2 - pos_out];  // listed from the replica (scan_strided, kRep)
       a.set_pos[(a.first + i) * kSetCap + gl] = pos_out;
       if (gl == 0) {
         const R qx = (R)px, qy = (R)py, qz = (R)pz;
