@@ -485,6 +485,70 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
 int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const double T[16], double map_voxel_size,
                          const o3ds_crop* map_builder_crop, double max_corr_hint);
 
+/* ---- place recognition: PlaceRecognition::buildLoopClosureConstraints' front half (src/PlaceRecognition.cpp:71-90) ---------------
+ * [O3D] ComputeFPFHFeature(cloud, KDTreeSearchParamHybrid(radius, max_nn)) as Submap::computeFeatures calls it (src/Submap.cpp:228-248):
+ * the neighbourhood of point i is the max_nn smallest (d2, index) among the points with d2 < radius^2, i itself included (the set
+ * o3ds_estimate_normals keeps); 33 bins per point, f64 arithmetic whatever the storage precision.  The cloud must have normals
+ * (O3DS_ERR_INVALID_ARG otherwise), 1 <= max_nn <= 128.  The n x 33 doubles are kept on the cloud like its normals and dropped by every
+ * call that changes the cloud's points or normals in place; a buffer beyond the handle's pool cap (O3DS_POOL_CAP_MB) is
+ * O3DS_ERR_CAPACITY.  download_fpfh: n x 33 row-major doubles, capacity in points. */
+int o3ds_compute_fpfh(o3ds_handle h, o3ds_cloud cloud, double radius, int max_nn);
+int o3ds_cloud_has_fpfh(o3ds_handle h, o3ds_cloud cloud, int* has_fpfh);
+int o3ds_cloud_download_fpfh(o3ds_handle h, o3ds_cloud cloud, double* out, size_t capacity);
+/* The correspondences of [O3D] RegistrationRANSACBasedOnFeatureMatching: for every source point i, j = the target point whose feature
+ * is nearest (sum over the 33 bins of the squared difference, f64, ties to the lower index).  mutual_filter: keep (i, j) only where
+ * the nearest source feature of j is i, in source order; fewer than 3 ransac_n such pairs falls back to the one-way set
+ * (*fell_back = 1).  pairs: [n][2] (source, target) with room for capacity pairs; *n_pairs is set even when the buffer is too small
+ * (O3DS_ERR_CAPACITY).  Both clouds need features. */
+int o3ds_feature_correspondences(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, int mutual_filter, int ransac_n, uint32_t* pairs,
+                                 size_t capacity, size_t* n_pairs, int* fell_back);
+/* [O3D] RegistrationRANSACBasedOnFeatureMatching(source, target, features, mutual_filter, max_correspondence_distance,
+ * TransformationEstimationPointToPoint(false), ransac_n, {CorrespondenceCheckerBasedOnEdgeLength(edge_length),
+ * CorrespondenceCheckerBasedOnDistance(distance)}, RANSACConvergenceCriteria(max_iteration, confidence)).
+ *   sampling   hypothesis t draws correspondence indices mix(seed + (ransac_n t + j + 1) 0x9E3779B97F4A7C15) mod m, j < ransac_n (with
+ *              replacement; mix = splitmix64's finaliser, as o3ds_random_down_sample).  Open3D seeds from std::random_device -- there
+ *              is no sequence to reproduce --; here the result is a function of (clouds, features, parameters, seed) alone.
+ *   estimate   Umeyama without scaling over the sample; the checkers run where their threshold is > 0.
+ *   validate   every source point placed by T, its nearest target point with d2 < max_correspondence_distance^2; fitness = pairs /
+ *              n_src, rmse = sqrt(sum d2 / pairs).  Better = more pairs, then lower rmse, then lower t.
+ *   stopping   Open3D's loop read in index order: est_k = max_iteration; t runs iff t < est_k; when t improves the best,
+ *              est_k = ceil(log(1 - confidence) / log(1 - fitness^ransac_n)) if that is below est_k (confidence clamped to [0, 1]).
+ *              The device evaluates hypotheses in batches and folds each batch in index order: the cut and the winner are the serial
+ *              rule's for any batch size.
+ * ransac_n < 3, fewer correspondences than ransac_n or max_correspondence_distance <= 0: Open3D's empty RegistrationResult (identity,
+ * zeros, best_t = -1).  ransac_n > 8: O3DS_ERR_INVALID_ARG.  trace (may be NULL): entry t < trace_cap describes hypothesis t; entries of
+ * hypotheses that did not run have checks = -1. */
+typedef struct {
+  int32_t mutual_filter;
+  int32_t ransac_n;                   /* ransacModelSize_ */
+  double max_correspondence_distance; /* ransacMaxCorrespondenceDistance_ */
+  double edge_length;                 /* correspondenceCheckerEdgeLength_ (similarity), <= 0: no checker */
+  double distance;                    /* correspondenceCheckerDistance_, <= 0: no checker */
+  int64_t max_iteration;              /* ransacNumIter_ */
+  double confidence;                  /* ransacProbability_ */
+} o3ds_ransac_params;
+typedef struct {
+  double transformation[16]; /* column-major */
+  double fitness;
+  double inlier_rmse;
+  uint64_t n_corr;           /* correspondence_set_.size() of the result */
+  uint64_t n_feature_corr;   /* feature correspondences RANSAC drew from */
+  int64_t iterations_run;    /* hypotheses the serial rule runs */
+  int64_t validations;       /* of which passed both checkers and were validated */
+  int64_t best_t;            /* the winner, -1 = none */
+  int32_t fell_back;         /* the mutual set was too small */
+  int32_t reserved;
+} o3ds_ransac_result;
+typedef struct {
+  uint32_t sample[8];        /* correspondence indices drawn (ransac_n of them) */
+  int32_t checks;            /* bit 0: edge length passed (or off), bit 1: distance passed (or off); -1: not run */
+  int32_t pairs;             /* validated: correspondences found; -1: not validated */
+  double error_sum;          /* validated: sum of d2 */
+  double transformation[16]; /* the estimate, column-major */
+} o3ds_ransac_trace;
+int o3ds_ransac_feature_matching(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_ransac_params* params, uint64_t seed,
+                                 o3ds_ransac_result* out, o3ds_ransac_trace* trace, size_t trace_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,24 @@ class CarvingParams(C.Structure):  # o3ds_carving_params (SpaceCarvingParameters
 
 OVERLAP_FN = C.CFUNCTYPE(None, C.c_void_p)  # o3ds_overlap_fn
 
+FPFH_DIM = 33
+
+
+class RansacParams(C.Structure):  # o3ds_ransac_params
+    _fields_ = [("mutual_filter", C.c_int32), ("ransac_n", C.c_int32), ("max_correspondence_distance", C.c_double),
+                ("edge_length", C.c_double), ("distance", C.c_double), ("max_iteration", C.c_int64), ("confidence", C.c_double)]
+
+
+class RansacResult(C.Structure):  # o3ds_ransac_result
+    _fields_ = [("transformation", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("n_corr", C.c_uint64),
+                ("n_feature_corr", C.c_uint64), ("iterations_run", C.c_int64), ("validations", C.c_int64), ("best_t", C.c_int64),
+                ("fell_back", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RansacTrace(C.Structure):  # o3ds_ransac_trace
+    _fields_ = [("sample", C.c_uint32 * 8), ("checks", C.c_int32), ("pairs", C.c_int32), ("error_sum", C.c_double),
+                ("transformation", C.c_double * 16)]
+
 SIGNATURES = {
     "o3ds_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
     "o3ds_destroy": (C.c_int, [_H]),
@@ -140,6 +158,13 @@ SIGNATURES = {
     "o3ds_cloud_copy_across": (C.c_int, [_H, _H, _CL, C.POINTER(_CL)]),
     "o3ds_voxelize_within_volume": (C.c_int, [_H, _CL, C.c_double, C.POINTER(Crop)]),
     "o3ds_map_insert_scan": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.POINTER(Crop), C.c_double]),
+    "o3ds_compute_fpfh": (C.c_int, [_H, _CL, C.c_double, C.c_int]),
+    "o3ds_cloud_has_fpfh": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
+    "o3ds_cloud_download_fpfh": (C.c_int, [_H, _CL, _dp, C.c_size_t]),
+    "o3ds_feature_correspondences": (C.c_int, [_H, _CL, _CL, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_int)]),
+    "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
+                                               C.POINTER(RansacTrace), C.c_size_t]),
 }
 
 _lib = None
@@ -777,3 +802,52 @@ class Backend:
     def map_insert_scan(self, map_id: int, scan_id: int, T, map_voxel: float, crop: Crop, max_corr_hint: float = 0.0):
         Tc, tp = _d(colmajor(T))
         self._ck(self.lib.o3ds_map_insert_scan(self.h, map_id, scan_id, tp, map_voxel, C.byref(crop), max_corr_hint))
+
+    # -- place recognition (o3ds_compute_fpfh, o3ds_feature_correspondences, o3ds_ransac_feature_matching)
+    def compute_fpfh(self, cid: int, radius: float, max_nn: int):
+        """[O3D] ComputeFPFHFeature(cloud, KDTreeSearchParamHybrid(radius, max_nn)); the features stay on the device cloud."""
+        self._ck(self.lib.o3ds_compute_fpfh(self.h, cid, float(radius), int(max_nn)))
+
+    def has_fpfh(self, cid: int) -> bool:
+        v = C.c_int()
+        self._ck(self.lib.o3ds_cloud_has_fpfh(self.h, cid, C.byref(v)))
+        return bool(v.value)
+
+    def fpfh(self, cid: int) -> np.ndarray:
+        """(n, 33) features, row-major (Open3D's Feature::data_ is 33 x n)."""
+        n, _ = self.size(cid)
+        out = np.zeros((n, FPFH_DIM))
+        self._ck(self.lib.o3ds_cloud_download_fpfh(self.h, cid, out.ctypes.data_as(_dp) if n else None, n))
+        return out
+
+    def feature_correspondences(self, source: int, target: int, mutual: bool = True, ransac_n: int = 3):
+        """((k, 2) uint32 (source, target) pairs, fell_back)"""
+        cap = self.size(source)[0]
+        buf = np.zeros((max(cap, 1), 2), np.uint32)
+        n, fb = C.c_size_t(0), C.c_int(0)
+        self._ck(self.lib.o3ds_feature_correspondences(self.h, source, target, int(bool(mutual)), int(ransac_n),
+                                                       buf.ctypes.data_as(C.POINTER(C.c_uint32)), cap, C.byref(n), C.byref(fb)))
+        return buf[: n.value].copy(), bool(fb.value)
+
+    def ransac_feature_matching(self, source: int, target: int, max_corr: float, ransac_n: int = 3, mutual: bool = True,
+                                edge_length: float = 0.0, distance: float = 0.0, max_iteration: int = 100000, confidence: float = 0.999,
+                                seed: int = 0, trace: int = 0) -> dict:
+        """[O3D] RegistrationRANSACBasedOnFeatureMatching with point-to-point estimation and the edge-length / distance checkers
+        (a threshold <= 0 leaves its checker out).  trace = number of hypotheses to record (the dict then has 'trace')."""
+        p = RansacParams()
+        p.mutual_filter, p.ransac_n = int(bool(mutual)), int(ransac_n)
+        p.max_correspondence_distance, p.edge_length, p.distance = float(max_corr), float(edge_length), float(distance)
+        p.max_iteration, p.confidence = int(max_iteration), float(confidence)
+        out = RansacResult()
+        tr = (RansacTrace * trace)() if trace else None
+        self._ck(self.lib.o3ds_ransac_feature_matching(self.h, source, target, C.byref(p), C.c_uint64(int(seed) & (2**64 - 1)),
+                                                       C.byref(out), tr, int(trace)))
+        r = dict(transformation=from_colmajor(out.transformation), fitness=out.fitness, inlier_rmse=out.inlier_rmse, n_corr=int(out.n_corr),
+                 n_feature_corr=int(out.n_feature_corr), iterations_run=int(out.iterations_run), validations=int(out.validations),
+                 best_t=int(out.best_t), fell_back=bool(out.fell_back))
+        if trace:
+            a = np.ctypeslib.as_array(tr)
+            r["trace"] = dict(sample=a["sample"][:, :ransac_n].astype(np.int64) if ransac_n > 0 else np.zeros((trace, 0), np.int64),
+                              checks=a["checks"].astype(np.int64), pairs=a["pairs"].astype(np.int64), error_sum=a["error_sum"].copy(),
+                              transformation=np.stack([from_colmajor(a["transformation"][k].copy()) for k in range(trace)]))
+        return r

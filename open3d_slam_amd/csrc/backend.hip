@@ -22,6 +22,7 @@
 
 #include "cloud_kernels.hpp"
 #include "common.hpp"
+#include "feature_kernels.hpp"
 #include "icp_kernels.hpp"
 #include "map_kernels.hpp"
 #include "normals_kernel.hpp"
@@ -90,6 +91,10 @@ struct CloudRec {
   bool box_padded = false;  // the box already has a margin against the rounding of derived values (never padded twice: a map is
                             // re-voxelised at every insertion and its box must not creep outwards over a long mission)
   double bmn[3] = {0, 0, 0}, bmx[3] = {0, 0, 0};
+  // FPFH features (o3ds_compute_fpfh): n x 33 doubles, row-major; dropped by every operation that changes the points or normals in place
+  double* fpfh = nullptr;
+  bool has_fpfh = false;
+  size_t fpfh_n = 0;
 };
 
 void box_inflate(CloudRec& c) {  // stored values are rounded (f32 storage, f64 -> f32 of means / placements): keep the box conservative
@@ -725,7 +730,18 @@ void pm_release(o3ds_handle h, CloudRec& c) {  // the persistent form's own bloc
   c.pm = nullptr;
   c.index_positions = 0;
 }
+void free_fpfh(o3ds_handle h, CloudRec& c) {
+  if (c.fpfh) dev_free(h, c.fpfh);
+  c.fpfh = nullptr;
+  c.has_fpfh = false;
+  c.fpfh_n = 0;
+}
+void drop_fpfh(o3ds_handle h, o3ds_cloud id) {  // the entry points that change a cloud in place
+  auto it = h->clouds.find(id);
+  if (it != h->clouds.end()) free_fpfh(h, it->second);
+}
 void free_cloud(o3ds_handle h, CloudRec& c) {
+  free_fpfh(h, c);
   pm_release(h, c);
   free_index(h, c);
   free_points(h, c);
@@ -3508,6 +3524,7 @@ int o3ds_crop_voxel_down_sample(o3ds_handle h, o3ds_cloud in, const o3ds_crop* c
 
 int o3ds_estimate_normals(o3ds_handle h, o3ds_cloud id, double radius, int max_nn) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, id);
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud_lazy(h, id);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "estimate_normals: unknown cloud id");
@@ -3594,6 +3611,7 @@ int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_
 
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, map);
   ArenaScope arena_scope(h);
   CloudRec* m = find_cloud(h, map);
   CloudRec* a = find_cloud(h, add);
@@ -4091,6 +4109,7 @@ extern "C" {
 
 int o3ds_voxelize_within_volume(o3ds_handle h, o3ds_cloud map, double voxel_size, const o3ds_crop* crop) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, map);
   ArenaScope arena_scope(h);
   return voxelize_within_volume_impl(h, map, voxel_size, crop);
 }
@@ -4098,6 +4117,7 @@ int o3ds_voxelize_within_volume(o3ds_handle h, o3ds_cloud map, double voxel_size
 int o3ds_cloud_undistort(o3ds_handle h, o3ds_cloud cloud, const double linear_velocity[3], const double angular_velocity_rpy[3],
                          double scan_duration, int spinning_clockwise) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, cloud);
   CloudRec* c = find_cloud(h, cloud);
   if (!c || !linear_velocity || !angular_velocity_rpy) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_undistort: bad argument");
   if (!(scan_duration > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "lidar scanDuration_: must be > 0");  // MotionCompensation.cpp:62
@@ -4378,6 +4398,7 @@ int o3ds_map_carve(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, const dou
 int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, const double map_to_range_sensor[16], const o3ds_crop* map_builder_crop,
                            const o3ds_carving_params* params, size_t* n_removed, o3ds_cloud* removed_out) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, map);
   ArenaScope arena_scope(h);
   {  // a submap in its persistent form is carved where it is when the carving voxel is the map's (the voxel hash is the reference's table)
     CloudRec* pmc = find_cloud_lazy(h, map);
@@ -4444,6 +4465,7 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
 int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const double T[16], double map_voxel_size,
                          const o3ds_crop* map_builder_crop, double max_corr_hint) {
   CHECK_HANDLE(h);
+  drop_fpfh(h, map);
   ArenaScope arena_scope(h);
   CloudRec* m = find_cloud_lazy(h, map);  // (a map in its persistent form stays in it)
   CloudRec* s = find_cloud_lazy(h, scan);
@@ -4542,5 +4564,327 @@ int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const d
 }
 
 }  // extern "C"
+
+// ---- place recognition: FPFH, feature correspondences, RANSAC (feature_kernels.hpp) ---------------------------------------------
+namespace {
+
+size_t pool_cap_bytes() {  // the same cap dev_free applies to the handle's cached blocks
+  static const size_t cap = (getenv("O3DS_POOL_CAP_MB") ? (size_t)atoll(getenv("O3DS_POOL_CAP_MB")) : (size_t)32768) << 20;
+  return cap;
+}
+
+template <typename P4>
+int fpfh_t(o3ds_handle h, CloudRec& c, double radius, int max_nn) {
+  const size_t n = c.n;
+  free_fpfh(h, c);
+  if (n > (size_t)INT_MAX / 2) return fail(h, O3DS_ERR_CAPACITY, "compute_fpfh: cloud too large");
+  const size_t feat_bytes = n * kFeatDim * sizeof(double), list_bytes = n * (size_t)max_nn * (sizeof(int) + sizeof(double));
+  if (feat_bytes > pool_cap_bytes() || list_bytes > pool_cap_bytes())
+    return fail(h, O3DS_ERR_CAPACITY, "compute_fpfh: feature buffer exceeds the pool cap (O3DS_POOL_CAP_MB)");
+  double* out = nullptr;
+  HIP_TRY(dev_alloc(h, (void**)&out, std::max<size_t>(feat_bytes, 8)));
+  c.fpfh = out;
+  if (n == 0) {
+    c.has_fpfh = true;
+    return O3DS_OK;
+  }
+  // the cloud's own index with a cell of about the radius: the neighbourhood is then the 3x3x3 block (an index with a much smaller
+  // or larger cell is rebuilt; one built here is marked as a by-product, so a registration against the cloud picks its own)
+  if (!c.has_index || c.grid.cell < 0.5 * radius || c.grid.cell > 2.0 * radius) {
+    int rc = build_index(h, c, radius);
+    if (rc) return rc;
+    c.index_byproduct = true;
+  }
+  const int K = std::max(1, (int)std::ceil(radius / c.grid.cell));
+  int *nb_idx = nullptr, *nb_cnt = nullptr;
+  double *nb_d2 = nullptr, *spfh = nullptr;
+  TMP_ALLOC(nb_idx, n * (size_t)max_nn * sizeof(int));
+  TMP_ALLOC(nb_d2, n * (size_t)max_nn * sizeof(double));
+  TMP_ALLOC(nb_cnt, n * sizeof(int));
+  TMP_ALLOC(spfh, feat_bytes);
+  const int ni = (int)n, nblk = (ni + 63) / 64;
+  fpfh_neighbours_kernel<P4><<<std::min(ni, 65536), 64, 0, h->stream>>>(c.grid, (const P4*)c.spts, (const P4*)c.pts, ni, radius * radius,
+                                                                          max_nn, K, nb_idx, nb_d2, nb_cnt);
+  spfh_kernel<P4><<<nblk, 64, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, ni, nb_idx, nb_cnt, max_nn, spfh);
+  fpfh_kernel<<<nblk, 64, 0, h->stream>>>(spfh, ni, nb_idx, nb_d2, nb_cnt, max_nn, out);
+  HIP_TRY(hipGetLastError());
+  c.has_fpfh = true;
+  c.fpfh_n = n;
+  return O3DS_OK;
+}
+
+bool fpfh_valid(const CloudRec& c) { return c.has_fpfh && c.fpfh_n == c.n && !c.pm; }
+
+// RegistrationRANSACBasedOnFeatureMatching's correspondences: (i, argmin_j) for every source point; with the mutual filter the pairs
+// whose reverse match is i, unless there are fewer than 3 ransac_n of them (then the one-way set, fell_back = 1)
+int feature_corr(o3ds_handle h, const CloudRec& s, const CloudRec& t, int mutual, int ransac_n, std::vector<uint32_t>& pairs, int* fell_back) {
+  pairs.clear();
+  *fell_back = 0;
+  const int ns = (int)s.fpfh_n, nt = (int)t.fpfh_n;
+  if (ns == 0 || nt == 0) return O3DS_OK;
+  int *d_ij = nullptr, *d_ji = nullptr;
+  TMP_ALLOC(d_ij, sizeof(int) * (size_t)ns);
+  TMP_ALLOC(d_ji, sizeof(int) * (size_t)nt);
+  feature_nn_kernel<<<(ns + kFnnBlock - 1) / kFnnBlock, kFnnBlock, 0, h->stream>>>(s.fpfh, ns, t.fpfh, nt, d_ij);
+  if (mutual) feature_nn_kernel<<<(nt + kFnnBlock - 1) / kFnnBlock, kFnnBlock, 0, h->stream>>>(t.fpfh, nt, s.fpfh, ns, d_ji);
+  HIP_TRY(hipGetLastError());
+  std::vector<int> ij((size_t)ns), ji(mutual ? (size_t)nt : 0);
+  int rc = d2h_copy(h, ij.data(), d_ij, sizeof(int) * (size_t)ns);
+  if (rc) return rc;
+  if (mutual) {
+    rc = d2h_copy(h, ji.data(), d_ji, sizeof(int) * (size_t)nt);
+    if (rc) return rc;
+    for (int i = 0; i < ns; ++i) {
+      const int j = ij[(size_t)i];
+      if (j >= 0 && j < nt && ji[(size_t)j] == i) pairs.push_back((uint32_t)i), pairs.push_back((uint32_t)j);
+    }
+    if (pairs.size() / 2 >= (size_t)(3 * std::max(ransac_n, 0))) return O3DS_OK;
+    *fell_back = 1;
+    pairs.clear();
+  }
+  for (int i = 0; i < ns; ++i) pairs.push_back((uint32_t)i), pairs.push_back((uint32_t)ij[(size_t)i]);
+  return O3DS_OK;
+}
+
+int ransac_batch_max() {  // hypotheses per batch at most (O3DS_RANSAC_BATCH fixes the batch size: the determinism A/B)
+  static const int fixed = ab_getenv("O3DS_RANSAC_BATCH") ? std::max(1, atoi(ab_getenv("O3DS_RANSAC_BATCH"))) : 0;
+  return fixed;
+}
+
+template <typename P4>
+int ransac_t(o3ds_handle h, CloudRec& s, CloudRec& t, const o3ds_ransac_params* p, uint64_t seed, const std::vector<uint32_t>& pairs,
+             o3ds_ransac_result* out, o3ds_ransac_trace* trace, size_t trace_cap) {
+  const int n = p->ransac_n;
+  const double r = p->max_correspondence_distance;
+  const uint64_t m = pairs.size() / 2;
+  const double conf = std::min(1.0, std::max(0.0, p->confidence));
+  const long long max_iter = p->max_iteration;
+  if (max_iter <= 0 || s.n == 0) return O3DS_OK;
+  uint32_t* d_corr = nullptr;
+  TMP_ALLOC(d_corr, pairs.size() * sizeof(uint32_t));
+  int rc = h2d_copy(h, d_corr, pairs.data(), pairs.size() * sizeof(uint32_t));
+  if (rc) return rc;
+  if (!t.has_index || t.grid.cell < 0.5 * r || t.grid.cell > 2.0 * r) {
+    rc = build_index(h, t, r);
+    if (rc) return rc;
+    t.index_byproduct = true;
+  }
+  const int K = std::max(1, (int)std::ceil(r / t.grid.cell));
+  const int fixed = ransac_batch_max();
+  const int bmax = fixed ? fixed : 65536;
+  int batch = fixed ? fixed : 1024;  // small first batches: a good hypothesis early cuts the search short
+  double *d_T = nullptr, *d_val = nullptr;
+  int *d_checks = nullptr, *d_list = nullptr, *d_count = nullptr;
+  uint32_t* d_samples = nullptr;
+  TMP_ALLOC(d_T, (size_t)bmax * 16 * sizeof(double));
+  TMP_ALLOC(d_val, (size_t)bmax * 3 * sizeof(double));
+  TMP_ALLOC(d_checks, (size_t)bmax * sizeof(int));
+  TMP_ALLOC(d_list, (size_t)bmax * sizeof(int));
+  TMP_ALLOC(d_count, sizeof(int));
+  if (trace && trace_cap) TMP_ALLOC(d_samples, (size_t)bmax * kRansacMaxN * sizeof(uint32_t));
+  long long est_k = max_iter, t0 = 0, best_t = -1, validations = 0;
+  long long best_pairs = 0;
+  double best_rmse = 0.0, best_T[16];
+  std::vector<double> val;
+  std::vector<int> checks;
+  std::vector<uint32_t> samples;
+  std::vector<double> Ts;
+  while (t0 < est_k) {
+    const int cnt = (int)std::min<long long>(batch, est_k - t0);
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int), h->stream));
+    RansacArgs a{};
+    a.corr = d_corr;
+    a.m = m;
+    a.seed = seed;
+    a.n = n;
+    a.t0 = t0;
+    a.count = cnt;
+    a.edge = p->edge_length;
+    a.dist = p->distance;
+    a.T = d_T;
+    a.checks = d_checks;
+    a.samples = d_samples;
+    a.list = d_list;
+    a.list_count = d_count;
+    ransac_hypothesis_kernel<P4><<<(cnt + 255) / 256, 256, 0, h->stream>>>((const P4*)s.pts, (const P4*)t.pts, a);
+    ransac_validate_kernel<P4><<<std::min(cnt, 2048), kValBlock, 0, h->stream>>>((const P4*)s.pts, (int)s.n, t.grid, (const P4*)t.spts,
+                                                                                  r * r, K, d_T, d_list, d_count, d_val);
+    HIP_TRY(hipGetLastError());
+    int nl = 0;
+    rc = read_back(h, {{&nl, d_count, sizeof(int)}});
+    if (rc) return rc;
+    if (nl < 0 || nl > cnt) return fail(h, O3DS_ERR_HIP, "ransac: validation list count out of range");
+    val.resize((size_t)nl * 3);
+    if (nl) {
+      rc = d2h_copy(h, val.data(), d_val, (size_t)nl * 3 * sizeof(double));
+      if (rc) return rc;
+    }
+    if (trace && (size_t)t0 < trace_cap) {
+      const size_t tn = std::min<size_t>((size_t)cnt, trace_cap - (size_t)t0);
+      checks.resize(tn);
+      samples.resize(tn * kRansacMaxN);
+      Ts.resize(tn * 16);
+      rc = d2h_copy(h, checks.data(), d_checks, tn * sizeof(int));
+      if (!rc) rc = d2h_copy(h, samples.data(), d_samples, tn * kRansacMaxN * sizeof(uint32_t));
+      if (!rc) rc = d2h_copy(h, Ts.data(), d_T, tn * 16 * sizeof(double));
+      if (rc) return rc;
+      for (size_t k = 0; k < tn; ++k) {
+        o3ds_ransac_trace& e = trace[(size_t)t0 + k];
+        for (int j = 0; j < kRansacMaxN; ++j) e.sample[j] = j < n ? samples[k * kRansacMaxN + j] : 0u;
+        e.checks = checks[k];
+        e.pairs = -1;
+        e.error_sum = 0.0;
+        memcpy(e.transformation, &Ts[k * 16], sizeof(e.transformation));
+      }
+      for (int k = 0; k < nl; ++k) {
+        const size_t slot = (size_t)val[3 * (size_t)k];
+        if (slot < tn) {
+          trace[(size_t)t0 + slot].pairs = (int32_t)val[3 * (size_t)k + 1];
+          trace[(size_t)t0 + slot].error_sum = val[3 * (size_t)k + 2];
+        }
+      }
+    }
+    // fold the batch's validated hypotheses in index order (the serial stopping rule)
+    std::vector<std::pair<long long, int>> order((size_t)nl);
+    for (int k = 0; k < nl; ++k) order[(size_t)k] = {(long long)val[3 * (size_t)k], k};
+    std::sort(order.begin(), order.end());
+    long long improved_slot = -1;
+    for (const auto& o : order) {
+      const long long tt = t0 + o.first;
+      if (tt >= est_k) break;
+      ++validations;
+      const long long pr = (long long)val[3 * (size_t)o.second + 1];
+      const double err = val[3 * (size_t)o.second + 2];
+      const double rmse = pr > 0 ? std::sqrt(err / (double)pr) : 0.0;
+      if (pr > best_pairs || (pr == best_pairs && rmse < best_rmse)) {  // [O3D] RegistrationResult::IsBetterRANSACThan
+        best_pairs = pr;
+        best_rmse = rmse;
+        best_t = tt;
+        improved_slot = o.first;
+        const double fitness = (double)pr / (double)s.n;
+        const double est = std::log(1.0 - conf) / std::log(1.0 - std::pow(fitness, n));
+        if (est < (double)est_k) est_k = (long long)std::ceil(est);
+      }
+    }
+    if (improved_slot >= 0) {
+      rc = read_back(h, {{best_T, d_T + (size_t)improved_slot * 16, sizeof(best_T)}});
+      if (rc) return rc;
+    }
+    t0 += cnt;
+    if (!fixed) batch = std::min(bmax, batch * 2);
+  }
+  const long long run = std::max(std::min(est_k, max_iter), best_t + 1);
+  out->iterations_run = run;
+  out->validations = validations;
+  out->best_t = best_t;
+  if (best_t >= 0) {
+    memcpy(out->transformation, best_T, sizeof(best_T));
+    out->fitness = (double)best_pairs / (double)s.n;
+    out->inlier_rmse = best_rmse;
+    out->n_corr = (uint64_t)best_pairs;
+  }
+  if (trace)
+    for (size_t k = (size_t)std::max<long long>(run, 0); k < trace_cap; ++k) {
+      trace[k].checks = -1;
+      trace[k].pairs = -1;
+      trace[k].error_sum = 0.0;
+    }
+  return O3DS_OK;
+}
+
+void empty_ransac_result(o3ds_ransac_result* out) {
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 16; ++k) out->transformation[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  out->best_t = -1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int o3ds_compute_fpfh(o3ds_handle h, o3ds_cloud cloud, double radius, int max_nn) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  CloudRec* c = find_cloud(h, cloud);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "compute_fpfh: unknown cloud id");
+  if (!c->nrm) return fail(h, O3DS_ERR_INVALID_ARG, "compute_fpfh: the cloud has no normals ([O3D] ComputeFPFHFeature needs them)");
+  if (!(radius > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "compute_fpfh: radius must be > 0");
+  if (max_nn < 1 || max_nn > kFpfhMaxNN) return fail(h, O3DS_ERR_INVALID_ARG, "compute_fpfh: max_nn outside 1..128");
+  return DISPATCH(c->precision, fpfh_t, h, *c, radius, max_nn);
+}
+
+int o3ds_cloud_has_fpfh(o3ds_handle h, o3ds_cloud cloud, int* has_fpfh) {
+  CHECK_HANDLE(h);
+  if (!has_fpfh) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_has_fpfh: null argument");
+  CloudRec* c = find_cloud(h, cloud);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_has_fpfh: unknown cloud id");
+  *has_fpfh = fpfh_valid(*c) ? 1 : 0;
+  return O3DS_OK;
+}
+
+int o3ds_cloud_download_fpfh(o3ds_handle h, o3ds_cloud cloud, double* out, size_t capacity) {
+  CHECK_HANDLE(h);
+  CloudRec* c = find_cloud(h, cloud);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_fpfh: unknown cloud id");
+  if (!fpfh_valid(*c)) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_fpfh: the cloud has no features");
+  if (capacity < c->n) return fail(h, O3DS_ERR_CAPACITY, "cloud_download_fpfh: buffer too small");
+  if (c->n == 0) return O3DS_OK;
+  if (!out) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_fpfh: null buffer");
+  return d2h_copy(h, out, c->fpfh, c->n * kFeatDim * sizeof(double));
+}
+
+int o3ds_feature_correspondences(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, int mutual_filter, int ransac_n, uint32_t* pairs,
+                                 size_t capacity, size_t* n_pairs, int* fell_back) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!n_pairs) return fail(h, O3DS_ERR_INVALID_ARG, "feature_correspondences: null argument");
+  CloudRec* s = find_cloud(h, source);
+  CloudRec* t = find_cloud(h, target);
+  if (!s || !t) return fail(h, O3DS_ERR_INVALID_ARG, "feature_correspondences: unknown cloud id");
+  if (!fpfh_valid(*s) || !fpfh_valid(*t)) return fail(h, O3DS_ERR_INVALID_ARG, "feature_correspondences: a cloud has no features");
+  std::vector<uint32_t> v;
+  int fb = 0;
+  int rc = feature_corr(h, *s, *t, mutual_filter, ransac_n, v, &fb);
+  if (rc) return rc;
+  *n_pairs = v.size() / 2;
+  if (fell_back) *fell_back = fb;
+  if (capacity < v.size() / 2) return fail(h, O3DS_ERR_CAPACITY, "feature_correspondences: buffer too small");
+  if (!v.empty()) {
+    if (!pairs) return fail(h, O3DS_ERR_INVALID_ARG, "feature_correspondences: null buffer");
+    memcpy(pairs, v.data(), v.size() * sizeof(uint32_t));
+  }
+  return O3DS_OK;
+}
+
+int o3ds_ransac_feature_matching(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_ransac_params* params, uint64_t seed,
+                                 o3ds_ransac_result* out, o3ds_ransac_trace* trace, size_t trace_cap) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!params || !out || (trace_cap && !trace)) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_feature_matching: null argument");
+  empty_ransac_result(out);
+  for (size_t k = 0; k < trace_cap; ++k) {
+    memset(&trace[k], 0, sizeof(trace[k]));
+    trace[k].checks = -1;
+    trace[k].pairs = -1;
+  }
+  CloudRec* s = find_cloud(h, source);
+  CloudRec* t = find_cloud(h, target);
+  if (!s || !t) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_feature_matching: unknown cloud id");
+  if (!fpfh_valid(*s) || !fpfh_valid(*t)) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_feature_matching: a cloud has no features");
+  if (params->ransac_n > kRansacMaxN) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_feature_matching: ransac_n > 8 unsupported");
+  if (s->precision != t->precision) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_feature_matching: clouds of different storage precision");
+  std::vector<uint32_t> pairs;
+  int fb = 0;
+  int rc = feature_corr(h, *s, *t, params->mutual_filter, params->ransac_n, pairs, &fb);
+  if (rc) return rc;
+  out->n_feature_corr = pairs.size() / 2;
+  out->fell_back = fb;
+  // [O3D] RegistrationRANSACBasedOnCorrespondence: the empty RegistrationResult
+  if (params->ransac_n < 3 || pairs.size() / 2 < (size_t)params->ransac_n || !(params->max_correspondence_distance > 0.0)) return O3DS_OK;
+  return DISPATCH(s->precision, ransac_t, h, *s, *t, params, seed, pairs, out, trace, trace_cap);
+}
+
+}  // extern "C"
+
 
 #include "sharded.hpp"

@@ -1,6 +1,7 @@
 """Mapper::addRangeMeasurement (include/open3d_slam/Mapper.hpp:47, src/Mapper.cpp:101-181) for ONE active submap:
 the caller of the scan-to-map hot path, kept as a thin host harness with the reference's names.  Submap switching,
-loop closure and the dense map are out of scope."""
+loop-closure candidate selection and the dense map are out of scope here; place recognition
+between submaps is place_recognition.py."""
 from __future__ import annotations
 
 import numpy as np

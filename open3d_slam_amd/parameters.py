@@ -89,6 +89,52 @@ class ScanToMapRegistrationParameters:  # Parameters.hpp:145-149
     icp_: IcpParameters = dataclasses.field(default_factory=IcpParameters)
 
 
+_DEG = np.pi / 180.0
+
+
+@dataclasses.dataclass
+class PlaceRecognitionConsistencyCheckParameters:  # Parameters.hpp:108-115 (radians)
+    maxDriftRoll_: float = 90.0 * _DEG
+    maxDriftPitch_: float = 90.0 * _DEG
+    maxDriftYaw_: float = 90.0 * _DEG
+    maxDriftZ_: float = 15.0
+    maxDriftY_: float = 10.0
+    maxDriftX_: float = 10.0
+
+
+@dataclasses.dataclass
+class PlaceRecognitionParameters:  # Parameters.hpp:117-136
+    normalEstimationRadius_: float = 1.0
+    featureVoxelSize_: float = 0.5
+    featureRadius_: float = 2.5
+    featureKnn_: int = 100
+    normalKnn_: int = 10
+    ransacNumIter_: int = 1000000
+    ransacProbability_: float = 0.99
+    ransacModelSize_: int = 3
+    ransacMaxCorrespondenceDistance_: float = 0.75
+    correspondenceCheckerDistance_: float = 0.75
+    correspondenceCheckerEdgeLength_: float = 0.5
+    ransacMinCorrespondenceSetSize_: int = 25
+    maxIcpCorrespondenceDistance_: float = 0.3
+    minRefinementFitness_: float = 0.7
+    isDumpPlaceRecognitionAlignmentsToFile_: bool = False
+    consistencyCheck_: PlaceRecognitionConsistencyCheckParameters = dataclasses.field(default_factory=PlaceRecognitionConsistencyCheckParameters)
+    minSubmapsBetweenLoopClosures_: int = 2
+    loopClosureSearchRadius_: float = 20.0
+
+
+def lua_place_recognition_parameters() -> PlaceRecognitionParameters:
+    """PLACE_RECOGNITION_PARAMETERS and LOOP_CLOSURE_CONSISTENCY_CHECK_PARAMETERS of the shipped Lua
+    (ros/open3d_slam_ros/param/default/parameter_structure_definitions.lua:145-173), angles in radians."""
+    return PlaceRecognitionParameters(
+        normalEstimationRadius_=2.0, featureVoxelSize_=0.5, featureRadius_=2.5, featureKnn_=100, normalKnn_=20, ransacNumIter_=10000000,
+        ransacProbability_=0.999, ransacModelSize_=3, ransacMaxCorrespondenceDistance_=0.75, correspondenceCheckerDistance_=0.8,
+        correspondenceCheckerEdgeLength_=0.6, ransacMinCorrespondenceSetSize_=25, maxIcpCorrespondenceDistance_=0.3, minRefinementFitness_=0.7,
+        consistencyCheck_=PlaceRecognitionConsistencyCheckParameters(30.0 * _DEG, 30.0 * _DEG, 30.0 * _DEG, 40.0, 80.0, 80.0),
+        minSubmapsBetweenLoopClosures_=2, loopClosureSearchRadius_=20.0)
+
+
 @dataclasses.dataclass
 class MapperParameters:  # Parameters.hpp:158-178 (hot-path subset)
     scanMatcher_: ScanToMapRegistrationParameters = dataclasses.field(default_factory=ScanToMapRegistrationParameters)
@@ -100,6 +146,7 @@ class MapperParameters:  # Parameters.hpp:158-178 (hot-path subset)
     isBuildDenseMap_: bool = True
     isUseInitialMap_: bool = False
     isMergeScansIntoMap_: bool = True
+    placeRecognition_: PlaceRecognitionParameters = dataclasses.field(default_factory=PlaceRecognitionParameters)
 
 
 def lua_default_mapper_parameters() -> MapperParameters:

@@ -19,6 +19,7 @@ class Submap:
         self.mapToRangeSensor_ = np.eye(4)
         self.nScansInsertedMap_ = 0
         self.nScansInsertedDenseMap_ = 0
+        self.sparseMapCloud_ = None  # computeFeatures: the voxelised map with normals and FPFH features (Submap.cpp:237-242)
         self._denseMap = None  # o3ds_dense_map id, made on first use (Submap::update move-assigns a fresh VoxelizedPointCloud, Submap.cpp:211)
         self.update(self.params_)
 
@@ -124,3 +125,24 @@ class Submap:
         return self.be.map_carve(self.mapCloud_.id, rawScan.id, mapToRangeSensor, self.mapBuilderCropper_.to_abi(), voxel=c.voxelSize_,
                                  max_length=c.maxRaytracingLength_, truncation=c.truncationDistance_, min_dot=c.minDotProductWithNormal_,
                                  want_count=want_count)
+
+    def computeFeatures(self):
+        """Submap::computeFeatures (Submap.cpp:228-248): VoxelDownSample(featureVoxelSize_), EstimateNormals(Hybrid(normalEstimationRadius_,
+        normalKnn_)) + NormalizeNormals + OrientNormalsTowardsCameraLocation(0), ComputeFPFHFeature(Hybrid(featureRadius_, featureKnn_)),
+        all on the device; the features stay on the sparse cloud.  (The minimum-seconds throttle and the voxel-map thread are left out.)"""
+        p = self.params_.placeRecognition_
+        sparse = PointCloud(self.be, self.be.voxel_down_sample(self.mapCloud_.id, p.featureVoxelSize_))
+        self.be.estimate_normals(sparse.id, p.normalEstimationRadius_, p.normalKnn_)
+        self.be.compute_fpfh(sparse.id, p.featureRadius_, p.featureKnn_)
+        if self.sparseMapCloud_ is not None:
+            self.sparseMapCloud_.release()
+        self.sparseMapCloud_ = sparse
+
+    def getSparseMapPointCloud(self) -> PointCloud:
+        if self.sparseMapCloud_ is None:
+            raise RuntimeError("Submap::getSparseMapPointCloud: computeFeatures has not run")
+        return self.sparseMapCloud_
+
+    def getFeatures(self) -> np.ndarray:
+        """The (n, 33) FPFH features of the sparse map (Open3D's Feature holds them as 33 x n)."""
+        return self.be.fpfh(self.getSparseMapPointCloud().id)
