@@ -42,11 +42,14 @@ def neighbours(P, radius, max_nn, tree=None):
     return out
 
 
-def pair_feature(p1, n1, p2, n2):
-    """ComputePairFeatures -> (f0, f1, f2) (Python floats, one rounding per operation)"""
+def pair_feature(p1, n1, p2, n2, tags=None):
+    """ComputePairFeatures -> (f0, f1, f2) (Python floats, one rounding per operation).  tags: a set that collects the branches taken
+    ("zero_d", "zero_cross", "swap", "equal_no_swap", "atan2_+pi", "atan2_-pi", "f1_+1", "f1_-1")."""
     dx, dy, dz = p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]
     dn = math.sqrt(dx * dx + dy * dy + dz * dz)
     if dn == 0.0:
+        if tags is not None:
+            tags.add("zero_d")
         return 0.0, 0.0, 0.0
     a1 = (n1[0] * dx + n1[1] * dy + n1[2] * dz) / dn
     a2 = (n2[0] * dx + n2[1] * dy + n2[2] * dz) / dn
@@ -55,16 +58,27 @@ def pair_feature(p1, n1, p2, n2):
         a, b = n2, n1
         dx, dy, dz = -dx, -dy, -dz
         f2 = -a2
+        if tags is not None:
+            tags.add("swap")
     else:
         f2 = a1
+        if tags is not None and abs(a1) == abs(a2):
+            tags.add("equal_no_swap")
     vx, vy, vz = dy * a[2] - dz * a[1], dz * a[0] - dx * a[2], dx * a[1] - dy * a[0]
     vn = math.sqrt(vx * vx + vy * vy + vz * vz)
     if vn == 0.0:
+        if tags is not None:
+            tags.add("zero_cross")
         return 0.0, 0.0, 0.0
     vx, vy, vz = vx / vn, vy / vn, vz / vn
     wx, wy, wz = a[1] * vz - a[2] * vy, a[2] * vx - a[0] * vz, a[0] * vy - a[1] * vx
     f1 = vx * b[0] + vy * b[1] + vz * b[2]
     f0 = math.atan2(wx * b[0] + wy * b[1] + wz * b[2], a[0] * b[0] + a[1] * b[1] + a[2] * b[2])
+    if tags is not None:
+        if abs(f0) == math.pi:
+            tags.add("atan2_+pi" if f0 > 0 else "atan2_-pi")
+        if abs(f1) == 1.0:
+            tags.add("f1_+1" if f1 > 0 else "f1_-1")
     return f0, f1, f2
 
 
@@ -163,3 +177,90 @@ def stopping_rule(max_iteration, confidence, ransac_n, n_src, validated):
             if est < est_k:
                 est_k = int(math.ceil(est))
     return max(min(est_k, max_iteration), t_last + 1), best_t, vals
+
+
+def pair_feature_tags(P, N, nbrs):
+    """the branches of pair_feature that the SPFH of (P, N, nbrs) takes (a set of tags)"""
+    tags = set()
+    for i, (idx, _) in enumerate(nbrs):
+        p, n = P[i].tolist(), N[i].tolist()
+        for k in idx[1:]:
+            pair_feature(p, n, P[k].tolist(), N[k].tolist(), tags)
+    return tags
+
+
+# ---- feature nearest neighbour, exactly as feature_nn_kernel ---------------------------------------------------------------------
+def feature_nn(A, B, chunk=256):
+    """out[i] = argmin_j d(A[i], B[j]) with d = 0; d = d + (a_b - b_b)^2 for b = 0..32 in order (f64, one rounding per operation), ties
+    to the lower j; -1 when B is empty"""
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    out = np.full(len(A), -1, np.int64)
+    if len(B) == 0:
+        return out
+    Bt = np.ascontiguousarray(B.T)
+    for i0 in range(0, len(A), chunk):
+        a = A[i0:i0 + chunk]
+        d = np.zeros((len(a), len(B)))
+        t = np.empty_like(d)
+        for b in range(A.shape[1]):
+            np.subtract(a[:, b:b + 1], Bt[b][None, :], out=t)
+            np.multiply(t, t, out=t)
+            d += t
+        out[i0:i0 + chunk] = np.argmin(d, axis=1)  # (the first minimum: the lower index)
+    return out
+
+
+def feature_correspondences(A, B, mutual, ransac_n, ab=None, ba=None):
+    """RegistrationRANSACBasedOnFeatureMatching's pairs as o3ds_feature_correspondences states them: ((k, 2) int64, fell_back).
+    ab / ba: feature_nn(A, B) / feature_nn(B, A) when already known."""
+    ab = feature_nn(A, B) if ab is None else ab
+    one = np.column_stack([np.arange(len(A)), ab]).astype(np.int64)
+    if len(A) == 0 or len(B) == 0:
+        return np.zeros((0, 2), np.int64), False
+    if not mutual:
+        return one, False
+    ba = feature_nn(B, A) if ba is None else ba
+    keep = ba[ab] == np.arange(len(A))
+    if keep.sum() >= 3 * max(ransac_n, 0):
+        return one[keep], False
+    return one, True
+
+
+def ls_cost(T, p, q):
+    """sum_k |q_k - T p_k|^2 (the least-squares cost Umeyama minimises over rigid T)"""
+    r = q - (p @ T[:3, :3].T + T[:3, 3])
+    return float(np.sum(r * r))
+
+
+# ---- structured clouds (every coordinate and normal exact in f32) ---------------------------------------------------------------
+AXES = np.array([[1.0, 0, 0], [-1.0, 0, 0], [0, 1.0, 0], [0, -1.0, 0], [0, 0, 1.0], [0, 0, -1.0]])
+
+
+def lattice(side, spacing=0.125, seed=0, dups=()):
+    """a side^3 cubic lattice (index order x fastest) with normals drawn from {+-x, +-y, +-z}; dups: indices of points appended a
+    second time (same position, another axis normal), for |d| = 0 pairs"""
+    g = np.arange(side) * spacing
+    z, y, x = np.meshgrid(g, g, g, indexing="ij")
+    P = np.column_stack([x.ravel(), y.ravel(), z.ravel()])
+    rng = np.random.default_rng(seed)
+    N = AXES[rng.integers(0, 6, len(P))]
+    if len(dups):
+        P = np.vstack([P, P[list(dups)]])
+        N = np.vstack([N, AXES[rng.integers(0, 6, len(dups))]])
+    return P, N
+
+
+def dyadic_cloud(n, seed, half=(7.0, 7.0, 7.0), q=2.0 ** -10):
+    """n points with coordinates on the 2^-10 grid, |x_a| < half_a < 8, and unit normals rounded to f32 (so f32 storage holds both
+    exactly)"""
+    rng = np.random.default_rng(seed)
+    P = np.round(rng.uniform(-1.0, 1.0, (n, 3)) * np.asarray(half) / q) * q
+    N = rng.normal(size=(n, 3))
+    N = (N / np.linalg.norm(N, axis=1, keepdims=True)).astype(np.float32).astype(np.float64)
+    return P, N
+
+
+def tile(P, N, offsets):
+    """copies of (P, N) at the given offsets, copy-major (copy c holds points c * len(P) ...)"""
+    offsets = np.asarray(offsets, np.float64)
+    return (np.vstack([P + o for o in offsets]), np.tile(N, (len(offsets), 1)))

@@ -191,6 +191,78 @@ def test_mutual_fallback(be64):
 
 
 # ---- 3. RANSAC replay -----------------------------------------------------------------------------------------------------------
+def _place(T, P):
+    """T p for every row of P, in the validate kernel's order of operations (one rounding each, no FMA)"""
+    R, t = T[:3, :3], T[:3, 3]
+    x, y, z = P[:, 0], P[:, 1], P[:, 2]
+    return np.column_stack([((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0], ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1],
+                            ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]])
+
+
+def replay_ransac(r, S, Tg, corr, seed, ransac_n, max_corr, edge, dist, n_iter, confidence, invariants=True):
+    """Replays the trace of an o3ds_ransac_feature_matching call with trace=n_iter (r) on the host: the draws, the Umeyama fit, the two
+    checkers, a cKDTree recount of every validated hypothesis and the serial stopping rule.  S, Tg: the stored source and target points;
+    corr: the pairs feature_correspondences returned.  invariants: also assert, for every hypothesis run (degenerate samples included),
+    a finite proper rotation that maps the sample's source centroid onto its target centroid and the least-squares cost of the
+    restatement's Umeyama.  Returns {t: (pairs, rmse)} of the validated hypotheses."""
+    tr = r["trace"]
+    m = len(corr)
+    run = r["iterations_run"]
+    assert 0 < run <= n_iter
+    tree = cKDTree(Tg)
+    validated = {}
+    recount = []
+    for t in range(run):
+        smp = rs.draw(seed, ransac_n, t, m)
+        assert list(tr["sample"][t]) == smp
+        ps, qs = S[corr[smp, 0]], Tg[corr[smp, 1]]
+        T = tr["transformation"][t]
+        sv = np.linalg.svd((qs - qs.mean(0)).T @ (ps - ps.mean(0)), compute_uv=False)
+        U = rs.umeyama(ps, qs)
+        if sv[1] > 1e-6 * sv[0]:  # a unique rotation (not a repeated draw or a collinear sample)
+            assert np.allclose(T, U, atol=1e-9), t
+        if invariants:
+            R = T[:3, :3]
+            assert np.all(np.isfinite(T)) and np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]), t
+            assert np.max(np.abs(R.T @ R - np.eye(3))) <= 1e-12, t
+            assert abs(np.linalg.det(R) - 1.0) <= 1e-12, t  # a rotation, never a reflection
+            assert np.max(np.abs(R @ ps.mean(0) + T[:3, 3] - qs.mean(0))) <= 1e-12, t
+            assert abs(rs.ls_cost(T, ps, qs) - rs.ls_cost(U, ps, qs)) <= 1e-9, t
+        e_ok, e_m = rs.edge_check(ps, qs, edge) if edge > 0 else (True, np.inf)
+        d_ok, d_m = rs.distance_check(ps, qs, T, dist) if dist > 0 else (True, np.inf)
+        if e_m > 1e-12 and d_m > 1e-12:
+            assert tr["checks"][t] == (int(e_ok) | (int(d_ok) << 1)), t
+        if tr["checks"][t] == 3:
+            recount.append(t)
+        else:
+            assert tr["pairs"][t] == -1
+    for k0 in range(0, len(recount), 64):  # the recount, 64 hypotheses per cKDTree call
+        ts = recount[k0:k0 + 64]
+        X = np.vstack([_place(tr["transformation"][t], S) for t in ts])
+        _, j = tree.query(X, k=1, distance_upper_bound=max_corr * (1 + 1e-9))
+        ok = j < len(Tg)
+        d2 = np.full(len(X), np.inf)
+        dd = Tg[j[ok]] - X[ok]
+        d2[ok] = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
+        d2 = np.where(d2 < max_corr * max_corr, d2, np.nan).reshape(len(ts), len(S))
+        for t, row in zip(ts, d2):
+            inl = ~np.isnan(row)
+            assert tr["pairs"][t] == int(inl.sum()), t
+            if inl.any():
+                assert tr["error_sum"][t] == pytest.approx(float(row[inl].sum()), rel=1e-12)
+            pairs = int(tr["pairs"][t])
+            validated[t] = (pairs, math.sqrt(tr["error_sum"][t] / pairs) if pairs else 0.0)
+    assert np.all(tr["checks"][run:] == -1)
+    exp_run, exp_best, exp_vals = rs.stopping_rule(n_iter, confidence, ransac_n, len(S), validated)
+    assert (r["iterations_run"], r["best_t"], r["validations"]) == (exp_run, exp_best, exp_vals)
+    assert len(validated) == r["validations"]
+    bt = r["best_t"]
+    if bt >= 0:
+        assert np.array_equal(r["transformation"], tr["transformation"][bt])
+        assert r["n_corr"] == tr["pairs"][bt] and r["fitness"] == tr["pairs"][bt] / len(S)
+    return validated
+
+
 def test_ransac_replay(be64, pair):
     a, b, _, p = pair
     cfg = p.placeRecognition_
@@ -201,50 +273,11 @@ def test_ransac_replay(be64, pair):
     n_iter, seed = 4096, 12345
     r = be64.ransac_feature_matching(sa.id, sb.id, cfg.ransacMaxCorrespondenceDistance_, 3, True, cfg.correspondenceCheckerEdgeLength_,
                                      cfg.correspondenceCheckerDistance_, n_iter, cfg.ransacProbability_, seed, trace=n_iter)
-    tr = r["trace"]
-    m = len(corr)
-    assert r["n_feature_corr"] == m and r["fell_back"] == fb
-    run = r["iterations_run"]
-    assert 0 < run <= n_iter
-    tree = cKDTree(Tg)
-    r_max = cfg.ransacMaxCorrespondenceDistance_
-    validated = {}
-    n_checked = 0
-    for t in range(run):
-        smp = rs.draw(seed, 3, t, m)
-        assert list(tr["sample"][t]) == smp
-        ps, qs = S[corr[smp, 0]], Tg[corr[smp, 1]]
-        T = tr["transformation"][t]
-        sv = np.linalg.svd((qs - qs.mean(0)).T @ (ps - ps.mean(0)), compute_uv=False)
-        if sv[1] > 1e-6 * sv[0]:  # a unique rotation (not a repeated draw or a collinear sample)
-            assert np.allclose(T, rs.umeyama(ps, qs), atol=1e-9), t
-        e_ok, e_m = rs.edge_check(ps, qs, cfg.correspondenceCheckerEdgeLength_)
-        d_ok, d_m = rs.distance_check(ps, qs, T, cfg.correspondenceCheckerDistance_)
-        if e_m > 1e-12 and d_m > 1e-12:
-            assert tr["checks"][t] == (int(e_ok) | (int(d_ok) << 1)), t
-        if tr["checks"][t] == 3:
-            X = S @ T[:3, :3].T + T[:3, 3]
-            _, j = tree.query(X, k=1, distance_upper_bound=r_max * (1 + 1e-9))
-            ok = j < len(Tg)
-            d2 = np.full(len(X), np.inf)
-            dd = Tg[j[ok]] - X[ok]
-            d2[ok] = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
-            inl = d2 < r_max * r_max
-            assert tr["pairs"][t] == int(inl.sum()), t
-            if inl.any():
-                assert tr["error_sum"][t] == pytest.approx(float(d2[inl].sum()), rel=1e-12)
-            pairs = int(tr["pairs"][t])
-            validated[t] = (pairs, math.sqrt(tr["error_sum"][t] / pairs) if pairs else 0.0)
-            n_checked += 1
-        else:
-            assert tr["pairs"][t] == -1
-    assert np.all(tr["checks"][run:] == -1)
-    exp_run, exp_best, exp_vals = rs.stopping_rule(n_iter, cfg.ransacProbability_, 3, len(S), validated)
-    assert (r["iterations_run"], r["best_t"], r["validations"]) == (exp_run, exp_best, exp_vals)
-    assert n_checked == r["validations"] and r["validations"] > 0
-    bt = r["best_t"]
-    assert np.array_equal(r["transformation"], tr["transformation"][bt])
-    assert r["n_corr"] == tr["pairs"][bt] and r["fitness"] == tr["pairs"][bt] / len(S)
+    assert r["n_feature_corr"] == len(corr) and r["fell_back"] == fb
+    validated = replay_ransac(r, S, Tg, corr, seed, 3, cfg.ransacMaxCorrespondenceDistance_, cfg.correspondenceCheckerEdgeLength_,
+                              cfg.correspondenceCheckerDistance_, n_iter, cfg.ransacProbability_)
+    assert len(validated) == r["validations"] and r["validations"] > 0
+    assert r["best_t"] >= 0
 
 
 # ---- 4. determinism -------------------------------------------------------------------------------------------------------------
