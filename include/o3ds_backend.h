@@ -549,6 +549,53 @@ typedef struct {
 int o3ds_ransac_feature_matching(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_ransac_params* params, uint64_t seed,
                                  o3ds_ransac_result* out, o3ds_ransac_trace* trace, size_t trace_cap);
 
+/* ---- pose-graph optimisation: OptimizationProblem::solve (src/OptimizationProblem.cpp:26-44) -----------------------------------------
+ * [O3D] GlobalOptimization(pose_graph, GlobalOptimizationLevenbergMarquardt(), criteria, option) of Open3D v0.15.1, restated:
+ *   1. ValidatePoseGraph: a graph that is not connected (over all edges), or a certain edge whose confidence is not 1, is Open3D's
+ *      "warn and return unchanged": O3DS_OK, out->valid = 0, poses and edges untouched.
+ *   2. an LM pass over every edge (the line-process weight preference * d^2 * mean(information(5,5)), the confidences of the uncertain
+ *      edges (mu / (mu + e^T Info e))^2, lambda0 = 1e-5 max diag(H), Open3D's stop checks);
+ *   3. CreatePoseGraphWithoutInvalidEdges: uncertain edges with confidence <= edge_prune_threshold are dropped (edge_kept[k] = 0);
+ *   4. a second LM pass on the pruned graph with its own line-process weight;
+ *   5. CompensateReferencePoseGraphNode: 0 <= reference_node < n_nodes keeps that node's input pose (every pose is premultiplied).
+ * Everything runs on the handle's stream in f64 whatever its storage precision: per-edge residuals and Jacobians, H (6N x 6N, dense)
+ * and b summed per block in edge order (no atomics), the solve of (H + lambda I) delta = b by Cholesky (one workgroup in LDS for
+ * 6N <= 128, blocked with an f64-MFMA trailing update above), the pose update and the step's sums in a fixed order.  The LM control
+ * flow runs on the host on those numbers, so a run is bit-reproducible.  A non-positive pivot is O3DS_ERR_INVALID_ARG.
+ * node_poses: n_nodes x 16 column-major, replaced by the optimised poses.  edges[k].confidence: in, Open3D's 1.0 by default for a new
+ * edge; out, its value after the last pass that held the edge.  Node ids out of range or a non-finite input: O3DS_ERR_INVALID_ARG.
+ * 0 or 1 nodes: valid = 1, nothing changes.  More than 4096 nodes (H and its factor are (6N)^2 doubles each, 4.8 GB at the cap) or
+ * 2^20 edges: O3DS_ERR_CAPACITY.  stop_reason: 0 none ran, 1 right term (max(b) < min_right_term), 2 relative increment, 3 relative
+ * residual increment, 4 residual, 5 max iteration, 6 max LM iteration (the first check that stopped the pass). */
+typedef struct {
+  int32_t source_node_id, target_node_id;
+  int32_t uncertain;          /* loop closures: 1, odometry: 0 */
+  int32_t pad;
+  double transformation[16];  /* column-major */
+  double information[36];     /* row-major 6x6 */
+  double confidence;          /* in: 1.0 (Open3D's default); out: final */
+} o3ds_pose_graph_edge;
+typedef struct {
+  double max_correspondence_distance; /* GlobalOptimizationParameters::maxCorrespondenceDistance_ */
+  double edge_prune_threshold;        /* edgePruneThreshold_ */
+  double preference_loop_closure;     /* loopClosurePreference_ */
+  int32_t reference_node;             /* referenceNode_, -1: none */
+  int32_t pad;
+} o3ds_global_optimization_option;
+typedef struct {
+  int32_t max_iteration, max_iteration_lm; /* Open3D's defaults: 100, 20 */
+  double min_relative_increment, min_relative_residual_increment, min_right_term, min_residual; /* 1e-6 each */
+  double upper_scale_factor, lower_scale_factor;                                               /* 2/3, 1/3 */
+} o3ds_global_optimization_criteria;
+typedef struct {
+  int32_t valid, n_edges_kept;
+  int32_t iterations[2], lm_steps[2], stop_reason[2]; /* per pass: outer iterations, linear solves, why it stopped */
+  double residual[2], line_process_weight[2];
+} o3ds_pose_graph_result;
+int o3ds_global_optimization(o3ds_handle h, double* node_poses, size_t n_nodes, o3ds_pose_graph_edge* edges, size_t n_edges,
+                             const o3ds_global_optimization_option* opt, const o3ds_global_optimization_criteria* crit, uint8_t* edge_kept,
+                             o3ds_pose_graph_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,27 @@ class RansacTrace(C.Structure):  # o3ds_ransac_trace
     _fields_ = [("sample", C.c_uint32 * 8), ("checks", C.c_int32), ("pairs", C.c_int32), ("error_sum", C.c_double),
                 ("transformation", C.c_double * 16)]
 
+
+class PoseGraphEdge(C.Structure):  # o3ds_pose_graph_edge
+    _fields_ = [("source_node_id", C.c_int32), ("target_node_id", C.c_int32), ("uncertain", C.c_int32), ("pad", C.c_int32),
+                ("transformation", C.c_double * 16), ("information", C.c_double * 36), ("confidence", C.c_double)]
+
+
+class GlobalOptimizationOption(C.Structure):  # o3ds_global_optimization_option
+    _fields_ = [("max_correspondence_distance", C.c_double), ("edge_prune_threshold", C.c_double), ("preference_loop_closure", C.c_double),
+                ("reference_node", C.c_int32), ("pad", C.c_int32)]
+
+
+class GlobalOptimizationCriteria(C.Structure):  # o3ds_global_optimization_criteria
+    _fields_ = [("max_iteration", C.c_int32), ("max_iteration_lm", C.c_int32), ("min_relative_increment", C.c_double),
+                ("min_relative_residual_increment", C.c_double), ("min_right_term", C.c_double), ("min_residual", C.c_double),
+                ("upper_scale_factor", C.c_double), ("lower_scale_factor", C.c_double)]
+
+
+class PoseGraphResult(C.Structure):  # o3ds_pose_graph_result
+    _fields_ = [("valid", C.c_int32), ("n_edges_kept", C.c_int32), ("iterations", C.c_int32 * 2), ("lm_steps", C.c_int32 * 2),
+                ("stop_reason", C.c_int32 * 2), ("residual", C.c_double * 2), ("line_process_weight", C.c_double * 2)]
+
 SIGNATURES = {
     "o3ds_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
     "o3ds_destroy": (C.c_int, [_H]),
@@ -165,6 +186,8 @@ SIGNATURES = {
                                                C.POINTER(C.c_int)]),
     "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
                                                C.POINTER(RansacTrace), C.c_size_t]),
+    "o3ds_global_optimization": (C.c_int, [_H, _dp, C.c_size_t, C.POINTER(PoseGraphEdge), C.c_size_t, C.POINTER(GlobalOptimizationOption),
+                                           C.POINTER(GlobalOptimizationCriteria), C.POINTER(C.c_uint8), C.POINTER(PoseGraphResult)]),
 }
 
 _lib = None
@@ -851,3 +874,35 @@ class Backend:
                               checks=a["checks"].astype(np.int64), pairs=a["pairs"].astype(np.int64), error_sum=a["error_sum"].copy(),
                               transformation=np.stack([from_colmajor(a["transformation"][k].copy()) for k in range(trace)]))
         return r
+
+    # -- pose-graph optimisation (o3ds_global_optimization)
+    def global_optimization(self, poses, edges, max_correspondence_distance: float = 0.075, edge_prune_threshold: float = 0.25,
+                            preference_loop_closure: float = 1.0, reference_node: int = -1, max_iteration: int = 100,
+                            max_iteration_lm: int = 20, min_relative_increment: float = 1e-6, min_relative_residual_increment: float = 1e-6,
+                            min_right_term: float = 1e-6, min_residual: float = 1e-6, upper_scale_factor: float = 2.0 / 3.0,
+                            lower_scale_factor: float = 1.0 / 3.0) -> dict:
+        """[O3D] GlobalOptimization with the LM method (defaults: Open3D's GlobalOptimizationOption / ConvergenceCriteria).  poses:
+        (n, 4, 4); edges: sequence of (source, target, transformation 4x4, information 6x6, uncertain[, confidence = 1.0]).  Returns
+        dict(poses (n, 4, 4), kept (bool per edge), confidence (per edge), valid, n_edges_kept, iterations, lm_steps, stop_reason,
+        residual, line_process_weight) -- the last five per pass."""
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)  # column-major
+        n = len(P) // 16
+        E = (PoseGraphEdge * max(len(edges), 1))()
+        for k, e in enumerate(edges):
+            E[k].source_node_id, E[k].target_node_id, E[k].uncertain = int(e[0]), int(e[1]), int(bool(e[4]))
+            E[k].transformation[:] = list(colmajor(e[2]))
+            E[k].information[:] = [float(v) for v in np.asarray(e[3], dtype=np.float64).reshape(36)]
+            E[k].confidence = float(e[5]) if len(e) > 5 else 1.0
+        o = GlobalOptimizationOption(float(max_correspondence_distance), float(edge_prune_threshold), float(preference_loop_closure),
+                                     int(reference_node), 0)
+        c = GlobalOptimizationCriteria(int(max_iteration), int(max_iteration_lm), float(min_relative_increment),
+                                       float(min_relative_residual_increment), float(min_right_term), float(min_residual),
+                                       float(upper_scale_factor), float(lower_scale_factor))
+        kept = np.ones(max(len(edges), 1), np.uint8)
+        out = PoseGraphResult()
+        self._ck(self.lib.o3ds_global_optimization(self.h, P.ctypes.data_as(_dp) if n else None, n, E if len(edges) else None, len(edges),
+                                                   C.byref(o), C.byref(c), kept.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
+        return dict(poses=P.reshape(n, 4, 4).transpose(0, 2, 1).copy(), kept=kept[: len(edges)].astype(bool),
+                    confidence=np.array([E[k].confidence for k in range(len(edges))]), valid=bool(out.valid),
+                    n_edges_kept=int(out.n_edges_kept), iterations=list(out.iterations), lm_steps=list(out.lm_steps),
+                    stop_reason=list(out.stop_reason), residual=list(out.residual), line_process_weight=list(out.line_process_weight))

@@ -26,6 +26,7 @@
 #include "icp_kernels.hpp"
 #include "map_kernels.hpp"
 #include "normals_kernel.hpp"
+#include "pose_graph_kernels.hpp"
 
 using namespace o3ds;
 
@@ -4882,6 +4883,367 @@ int o3ds_ransac_feature_matching(o3ds_handle h, o3ds_cloud source, o3ds_cloud ta
   // [O3D] RegistrationRANSACBasedOnCorrespondence: the empty RegistrationResult
   if (params->ransac_n < 3 || pairs.size() / 2 < (size_t)params->ransac_n || !(params->max_correspondence_distance > 0.0)) return O3DS_OK;
   return DISPATCH(s->precision, ransac_t, h, *s, *t, params, seed, pairs, out, trace, trace_cap);
+}
+
+}  // extern "C"
+
+// ---- pose-graph optimisation (o3ds_global_optimization) ------------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kPgMaxNodes = 4096, kPgMaxEdges = (size_t)1 << 20;  // the caps o3ds_backend.h documents
+
+struct DevBlock {  // a device block outside the arena (H and its factor are up to 4.8 GB each: they go back to the pool on return)
+  o3ds_handle h;
+  void* p = nullptr;
+  explicit DevBlock(o3ds_handle hh) : h(hh) {}
+  ~DevBlock() { dev_free(h, p); }
+};
+
+struct PgCtx {
+  int n = 0, m = 0, nb = 0;
+  size_t M = 0;
+  double* poses[2] = {nullptr, nullptr};
+  double* H = nullptr;
+  double* L = nullptr;
+  double *b[2] = {nullptr, nullptr}, *bw = nullptr, *y = nullptr, *x = nullptr, *part = nullptr;
+  PgRecord* rec = nullptr;
+  int cur = 0;  // poses[cur] are the graph's current poses
+};
+
+int pg_read(o3ds_handle h, PgCtx& C, PgRecord* r) {
+  int rc = read_back(h, {{r, C.rec, sizeof(PgRecord)}});
+  if (rc) return rc;
+  if (r->err) return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: H + lambda I is not positive definite (pivot of row " + std::to_string(r->err - 1) + ")");
+  return O3DS_OK;
+}
+
+int pg_solve(o3ds_handle h, PgCtx& C, const double* b, double lambda) {
+  if (C.m <= kPgSmallMax) {
+    pg_small_solve_kernel<<<1, kPgSmallThreads, 0, h->stream>>>(C.H, C.M, C.m, lambda, b, C.x, C.rec);
+    HIP_TRY(hipGetLastError());
+    return O3DS_OK;
+  }
+  const size_t MM = C.M * C.M;
+  pg_shift_copy_kernel<<<(int)std::min<size_t>((MM + 255) / 256, 8192), 256, 0, h->stream>>>(C.H, C.L, C.M, lambda);
+  for (int k = 0; k < C.nb; ++k) {
+    pg_panel_kernel<<<1, 256, 0, h->stream>>>(C.L, C.M, k, C.rec);
+    const int rest = C.nb - k - 1;
+    if (rest > 0) {
+      pg_trsm_kernel<<<rest, kPgNB, 0, h->stream>>>(C.L, C.M, k);
+      pg_syrk_kernel<<<dim3(rest, rest), 256, 0, h->stream>>>(C.L, C.M, k);
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(C.bw, b, C.M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  for (int k = 0; k < C.nb; ++k) pg_fwd_kernel<<<C.nb - k, kPgNB, 0, h->stream>>>(C.L, C.M, k, C.bw, C.y);
+  for (int k = C.nb - 1; k >= 0; --k) pg_bwd_kernel<<<k + 1, kPgNB, 0, h->stream>>>(C.L, C.M, k, C.y, C.x);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+// One GlobalOptimizationLevenbergMarquardt::OptimizePoseGraph over the edges `ids` of `all`: the poses in C.poses[C.cur] move, conf[k]
+// (indexed like ids) is updated.  The host runs Open3D's control flow on the numbers of the device record.
+int pg_pass(o3ds_handle h, PgCtx& C, const o3ds_pose_graph_edge* all, const std::vector<int>& ids, std::vector<double>& conf,
+            const o3ds_global_optimization_option* opt, const o3ds_global_optimization_criteria* crit, int pass, o3ds_pose_graph_result* out) {
+  const int ne = (int)ids.size(), n = C.n;
+  // ComputeLineProcessWeight: serial, in edge order
+  double lpw = 0.0;
+  if (ne > 0) {
+    double avg = 0.0;
+    for (int k = 0; k < ne; ++k) avg += all[ids[k]].information[5 * 6 + 5];
+    avg /= (double)ne;
+    lpw = opt->preference_loop_closure * std::pow(opt->max_correspondence_distance, 2) * avg;
+  }
+  out->line_process_weight[pass] = lpw;
+  // edges, confidences, the per-block and per-node lists (the graph's structure is fixed for the pass)
+  std::vector<PgEdgeIn> ein((size_t)ne);
+  std::map<std::pair<int, int>, std::vector<int>> blk;
+  std::vector<std::vector<int>> nod((size_t)n);
+  for (int k = 0; k < ne; ++k) {
+    const o3ds_pose_graph_edge& e = all[ids[k]];
+    PgEdgeIn& d = ein[(size_t)k];
+    memcpy(d.X, e.transformation, sizeof(d.X));
+    memcpy(d.info, e.information, sizeof(d.info));
+    d.src = e.source_node_id, d.tgt = e.target_node_id, d.uncertain = e.uncertain ? 1 : 0, d.pad = 0;
+    const int s = d.src, t = d.tgt;  // Open3D's order: H_ss += P, H_st += -P, H_ts += -P, H_tt += P; b_s -= q, b_t -= -q
+    blk[{s, s}].push_back(2 * k);
+    blk[{s, t}].push_back(2 * k + 1);
+    blk[{t, s}].push_back(2 * k + 1);
+    blk[{t, t}].push_back(2 * k);
+    nod[(size_t)s].push_back(2 * k);
+    nod[(size_t)t].push_back(2 * k + 1);
+  }
+  std::vector<int4> blocks;
+  std::vector<int> hlist, blist;
+  for (auto& kv : blk) {
+    blocks.push_back(make_int4(kv.first.first, kv.first.second, (int)hlist.size(), (int)kv.second.size()));
+    hlist.insert(hlist.end(), kv.second.begin(), kv.second.end());
+  }
+  std::vector<int2> nodes((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    nodes[(size_t)i] = make_int2((int)blist.size(), (int)nod[(size_t)i].size());
+    blist.insert(blist.end(), nod[(size_t)i].begin(), nod[(size_t)i].end());
+  }
+  PgEdgeIn* d_e = nullptr;
+  double *d_conf[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+  int4* d_blocks = nullptr;
+  int2* d_nodes = nullptr;
+  int *d_hl = nullptr, *d_bl = nullptr;
+  TMP_ALLOC(d_e, std::max<size_t>(1, ein.size()) * sizeof(PgEdgeIn));
+  for (int s = 0; s < 2; ++s) {
+    TMP_ALLOC(d_conf[s], std::max(1, ne) * sizeof(double));
+    TMP_ALLOC(d_out[s], (size_t)std::max(1, ne) * kPgEdgeOut * sizeof(double));
+  }
+  TMP_ALLOC(d_blocks, std::max<size_t>(1, blocks.size()) * sizeof(int4));
+  TMP_ALLOC(d_hl, std::max<size_t>(1, hlist.size()) * sizeof(int));
+  TMP_ALLOC(d_nodes, (size_t)n * sizeof(int2));
+  TMP_ALLOC(d_bl, std::max<size_t>(1, blist.size()) * sizeof(int));
+  int rc = O3DS_OK;
+  if (ne > 0) {
+    if ((rc = h2d_copy(h, d_e, ein.data(), ein.size() * sizeof(PgEdgeIn)))) return rc;
+    if ((rc = h2d_copy(h, d_conf[0], conf.data(), (size_t)ne * sizeof(double)))) return rc;
+    if ((rc = h2d_copy(h, d_blocks, blocks.data(), blocks.size() * sizeof(int4)))) return rc;
+    if ((rc = h2d_copy(h, d_hl, hlist.data(), hlist.size() * sizeof(int)))) return rc;
+    if ((rc = h2d_copy(h, d_bl, blist.data(), blist.size() * sizeof(int)))) return rc;
+  }
+  if ((rc = h2d_copy(h, d_nodes, nodes.data(), nodes.size() * sizeof(int2)))) return rc;
+  HIP_TRY(hipMemsetAsync(C.rec, 0, sizeof(PgRecord), h->stream));
+  HIP_TRY(hipMemsetAsync(C.b[0], 0, C.M * sizeof(double), h->stream));
+  HIP_TRY(hipMemsetAsync(C.b[1], 0, C.M * sizeof(double), h->stream));
+  pg_init_h_kernel<<<(int)std::min<size_t>((C.M * C.M + 255) / 256, 8192), 256, 0, h->stream>>>(C.H, C.M, (size_t)C.m);
+  int cc = 0, co = 0, cb = 0;  // current confidences, edge outputs, b
+  const int eg = (ne + 63) / 64, ng = (6 * n + 63) / 64, ug = (n + 63) / 64, nbk = (int)blocks.size();
+  auto edge_pass = [&](const double* poses, int cin, int cout, int eo) {
+    if (ne > 0)
+      pg_edge_kernel<<<eg, 64, 0, h->stream>>>(poses, d_e, ne, d_conf[cin], d_conf[cout], d_out[eo], lpw, opt->edge_prune_threshold);
+  };
+  auto assemble_b = [&](int eo, int bo) {
+    if (ne > 0) pg_assemble_b_kernel<<<ng, 64, 0, h->stream>>>(d_nodes, d_bl, d_out[eo], n, C.b[bo]);
+  };
+  // initial: the residual with the confidences as given, then UpdateConfidence, then ComputeLinearSystem
+  edge_pass(C.poses[C.cur], 0, 1, 0);
+  cc = ne > 0 ? 1 : 0;
+  if (nbk) pg_assemble_h_kernel<<<nbk, 64, 0, h->stream>>>(d_blocks, d_hl, d_out[0], C.H, C.M);
+  assemble_b(0, 0);
+  pg_reduce_kernel<<<1, kPgRed, 0, h->stream>>>(d_out[0], ne, nullptr, n, C.b[0], C.H, C.M, C.m, C.rec);
+  HIP_TRY(hipGetLastError());
+  PgRecord R;
+  if ((rc = pg_read(h, C, &R))) return rc;
+  double current_residual = R.residual, new_residual = R.residual;
+  double lambda = 1e-5 * R.maxdiag, ni = 2.0, rho = 0.0;
+  int reason = 0, iters = 0, lm_steps = 0;
+  bool stop = false;
+  auto set_stop = [&](bool c, int why) {
+    if (!stop && c) stop = true, reason = why;
+  };
+  if (R.maxb < crit->min_right_term) {
+    reason = 1;
+  } else {
+    for (int iter = 0; !stop; ++iter) {
+      int lm_count = 0;
+      for (;;) {
+        if ((rc = pg_solve(h, C, C.b[cb], lambda))) return rc;
+        const int nw = C.cur ^ 1;
+        pg_update_kernel<<<ug, 64, 0, h->stream>>>(C.poses[C.cur], C.x, C.b[cb], lambda, n, C.poses[nw], C.part);
+        edge_pass(C.poses[nw], cc, cc ^ 1, co ^ 1);
+        assemble_b(co ^ 1, cb ^ 1);
+        pg_reduce_kernel<<<1, kPgRed, 0, h->stream>>>(d_out[co ^ 1], ne, C.part, n, C.b[cb ^ 1], nullptr, C.M, C.m, C.rec);
+        HIP_TRY(hipGetLastError());
+        if ((rc = pg_read(h, C, &R))) return rc;
+        ++lm_steps;
+        set_stop(std::sqrt(R.dn2) < crit->min_relative_increment * (std::sqrt(R.xn2) + crit->min_relative_increment), 2);
+        if (!stop) {
+          new_residual = R.residual;  // with the old graph's confidences
+          rho = (current_residual - new_residual) / (R.ddb + 1e-3);
+          if (rho > 0) {
+            set_stop(current_residual - new_residual < crit->min_relative_residual_increment * current_residual, 3);
+            double alpha = 1. - std::pow(2 * rho - 1, 3);
+            alpha = std::min(alpha, crit->upper_scale_factor);
+            lambda *= std::max(crit->lower_scale_factor, alpha);
+            ni = 2;
+            current_residual = new_residual;
+            C.cur = nw;  // pose_graph = *pose_graph_new, its confidences updated, its linear system
+            cc ^= ne > 0 ? 1 : 0;
+            co ^= 1;
+            cb ^= 1;
+            set_stop(R.maxb < crit->min_right_term, 1);
+            if (stop) break;
+            if (nbk) pg_assemble_h_kernel<<<nbk, 64, 0, h->stream>>>(d_blocks, d_hl, d_out[co], C.H, C.M);
+          } else {
+            lambda *= ni;
+            ni *= 2;
+          }
+        }
+        ++lm_count;
+        set_stop(lm_count >= crit->max_iteration_lm, 6);
+        if (rho > 0 || stop) break;
+      }
+      set_stop(current_residual < crit->min_residual, 4);
+      set_stop(iter >= crit->max_iteration, 5);
+      iters = iter + 1;
+    }
+  }
+  out->iterations[pass] = iters;
+  out->lm_steps[pass] = lm_steps;
+  out->stop_reason[pass] = reason;
+  out->residual[pass] = current_residual;
+  if (ne > 0) return d2h_copy(h, conf.data(), d_conf[cc], (size_t)ne * sizeof(double));
+  return O3DS_OK;
+}
+
+void pg_inv4_host(const double* cm, double* out_cm) {  // column-major in and out, the kernel's cofactor inverse
+  double m[16], o[16];
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) m[r * 4 + c] = cm[c * 4 + r];
+  double inv[16];
+  inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+  inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+  inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+  inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+  inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+  inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+  inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+  inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+  inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+  inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+  inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+  inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+  inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+  inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+  inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+  inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+  const double rdet = 1.0 / (m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12]);
+  for (int k = 0; k < 16; ++k) o[k] = inv[k] * rdet;
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) out_cm[c * 4 + r] = o[r * 4 + c];
+}
+
+void pg_mul4_host(const double* a, const double* b, double* o) {  // column-major
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r) {
+      double s = a[r] * b[c * 4];
+      for (int k = 1; k < 4; ++k) s += a[k * 4 + r] * b[c * 4 + k];
+      o[c * 4 + r] = s;
+    }
+}
+
+bool pg_connected(size_t n, const o3ds_pose_graph_edge* edges, size_t ne) {  // ValidatePoseGraphConnectivity(pose_graph, false)
+  if (n == 0) return true;
+  std::vector<std::vector<int>> adj(n);
+  for (size_t k = 0; k < ne; ++k) {
+    adj[(size_t)edges[k].source_node_id].push_back(edges[k].target_node_id);
+    adj[(size_t)edges[k].target_node_id].push_back(edges[k].source_node_id);
+  }
+  std::vector<char> seen(n, 0);
+  std::vector<int> todo{0};
+  seen[0] = 1;
+  size_t count = 1;
+  while (!todo.empty()) {
+    const int i = todo.back();
+    todo.pop_back();
+    for (int j : adj[(size_t)i])
+      if (!seen[(size_t)j]) seen[(size_t)j] = 1, ++count, todo.push_back(j);
+  }
+  return count == n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int o3ds_global_optimization(o3ds_handle h, double* node_poses, size_t n_nodes, o3ds_pose_graph_edge* edges, size_t n_edges,
+                             const o3ds_global_optimization_option* opt, const o3ds_global_optimization_criteria* crit, uint8_t* edge_kept,
+                             o3ds_pose_graph_result* out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!opt || !crit || !out || (n_nodes && !node_poses) || (n_edges && !edges))
+    return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: null argument");
+  memset(out, 0, sizeof(*out));
+  out->n_edges_kept = (int32_t)std::min<size_t>(n_edges, INT32_MAX);
+  if (edge_kept)
+    for (size_t k = 0; k < n_edges; ++k) edge_kept[k] = 1;
+  if (n_nodes > kPgMaxNodes || n_edges > kPgMaxEdges)
+    return fail(h, O3DS_ERR_CAPACITY, "global_optimization: more than 4096 nodes or 2^20 edges");
+  for (size_t k = 0; k < n_edges; ++k) {
+    const o3ds_pose_graph_edge& e = edges[k];
+    if (e.source_node_id < 0 || (size_t)e.source_node_id >= n_nodes || e.target_node_id < 0 || (size_t)e.target_node_id >= n_nodes)
+      return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: edge " + std::to_string(k) + " references a node out of range");
+    bool ok = std::isfinite(e.confidence);
+    for (int i = 0; i < 16; ++i) ok = ok && std::isfinite(e.transformation[i]);
+    for (int i = 0; i < 36; ++i) ok = ok && std::isfinite(e.information[i]);
+    if (!ok) return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: edge " + std::to_string(k) + " has a non-finite value");
+  }
+  for (size_t i = 0; i < n_nodes * 16; ++i)
+    if (!std::isfinite(node_poses[i])) return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: a node pose has a non-finite value");
+  const double o3[] = {opt->max_correspondence_distance, opt->edge_prune_threshold, opt->preference_loop_closure, crit->min_relative_increment,
+                       crit->min_relative_residual_increment, crit->min_right_term, crit->min_residual, crit->upper_scale_factor,
+                       crit->lower_scale_factor};
+  for (double v : o3)
+    if (!std::isfinite(v)) return fail(h, O3DS_ERR_INVALID_ARG, "global_optimization: a non-finite option or criterion");
+  // ValidatePoseGraph: Open3D warns and returns the graph unchanged
+  if (!pg_connected(n_nodes, edges, n_edges)) return O3DS_OK;
+  for (size_t k = 0; k < n_edges; ++k)
+    if (!edges[k].uncertain && edges[k].confidence != 1.0) return O3DS_OK;
+  out->valid = 1;
+  if (n_nodes <= 1) return O3DS_OK;
+
+  PgCtx C;
+  C.n = (int)n_nodes;
+  C.m = 6 * C.n;
+  C.M = ((size_t)C.m + kPgNB - 1) / kPgNB * kPgNB;
+  C.nb = (int)(C.M / kPgNB);
+  DevBlock hb(h), lb(h);
+  const size_t mat = C.M * C.M * sizeof(double);
+  if (dev_alloc(h, &hb.p, mat) != hipSuccess) return fail(h, O3DS_ERR_OOM, "global_optimization: out of memory for H");
+  C.H = (double*)hb.p;
+  if (C.m > kPgSmallMax) {
+    if (dev_alloc(h, &lb.p, mat) != hipSuccess) return fail(h, O3DS_ERR_OOM, "global_optimization: out of memory for the factor");
+    C.L = (double*)lb.p;
+  }
+  for (int s = 0; s < 2; ++s) {
+    TMP_ALLOC(C.poses[s], n_nodes * 16 * sizeof(double));
+    TMP_ALLOC(C.b[s], C.M * sizeof(double));
+  }
+  TMP_ALLOC(C.bw, C.M * sizeof(double));
+  TMP_ALLOC(C.y, C.M * sizeof(double));
+  TMP_ALLOC(C.x, C.M * sizeof(double));
+  TMP_ALLOC(C.part, n_nodes * 3 * sizeof(double));
+  TMP_ALLOC(C.rec, sizeof(PgRecord));
+  int rc = h2d_copy(h, C.poses[0], node_poses, n_nodes * 16 * sizeof(double));
+  if (rc) return rc;
+  // pass 1 on every edge
+  std::vector<int> ids(n_edges);
+  std::vector<double> conf(n_edges);
+  for (size_t k = 0; k < n_edges; ++k) ids[k] = (int)k, conf[k] = edges[k].confidence;
+  if ((rc = pg_pass(h, C, edges, ids, conf, opt, crit, 0, out))) return rc;
+  // CreatePoseGraphWithoutInvalidEdges, pass 2 with the kept edges' confidences
+  std::vector<int> kept;
+  std::vector<double> conf2;
+  std::vector<double> final_conf(conf);
+  for (size_t k = 0; k < n_edges; ++k)
+    if (!edges[k].uncertain || conf[k] > opt->edge_prune_threshold) kept.push_back((int)k), conf2.push_back(conf[k]);
+  if ((rc = pg_pass(h, C, edges, kept, conf2, opt, crit, 1, out))) return rc;
+  for (size_t j = 0; j < kept.size(); ++j) final_conf[(size_t)kept[j]] = conf2[j];
+  std::vector<double> poses(n_nodes * 16);
+  if ((rc = d2h_copy(h, poses.data(), C.poses[C.cur], poses.size() * sizeof(double)))) return rc;
+  // CompensateReferencePoseGraphNode
+  const int ref = opt->reference_node;
+  if (ref >= 0 && (size_t)ref < n_nodes) {
+    double inv[16], comp[16], tmp[16];
+    pg_inv4_host(&poses[(size_t)ref * 16], inv);
+    pg_mul4_host(&node_poses[(size_t)ref * 16], inv, comp);
+    for (size_t i = 0; i < n_nodes; ++i) {
+      pg_mul4_host(comp, &poses[i * 16], tmp);
+      memcpy(&poses[i * 16], tmp, sizeof(tmp));
+    }
+  }
+  memcpy(node_poses, poses.data(), poses.size() * sizeof(double));
+  for (size_t k = 0; k < n_edges; ++k) edges[k].confidence = final_conf[k];
+  if (edge_kept) {
+    for (size_t k = 0; k < n_edges; ++k) edge_kept[k] = 0;
+    for (int k : kept) edge_kept[(size_t)k] = 1;
+  }
+  out->n_edges_kept = (int32_t)kept.size();
+  return O3DS_OK;
 }
 
 }  // extern "C"

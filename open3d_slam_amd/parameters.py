@@ -136,6 +136,19 @@ def lua_place_recognition_parameters() -> PlaceRecognitionParameters:
 
 
 @dataclasses.dataclass
+class GlobalOptimizationParameters:  # Parameters.hpp:138-143
+    maxCorrespondenceDistance_: float = 10.0
+    loopClosurePreference_: float = 2.0
+    edgePruneThreshold_: float = 0.2
+    referenceNode_: int = 0
+
+
+def lua_global_optimization_parameters() -> GlobalOptimizationParameters:
+    """GLOBAL_OPTIMIZATION_PARAMETERS of the shipped Lua (ros/open3d_slam_ros/param/default/parameter_structure_definitions.lua:45-50)."""
+    return GlobalOptimizationParameters(maxCorrespondenceDistance_=1000.0, loopClosurePreference_=2.0, edgePruneThreshold_=0.2, referenceNode_=0)
+
+
+@dataclasses.dataclass
 class MapperParameters:  # Parameters.hpp:158-178 (hot-path subset)
     scanMatcher_: ScanToMapRegistrationParameters = dataclasses.field(default_factory=ScanToMapRegistrationParameters)
     scanProcessing_: ScanProcessingParameters = dataclasses.field(default_factory=ScanProcessingParameters)
@@ -147,6 +160,8 @@ class MapperParameters:  # Parameters.hpp:158-178 (hot-path subset)
     isUseInitialMap_: bool = False
     isMergeScansIntoMap_: bool = True
     placeRecognition_: PlaceRecognitionParameters = dataclasses.field(default_factory=PlaceRecognitionParameters)
+    globalOptimization_: GlobalOptimizationParameters = dataclasses.field(default_factory=GlobalOptimizationParameters)
+    isRefineOdometryConstraintsBetweenSubmaps_: bool = False  # Parameters.hpp:172
 
 
 def lua_default_mapper_parameters() -> MapperParameters:
