@@ -357,8 +357,14 @@ int o3ds_random_down_sample(o3ds_handle h, o3ds_cloud in, double ratio, uint64_t
 
 /* ---- map fusion: Submap::insertScan (Submap.cpp:39-75) ------------------------------------- */
 /* o3d_slam::transform (helpers.cpp:273-305): p' = (T p).xyz/w, n' = R n.  Returns a new cloud.
- * (The reference's duplicate-on-identity quirk, SURVEY B4, is intentionally not reproduced.) */
+ * (The reference's duplicate-on-identity quirk, SURVEY B4, is intentionally not reproduced.)  FPFH features of the input
+ * (o3ds_compute_fpfh) are carried over unchanged, as [O3D] PointCloud::Transform leaves a Feature alone. */
 int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_cloud* out);
+/* The mean of the points, [O3D] PointCloud::GetCenter as Submap::computeSubmapCenter (Submap.cpp:255-259) uses it: summed in f64
+ * whatever the storage precision, in one fixed order that depends on the number of points only (not on the device, the handle or whether
+ * the host knew the size), so repeated calls give the same bits; non-finite points propagate into the mean; an empty cloud gives
+ * (0, 0, 0).  A submap in its persistent form is first turned into its array (as a download would).  Waits for the result. */
+int o3ds_cloud_center(o3ds_handle h, o3ds_cloud c, double center[3]);
 /* mapCloud_ += cloud (Submap.cpp:70; [O3D] PointCloud::operator+=). Appends `add` to `map` in place. */
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add);
 /* A copy of a cloud of handle `src` as a cloud of handle `dst` (same device, same storage precision), device to device: points,

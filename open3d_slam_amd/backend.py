@@ -175,6 +175,7 @@ SIGNATURES = {
     "o3ds_select_by_index": (C.c_int, [_H, _CL, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(_CL)]),
     "o3ds_random_down_sample": (C.c_int, [_H, _CL, C.c_double, C.c_uint64, C.POINTER(_CL)]),
     "o3ds_transform_cloud": (C.c_int, [_H, _CL, _dp, C.POINTER(_CL)]),
+    "o3ds_cloud_center": (C.c_int, [_H, _CL, _dp]),
     "o3ds_cloud_append": (C.c_int, [_H, _CL, _CL]),
     "o3ds_cloud_copy_across": (C.c_int, [_H, _H, _CL, C.POINTER(_CL)]),
     "o3ds_voxelize_within_volume": (C.c_int, [_H, _CL, C.c_double, C.POINTER(Crop)]),
@@ -714,6 +715,12 @@ class Backend:
         out = _CL()
         self._ck(self.lib.o3ds_transform_cloud(self.h, cid, tp, C.byref(out)))
         return out.value
+
+    def cloud_center(self, cid: int) -> np.ndarray:
+        """[O3D] PointCloud::GetCenter on the device (f64 sums in a fixed order; (0, 0, 0) for an empty cloud)"""
+        out = np.zeros(3)
+        self._ck(self.lib.o3ds_cloud_center(self.h, cid, out.ctypes.data_as(_dp)))
+        return out
 
     def cloud_append(self, map_id: int, add_id: int):
         self._ck(self.lib.o3ds_cloud_append(self.h, map_id, add_id))

@@ -3148,6 +3148,13 @@ int transform_t(o3ds_handle h, const CloudRec& in, const double T[16], CloudRec&
     HIP_TRY(dev_alloc(h, (void**)&out.col, sizeof(P4) * in.n));
     HIP_TRY(hipMemcpyAsync(out.col, in.col, sizeof(P4) * in.n, hipMemcpyDeviceToDevice, h->stream));
   }
+  if (in.has_fpfh && in.fpfh_n == in.n && in.fpfh) {  // [O3D] PointCloud::Transform leaves a Feature as it is (Submap::transform moves the
+    const size_t bytes = in.n * kFeatDim * sizeof(double);  // sparse map, Submap.cpp:96, and keeps feature_)
+    HIP_TRY(dev_alloc(h, (void**)&out.fpfh, bytes));
+    HIP_TRY(hipMemcpyAsync(out.fpfh, in.fpfh, bytes, hipMemcpyDeviceToDevice, h->stream));
+    out.has_fpfh = true;
+    out.fpfh_n = in.n;
+  }
   HIP_TRY(hipGetLastError());
   return O3DS_OK;
 }
@@ -3608,6 +3615,32 @@ int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_
   }
   *out = add_cloud(h, std::move(o));
   return O3DS_OK;
+}
+
+int o3ds_cloud_center(o3ds_handle h, o3ds_cloud cloud, double center[3]) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  CloudRec* c = find_cloud_lazy(h, cloud);  // (the size may still be on its way: the kernels read it from the device word)
+  if (!c || !center) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_center: bad argument");
+  if (c->pm) {  // a submap in its persistent form: the mean of the reference's array (the sum's order is the array's)
+    const int rc = pm_exit(h, *c);
+    if (rc) return rc;
+  }
+  if (c->n == 0) {  // (n is an upper bound: zero is exact)
+    center[0] = center[1] = center[2] = 0.0;
+    return O3DS_OK;
+  }
+  double *partial = nullptr, *d_out = nullptr;
+  TMP_ALLOC(partial, sizeof(double) * 3 * kCenterChunks);
+  TMP_ALLOC(d_out, sizeof(double) * 3);
+  const CountRef cnt = count_ref(h, *c);
+  if (c->precision == O3DS_PRECISION_F64)
+    center_partial_kernel<P4d><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4d*)c->pts, cnt, partial);
+  else
+    center_partial_kernel<P4f><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4f*)c->pts, cnt, partial);
+  center_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, cnt, d_out);
+  HIP_TRY(hipGetLastError());
+  return read_back(h, {{center, d_out, sizeof(double) * 3}});
 }
 
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add) {

@@ -336,6 +336,72 @@ __global__ __launch_bounds__(kBlock) void transform_kernel(const P4* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------- centre of a cloud
+// [O3D] PointCloud::GetCenter (the plain mean of the points), Submap::computeSubmapCenter (Submap.cpp:255-259).  The sum is f64 whatever
+// the storage, in ONE order that depends on n only: kCenterChunks workgroups of kBlock threads, always, each owning the contiguous chunk
+// [c * len, (c + 1) * len) with len = ceil(n / kCenterChunks); thread t adds the points lo + t, lo + t + kBlock, ... one after the other;
+// a fixed halving tree over the threads, then (center_finish_kernel) the same tree over the chunks.  Nothing depends on the device, the
+// handle or on whether n came from the host or from the device word, so two runs give the same bits.  Error of each sum: about
+// (n / (kCenterChunks * kBlock) + 16) ulp of max |p| * n, far below the 1e-12 the mirror promises.  NaN / Inf propagate as in the
+// reference's Eigen sum.  Empty cloud: (0, 0, 0), as GetCenter returns.
+constexpr int kCenterChunks = 256;
+static_assert(kCenterChunks == kBlock, "center_finish_kernel gives one chunk to each thread");
+
+__device__ __forceinline__ void center_tree(double* sx, double* sy, double* sz, int t) {
+  for (int s = kBlock / 2; s >= 1; s >>= 1) {
+    __syncthreads();
+    if (t < s) {
+      sx[t] += sx[t + s];
+      sy[t] += sy[t + s];
+      sz[t] += sz[t + s];
+    }
+  }
+  __syncthreads();
+}
+
+template <typename P4>
+__global__ __launch_bounds__(kBlock) void center_partial_kernel(const P4* __restrict__ pts, CountRef cnt, double* __restrict__ partial) {
+  __shared__ double sx[kBlock], sy[kBlock], sz[kBlock];
+  const int t = threadIdx.x;
+  const size_t n = count_of(cnt);
+  const size_t len = (n + kCenterChunks - 1) / kCenterChunks;
+  const size_t lo = (size_t)blockIdx.x * len;
+  const size_t hi = lo + len < n ? lo + len : n;
+  double x = 0.0, y = 0.0, z = 0.0;
+  for (size_t i = lo + (size_t)t; i < hi; i += kBlock) {
+    const P4 p = pts[i];
+    x += (double)p.x;
+    y += (double)p.y;
+    z += (double)p.z;
+  }
+  sx[t] = x;
+  sy[t] = y;
+  sz[t] = z;
+  center_tree(sx, sy, sz, t);
+  if (t == 0) {
+    partial[3 * blockIdx.x] = sx[0];
+    partial[3 * blockIdx.x + 1] = sy[0];
+    partial[3 * blockIdx.x + 2] = sz[0];
+  }
+}
+
+// one workgroup: the chunk sums in the same fixed tree, divided by n
+__global__ __launch_bounds__(kBlock) void center_finish_kernel(const double* __restrict__ partial, CountRef cnt, double* __restrict__ out) {
+  __shared__ double sx[kBlock], sy[kBlock], sz[kBlock];
+  const int t = threadIdx.x;
+  sx[t] = partial[3 * t];
+  sy[t] = partial[3 * t + 1];
+  sz[t] = partial[3 * t + 2];
+  center_tree(sx, sy, sz, t);
+  if (t == 0) {
+    const size_t n = count_of(cnt);
+    const double d = (double)n;
+    out[0] = n ? sx[0] / d : 0.0;
+    out[1] = n ? sy[0] / d : 0.0;
+    out[2] = n ? sz[0] / d : 0.0;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- constant-velocity de-skew
 // ConstantVelocityMotionCompensation::undistortInputPointCloud (MotionCompensation.cpp:64-139), in place: the phase of a point is
 // its azimuth / 2 pi (1 - that for a clockwise sensor, 0 at azimuth exactly 0), its motion T(phase * D * v, Rz Ry Rx(phase * D * w)).

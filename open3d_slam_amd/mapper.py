@@ -1,7 +1,7 @@
-"""Mapper::addRangeMeasurement (include/open3d_slam/Mapper.hpp:47, src/Mapper.cpp:101-181) for ONE active submap:
-the caller of the scan-to-map hot path, kept as a thin host harness with the reference's names.  Submap switching,
-loop-closure candidate selection and the dense map are out of scope here; place recognition
-between submaps is place_recognition.py."""
+"""Mapper::addRangeMeasurement (include/open3d_slam/Mapper.hpp:47, src/Mapper.cpp:101-181): the caller of the scan-to-map hot path,
+kept as a thin host harness with the reference's names.  Without `submaps` it holds ONE submap (the path bench.py measures); with a
+SubmapCollection (submap_collection.py) it switches submaps as the reference's Mapper does, and loop_closure.py closes loops over
+them.  The dense map is out of scope here."""
 from __future__ import annotations
 
 import numpy as np
@@ -14,11 +14,13 @@ from .submap import Submap
 
 
 class Mapper:
-    def __init__(self, be, odometry: LidarOdometry | None = None):
+    def __init__(self, be, odometry: LidarOdometry | None = None, submaps=None):
+        """submaps: a SubmapCollection to map into (Mapper.cpp:30-33); None: one submap of this mapper's own."""
         self.be = be
         self.odometry_ = odometry
         self.params_ = MapperParameters()
-        self.submap_ = Submap(be)
+        self.submaps_ = submaps
+        self.submap_ = Submap(be) if submaps is None else None
         self.mapToRangeSensor_ = np.eye(4)
         self.mapToRangeSensorPrev_ = np.eye(4)
         self.mapToRangeSensorLastScanInsertion_ = np.eye(4)
@@ -33,23 +35,36 @@ class Mapper:
 
     def update(self, p: MapperParameters):  # Mapper.cpp:53-56
         self.scan2MapReg_ = scanToMapRegistrationFactory(p)
-        self.submap_.setParameters(p)
+        if self.submaps_ is None:
+            self.submap_.setParameters(p)
+        else:
+            self.submaps_.setParameters(p)
 
     def getActiveSubmap(self) -> Submap:
-        return self.submap_
+        return self.submap_ if self.submaps_ is None else self.submaps_.getActiveSubmap()
 
-    def getAssembledMapPointCloud(self) -> PointCloud:  # Mapper.cpp:183-208 (this harness holds one submap)
+    def getSubmaps(self):
+        return self.submaps_
+
+    def getAssembledMapPointCloud(self) -> PointCloud:  # Mapper.cpp:183-208: every submap's map, in submap order
         from .output import assembleMapPointCloud
-        return assembleMapPointCloud(self.be, [self.submap_])
+        return assembleMapPointCloud(self.be, [self.submap_] if self.submaps_ is None else self.submaps_.submaps_)
+
+    def loopClosureUpdate(self, loopClosureCorrection):  # Mapper.cpp:44-47
+        dT = np.array(loopClosureCorrection, dtype=np.float64)
+        self.mapToRangeSensor_ = dT @ self.mapToRangeSensor_
+        self.mapToRangeSensorPrev_ = dT @ self.mapToRangeSensorPrev_
 
     def getMapToRangeSensor(self) -> np.ndarray:
         return self.mapToRangeSensor_
 
     def addRangeMeasurement(self, rawScan: PointCloud, timestamp: float) -> bool:
         p = self.params_
-        if self.submap_.isEmpty():  # Mapper.cpp:105-114: insert the first scan at identity
+        if self.submaps_ is not None:
+            self.submaps_.setMapToRangeSensor(self.mapToRangeSensor_)
+        if self.getActiveSubmap().isEmpty():  # Mapper.cpp:105-114: insert the first scan at identity
             processed = self.scan2MapReg_.processForScanMatchingAndMerging(rawScan, self.mapToRangeSensor_)
-            self.submap_.insertScan(rawScan, processed.merge_, np.eye(4), timestamp, isPerformCarving=True)
+            self._insertScan(rawScan, processed.merge_, np.eye(4), timestamp)
             self.mapToRangeSensorBuffer_.append((timestamp, self.mapToRangeSensor_.copy()))
             # (the reference leaves lastMeasurementTimestamp_ at the epoch here and lets TransformInterpolationBuffer clamp the lookup of
             # the next frame to the earliest odometry sample; this harness looks stamps up exactly, so it records the first stamp)
@@ -65,23 +80,31 @@ class Mapper:
             odomPrev = self.odometry_.getOdomToRangeSensor(self.lastMeasurementTimestamp_)
             estimate = self.mapToRangeSensorPrev_ @ (np.linalg.inv(odomPrev) @ odomNow)
         processed = self.scan2MapReg_.processForScanMatchingAndMerging(rawScan, self.mapToRangeSensor_)
-        result = self.scan2MapReg_.scanToMapRegistration(processed.match_, self.submap_, self.mapToRangeSensor_, estimate)
+        result = self.scan2MapReg_.scanToMapRegistration(processed.match_, self.getActiveSubmap(), self.mapToRangeSensor_, estimate)
         self.lastResult_ = result
         if not p.isIgnoreMinRefinementFitness_ and result.fitness_ < p.scanMatcher_.minRefinementFitness_:
             self._release(processed)
             return False  # Mapper.cpp:151-156: pose not updated, scan not inserted
         self.mapToRangeSensor_ = np.array(result.transformation_)
         self.mapToRangeSensorBuffer_.append((timestamp, self.mapToRangeSensor_.copy()))
+        if self.submaps_ is not None:
+            self.submaps_.setMapToRangeSensor(self.mapToRangeSensor_)
         motion = np.linalg.inv(self.mapToRangeSensorLastScanInsertion_) @ self.mapToRangeSensor_
         if not (np.linalg.norm(motion[:3, 3]) < p.minMovementBetweenMappingSteps_):  # Mapper.cpp:170-176
             # SubmapCollection::insertScan (SubmapCollection.cpp:178,189,203) always asks the submap to carve; Submap::carve applies the
             # every-N-scans gate itself (Submap.cpp:111)
-            self.submap_.insertScan(rawScan, processed.merge_, self.mapToRangeSensor_, timestamp, isPerformCarving=True)
+            self._insertScan(rawScan, processed.merge_, self.mapToRangeSensor_, timestamp)
             self.mapToRangeSensorLastScanInsertion_ = self.mapToRangeSensor_.copy()
         self.lastMeasurementTimestamp_ = timestamp
         self.mapToRangeSensorPrev_ = self.mapToRangeSensor_.copy()
         self._release(processed)
         return True
+
+    def _insertScan(self, rawScan, preProcessedScan, mapToRangeSensor, timestamp):
+        if self.submaps_ is None:
+            self.submap_.insertScan(rawScan, preProcessedScan, mapToRangeSensor, timestamp, isPerformCarving=True)
+        else:  # (the collection keeps the pre-processed scan in its overlap ring: it retains it)
+            self.submaps_.insertScan(rawScan, preProcessedScan, mapToRangeSensor, timestamp)
 
     @staticmethod
     def _release(processed):

@@ -2,7 +2,8 @@
 constraint builders (src/constraint_builders.cpp:33-90) and the submap update of SubmapCollection::transform
 (src/SubmapCollection.cpp:284-330).  The pose graph lives on the host, as Open3D's PoseGraph does; OptimizationProblem.solve runs
 GlobalOptimization on the device (o3ds_global_optimization).  The reference's quirks are kept and marked where they are odd.
-Candidate selection, Mapper::loopClosureUpdate and the PoseGraph JSON dump are not modelled (DESIGN.md section 7.2)."""
+Candidate selection and the cycle that calls this are submap_collection.py and loop_closure.py; the PoseGraph JSON dump is not
+modelled (DESIGN.md sections 7.2, 7.3)."""
 from __future__ import annotations
 
 import copy

@@ -83,6 +83,15 @@ class MapBuilderParameters:  # Parameters.hpp:94-98
 
 
 @dataclasses.dataclass
+class SubmapParameters:  # Parameters.hpp:100-106
+    radius_: float = 20.0
+    minNumRangeData_: int = 5
+    minSecondsBetweenFeatureComputation_: float = 5.0
+    adjacencyBasedRevisitingMinFitness_: float = 0.4
+    numScansOverlap_: int = 3
+
+
+@dataclasses.dataclass
 class ScanToMapRegistrationParameters:  # Parameters.hpp:145-149
     scanToMapRegType_: ScanToMapRegistrationType = ScanToMapRegistrationType.PointToPlaneIcp
     minRefinementFitness_: float = 0.7
@@ -157,6 +166,8 @@ class MapperParameters:  # Parameters.hpp:158-178 (hot-path subset)
     mapBuilder_: MapBuilderParameters = dataclasses.field(default_factory=MapBuilderParameters)
     denseMapBuilder_: MapBuilderParameters = dataclasses.field(default_factory=MapBuilderParameters)
     isBuildDenseMap_: bool = True
+    submaps_: SubmapParameters = dataclasses.field(default_factory=SubmapParameters)
+    isAttemptLoopClosures_: bool = True  # read by loop_closure.py only (SlamWrapper.cpp:141)
     isUseInitialMap_: bool = False
     isMergeScansIntoMap_: bool = True
     placeRecognition_: PlaceRecognitionParameters = dataclasses.field(default_factory=PlaceRecognitionParameters)

@@ -1,8 +1,8 @@
 """PlaceRecognition (include/open3d_slam/PlaceRecognition.hpp, src/PlaceRecognition.cpp:38-226) over the HIP backend: loop-closure
 constraints between a finished submap and candidate submaps, with every data-parallel step on the device -- FPFH features
 (Submap.computeFeatures), feature correspondences and the RANSAC hypothesis search (o3ds_ransac_feature_matching), the overlap crop
-(o3ds_overlap_indices), the ICP refinement and the information matrix.  Candidate selection (getLoopClosureCandidatesIdxs) needs the
-SubmapCollection and its adjacency matrix, which this package does not model: the caller passes the candidates."""
+(o3ds_overlap_indices), the ICP refinement and the information matrix.  Candidate selection (getLoopClosureCandidatesIdxs) is
+submap_collection.py's, which passes the candidates here."""
 from __future__ import annotations
 
 import dataclasses

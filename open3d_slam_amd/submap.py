@@ -9,6 +9,8 @@ from .croppers import croppingVolumeFactory
 from .parameters import MapperParameters
 from .pointcloud import PointCloud
 
+VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING = 2.5  # magic.hpp:16
+
 
 class Submap:
     def __init__(self, be, id_: int = 0, parentId: int = 0):
@@ -17,6 +19,10 @@ class Submap:
         self.params_ = MapperParameters()
         self.mapCloud_ = PointCloud.from_numpy(be, np.zeros((0, 3)))
         self.mapToRangeSensor_ = np.eye(4)
+        self.mapToSubmap_ = np.eye(4)  # setMapToSubmapOrigin: where the submap was opened (SubmapCollection::createNewSubmap)
+        self.submapCenter_ = np.zeros(3)
+        self.isCenterComputed_ = False
+        self._voxelMap = None  # o3ds_dense_map id of the VoxelMap (Submap.cpp:216-217) that isSwitchingSubmapsConsistant probes; made at feature time
         self.nScansInsertedMap_ = 0
         self.nScansInsertedDenseMap_ = 0
         self.sparseMapCloud_ = None  # computeFeatures: the voxelised map with normals and FPFH features (Submap.cpp:237-242)
@@ -33,6 +39,9 @@ class Submap:
         if self._denseMap is not None:
             self.be.dense_map_free(self._denseMap)
             self._denseMap = None
+        if self._voxelMap is not None:  # voxelMap_ = VoxelMap(2.5 * mapVoxelSize_): a fresh, empty map
+            self.be.dense_map_free(self._voxelMap)
+            self._voxelMap = None
 
     def _dense(self) -> int:
         if self._denseMap is None:
@@ -72,9 +81,14 @@ class Submap:
         return True
 
     def transform(self, T):
-        """Submap::transform (Submap.cpp:94-107): the sparse map (its NN index is rebuilt), the dense map as VoxelizedPointCloud::transform
-        is written, mapToRangeSensor_ = mapToRangeSensor_ * T."""
+        """Submap::transform (Submap.cpp:94-107): the sparse (feature) map, the map (its NN index is rebuilt), the dense map as
+        VoxelizedPointCloud::transform is written, mapToRangeSensor_ = mapToRangeSensor_ * T, the centre = T * centre.  As in the
+        reference, the voxel map of the switch check and mapToSubmap_ stay where they were."""
         T = np.array(T, dtype=np.float64)
+        if self.sparseMapCloud_ is not None and not self.sparseMapCloud_.IsEmpty():
+            moved = PointCloud(self.be, self.be.transform_cloud(self.sparseMapCloud_.id, T))  # (the FPFH features travel along)
+            self.sparseMapCloud_.release()
+            self.sparseMapCloud_ = moved
         if not self.mapCloud_.IsEmpty():
             moved = PointCloud(self.be, self.be.transform_cloud(self.mapCloud_.id, T))
             self.mapCloud_.release()
@@ -83,6 +97,40 @@ class Submap:
         if self._denseMap is not None:
             self.be.dense_map_transform(self._denseMap, T)
         self.mapToRangeSensor_ = self.mapToRangeSensor_ @ T
+        self.submapCenter_ = T[:3, :3] @ self.submapCenter_ + T[:3, 3]
+
+    def setMapToSubmapOrigin(self, T):  # Submap.cpp:206-208
+        self.mapToSubmap_ = np.array(T, dtype=np.float64)
+
+    def getMapToSubmapOrigin(self):
+        return self.mapToSubmap_
+
+    def computeSubmapCenter(self):
+        """Submap.cpp:255-259: the mean of the map's points ([O3D] GetCenter), on the device (o3ds_cloud_center); three numbers come back."""
+        self.submapCenter_ = self.be.cloud_center(self.mapCloud_.id)
+        self.isCenterComputed_ = True
+
+    def getMapToSubmapCenter(self) -> np.ndarray:  # Submap.cpp:180-182
+        return self.submapCenter_ if self.isCenterComputed_ else self.mapToSubmap_[:3, 3]
+
+    def hasVoxelMap(self) -> bool:
+        return self._voxelMap is not None
+
+    def computeVoxelMap(self):
+        """voxelMap_.clear(); voxelMap_.insertCloud(layer, mapCloud_) (Submap.cpp:233-237): the occupied voxels of the map at voxel size
+        2.5 * mapBuilder_.mapVoxelSize_, kept on the device as a dense voxel map (only which voxels are occupied is ever asked)."""
+        if self._voxelMap is not None:
+            self.be.dense_map_free(self._voxelMap)
+        self._voxelMap = self.be.dense_map_create(VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING * self.params_.mapBuilder_.mapVoxelSize_)
+        if not self.mapCloud_.IsEmpty():
+            self.be.dense_map_insert(self._voxelMap, self.mapCloud_.id)
+
+    def countVoxelMapHits(self, scan: PointCloud, mapToRangeSensor) -> int:
+        """isSwitchingSubmapsConsistant's numerator (SubmapCollection.cpp:355-360): points of T * scan inside an occupied voxel of the
+        voxel map; 0 while the voxel map has not been built (the reference's map is empty then)."""
+        if self._voxelMap is None:
+            return 0
+        return self.be.dense_map_count_occupied(self._voxelMap, scan.id, np.array(mapToRangeSensor, dtype=np.float64))
 
     def getMapPointCloud(self) -> PointCloud:
         return self.mapCloud_
@@ -129,7 +177,8 @@ class Submap:
     def computeFeatures(self):
         """Submap::computeFeatures (Submap.cpp:228-248): VoxelDownSample(featureVoxelSize_), EstimateNormals(Hybrid(normalEstimationRadius_,
         normalKnn_)) + NormalizeNormals + OrientNormalsTowardsCameraLocation(0), ComputeFPFHFeature(Hybrid(featureRadius_, featureKnn_)),
-        all on the device; the features stay on the sparse cloud.  (The minimum-seconds throttle and the voxel-map thread are left out.)"""
+        all on the device; the features stay on the sparse cloud; then the voxel map of the switch check (the reference builds it on a
+        thread of its own meanwhile).  (The minimum-seconds throttle is left out.)"""
         p = self.params_.placeRecognition_
         sparse = PointCloud(self.be, self.be.voxel_down_sample(self.mapCloud_.id, p.featureVoxelSize_))
         self.be.estimate_normals(sparse.id, p.normalEstimationRadius_, p.normalKnn_)
@@ -137,6 +186,7 @@ class Submap:
         if self.sparseMapCloud_ is not None:
             self.sparseMapCloud_.release()
         self.sparseMapCloud_ = sparse
+        self.computeVoxelMap()
 
     def getSparseMapPointCloud(self) -> PointCloud:
         if self.sparseMapCloud_ is None:
