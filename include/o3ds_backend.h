@@ -326,6 +326,36 @@ int o3ds_comm_destroy(o3ds_handle h);
 int o3ds_icp_register_sharded(o3ds_handle h, int partitioning, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* target_crop,
                               const double init[16], const o3ds_icp_params* params, o3ds_icp_result* out);
 
+/* ---- one registration against SEVERAL resident targets of one handle (a SubmapCollection's submaps), in one process and without a
+ *      copy: BASELINE.json configs[3] on one GPU.  A capability beyond the reference, which registers against the active submap only
+ *      (Mapper.cpp:141).  All targets are clouds of `h` in one common frame, each in the state o3ds_icp_register_dev accepts a target
+ *      in, WITH its index (o3ds_cloud_build_index, or a persistent-form map) and, for the estimators that need them, its normals.
+ *      `target_crop` is a predicate inside every target's search, as in the one-target call; params->method, the loop, the solve, the
+ *      convergence test and the result fields are that call's.  One launch walks the whole list per query and pass.
+ *   O3DS_MULTI_UNION  the correspondence of a query is its nearest point over the union of the targets' (cropped) points within
+ *                     max_correspondence_distance.  The d2 compared across targets is the d2 the one-target search compares (storage
+ *                     precision, never rounded further); equal d2 go to the LOWER slot of `targets`, inside a slot to the one-target
+ *                     search's choice (the smaller original index).  The result is the registration o3ds_icp_register_dev gives against
+ *                     the cloud obtained by appending the targets in slot order (o3ds_cloud_append) and indexing it.
+ *   O3DS_MULTI_JOINT  every target contributes its own correspondence per query and the normal-equation records are summed over the
+ *                     targets: fitness = correspondences / (n_targets * n_src), the mean over the targets; inlier_rmse over all
+ *                     correspondences.  O3DS_SHARD_SUBMAP in one process.  The sums are exact: K copies of one cloud give the
+ *                     one-target pose bit for bit when K is a power of two.
+ * n_targets == 1 returns the bits of o3ds_icp_register_dev in either form.  An empty target in the list is legal and contributes
+ * nothing (JOINT still counts it in the denominator); a list of empty targets only returns O3DS_ERR_EMPTY as the one-target call does.
+ * O3DS_ERR_INVALID_ARG: n_targets == 0 or > O3DS_MULTI_MAX_TARGETS, a null list, an unknown form, an id that is not a cloud of `h`
+ * (a cloud of another handle), a non-empty target without an index, without the normals the estimator needs or of another precision
+ * than the source.  O3DS_ERR_CAPACITY (nothing is looped): with n_targets > 1 the source may have at most O3DS_ICP_PASS_MAX_QUERIES
+ * points, and in JOINT form n_targets * ceil(n_src / 128) may be at most 4096, the number of workgroup records the exact sums hold per
+ * pass (8 targets x 65 536 points, 16 x 32 768).  Candidate sets are not carried between the passes of this call: every pass searches,
+ * from the previous pass's match as its bound.  A function armed with o3ds_icp_overlap_next is NOT consumed by this call: it stays
+ * armed for the next one-target registration. */
+#define O3DS_MULTI_MAX_TARGETS 16 /* as the sharded forms: W <= 16 */
+#define O3DS_MULTI_UNION 0
+#define O3DS_MULTI_JOINT 1
+int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3ds_cloud* targets, size_t n_targets,
+                            const o3ds_crop* target_crop, const double init[16], const o3ds_icp_params* params, o3ds_icp_result* out);
+
 /* ---- scan pre-processing: ScanToMapIcp::preprocess (ScanToMapRegistration.cpp:35-40),
  *      LidarOdometry::preprocess (Odometry.cpp:25-30) ------------------------------------------ */
 /* CroppingVolume::crop (croppers.cpp:76-106): stable compaction of points (+normals) inside the volume. */

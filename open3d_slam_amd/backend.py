@@ -168,6 +168,8 @@ SIGNATURES = {
     "o3ds_comm_attach": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int]),
     "o3ds_comm_destroy": (C.c_int, [_H]),
     "o3ds_icp_register_sharded": (C.c_int, [_H, C.c_int, _CL, _CL, C.POINTER(Crop), _dp, C.POINTER(IcpParams), C.POINTER(IcpResult)]),
+    "o3ds_icp_register_multi": (C.c_int, [_H, C.c_int, _CL, C.POINTER(_CL), C.c_size_t, C.POINTER(Crop), _dp, C.POINTER(IcpParams),
+                                          C.POINTER(IcpResult)]),
     "o3ds_crop_cloud": (C.c_int, [_H, _CL, C.POINTER(Crop), C.POINTER(_CL)]),
     "o3ds_voxel_down_sample": (C.c_int, [_H, _CL, C.c_double, C.POINTER(_CL)]),
     "o3ds_crop_voxel_down_sample": (C.c_int, [_H, _CL, C.POINTER(Crop), C.c_double, C.POINTER(_CL)]),
@@ -605,6 +607,23 @@ class Backend:
         out = IcpResult()
         self._ck(self.lib.o3ds_icp_register_sharded(self.h, int(partitioning), source, target, C.byref(target_crop) if target_crop else None, ip,
                                                     C.byref(p), C.byref(out)))
+        return self._result(out)
+
+    # -- one registration against several resident targets of this handle (o3ds_backend.h, o3ds_icp_register_multi)
+    MULTI_UNION, MULTI_JOINT, MULTI_MAX_TARGETS = 0, 1, 16
+
+    def icp_register_multi(self, source: int, targets, form: int = 0, crop: Crop | None = None, init=None, params: IcpParams | None = None):
+        """o3ds_icp_register_multi: `targets` is a sequence of cloud ids of this handle (slot order), `form` MULTI_UNION (nearest point
+        over the union of the targets; ties to the lower slot) or MULTI_JOINT (every target contributes its own correspondence).
+        `params`: an IcpParams (Backend._params builds one); `crop` applies to every target."""
+        if params is None:
+            raise ValueError("icp_register_multi: params (IcpParams) is required")
+        ids = [int(t) for t in targets]
+        arr = (_CL * max(len(ids), 1))(*ids)
+        T0, ip = (None, _IDENTITY16) if init is None else _d(colmajor(init))
+        out = IcpResult()
+        self._ck(self.lib.o3ds_icp_register_multi(self.h, int(form), source, arr, len(ids), C.byref(crop) if crop else None, ip, C.byref(params),
+                                                  C.byref(out)))
         return self._result(out)
 
     def set_gicp_epsilon(self, eps: float):

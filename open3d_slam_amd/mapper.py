@@ -14,13 +14,17 @@ from .submap import Submap
 
 
 class Mapper:
-    def __init__(self, be, odometry: LidarOdometry | None = None, submaps=None):
-        """submaps: a SubmapCollection to map into (Mapper.cpp:30-33); None: one submap of this mapper's own."""
+    def __init__(self, be, odometry: LidarOdometry | None = None, submaps=None, numSubmapsForScanMatching: int = 1):
+        """submaps: a SubmapCollection to map into (Mapper.cpp:30-33); None: one submap of this mapper's own.
+        numSubmapsForScanMatching: with a collection, how many resident submaps a scan is registered against (the active one and its
+        nearest adjacent ones, SubmapCollection.getSubmapsForScanMatching) -- beyond the reference, which uses the active submap only
+        (Mapper.cpp:141); 1, the default, is the reference's behaviour and calls exactly what it always called."""
         self.be = be
         self.odometry_ = odometry
         self.params_ = MapperParameters()
         self.submaps_ = submaps
         self.submap_ = Submap(be) if submaps is None else None
+        self.numSubmapsForScanMatching_ = int(numSubmapsForScanMatching)
         self.mapToRangeSensor_ = np.eye(4)
         self.mapToRangeSensorPrev_ = np.eye(4)
         self.mapToRangeSensorLastScanInsertion_ = np.eye(4)
@@ -80,7 +84,11 @@ class Mapper:
             odomPrev = self.odometry_.getOdomToRangeSensor(self.lastMeasurementTimestamp_)
             estimate = self.mapToRangeSensorPrev_ @ (np.linalg.inv(odomPrev) @ odomNow)
         processed = self.scan2MapReg_.processForScanMatchingAndMerging(rawScan, self.mapToRangeSensor_)
-        result = self.scan2MapReg_.scanToMapRegistration(processed.match_, self.getActiveSubmap(), self.mapToRangeSensor_, estimate)
+        if self.submaps_ is not None and self.numSubmapsForScanMatching_ > 1:
+            targets = self.submaps_.getSubmapsForScanMatching(self.numSubmapsForScanMatching_)
+            result = self.scan2MapReg_.scanToMultiMapRegistration(processed.match_, targets, self.mapToRangeSensor_, estimate)
+        else:
+            result = self.scan2MapReg_.scanToMapRegistration(processed.match_, self.getActiveSubmap(), self.mapToRangeSensor_, estimate)
         self.lastResult_ = result
         if not p.isIgnoreMinRefinementFitness_ and result.fitness_ < p.scanMatcher_.minRefinementFitness_:
             self._release(processed)

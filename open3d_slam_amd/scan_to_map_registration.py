@@ -5,7 +5,8 @@ import dataclasses
 
 import numpy as np
 
-from .cloud_registration import RegistrationResult, cloudRegistrationFactory
+from . import backend as _b
+from .cloud_registration import (RegistrationIcpGeneralized, RegistrationIcpPointToPoint, RegistrationResult, cloudRegistrationFactory)
 from .croppers import croppingVolumeFactory
 from .parameters import (CloudRegistrationParameters, CloudRegistrationType, MapperParameters, ScanToMapRegistrationParameters,
                          ScanToMapRegistrationType)
@@ -100,6 +101,37 @@ class ScanToMapIcp(ScanToMapRegistration):  # ScanToMapRegistration.hpp:40-59
             raise RuntimeError("map patch size is zero")
         r = self.cloudRegistration.registerClouds(scan, mapCloud, initialGuess, target_crop=self.scanMatcherCropper_.to_abi())
         return r
+
+    def scanToMultiMapRegistration(self, scan: PointCloud, submaps, mapToRangeSensorPrev, mapToRangeSensorEstimate) -> RegistrationResult:
+        """The body of scanToMapRegistration (ScanToMapRegistration.cpp:55-62: the scan-matcher volume at the PREVIOUS pose, the estimate
+        as the initial guess) against a LIST of submaps, the active one first: one o3ds_icp_register_multi call in UNION form -- every
+        scan point is matched to its nearest map point over all listed maps inside the volume.  Beyond the reference, which registers
+        against the active submap only (Mapper.cpp:141); with one submap in the list the call is scanToMapRegistration's, bit for bit."""
+        maps = [s.getMapPointCloud() for s in submaps]
+        self.scanMatcherCropper_.setPose(mapToRangeSensorPrev)
+        if not maps or maps[0].IsEmpty():
+            raise RuntimeError("map patch size is zero")
+        reg = self.cloudRegistration
+        method = (_b.ICP_GENERALIZED if isinstance(reg, RegistrationIcpGeneralized)
+                  else _b.ICP_POINT_TO_POINT if isinstance(reg, RegistrationIcpPointToPoint) else _b.ICP_POINT_TO_PLANE)
+        c = reg.icpConvergenceCriteria_
+        params = _b.Backend._params(reg.maxCorrespondenceDistance_, c.max_iteration_, c.relative_fitness_, c.relative_rmse_, method)
+        ids, crop = [m.id for m in maps], self.scanMatcherCropper_.to_abi()
+        try:
+            try:
+                r = scan.be.icp_register_multi(scan.id, ids, form=_b.Backend.MULTI_UNION, crop=crop, init=mapToRangeSensorEstimate, params=params)
+            except _b.BackendError as e:
+                if e.code != _b.ERR_INVALID_ARG or "has no index" not in str(e):
+                    raise
+                # a finished submap's map was folded into its array form when its centre was taken and lost its index: the call wants
+                # every target indexed (it builds nothing), so the finished ones are indexed here, once per fold, and the call repeated
+                for m in maps[1:]:
+                    if not m.IsEmpty():
+                        scan.be.build_index(m.id, reg.maxCorrespondenceDistance_)
+                r = scan.be.icp_register_multi(scan.id, ids, form=_b.Backend.MULTI_UNION, crop=crop, init=mapToRangeSensorEstimate, params=params)
+        except _b.BackendError as e:
+            raise RuntimeError(str(e)) from e
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
 
     def isMergeScanValid(self, cloud: PointCloud) -> bool:  # ScanToMapRegistration.cpp:64-80
         t = self.params_.scanMatcher_.scanToMapRegType_

@@ -128,6 +128,24 @@ class SubmapCollection:
     def getActiveSubmap(self) -> Submap:
         return self.submaps_[self.activeSubmapIdx_]
 
+    def getSubmapsForScanMatching(self, k: int) -> list:
+        """The submaps one scan is registered against when the mapper is asked for more than the active one (a capability beyond the
+        reference, which registers against the active submap only, Mapper.cpp:141): the active submap first, then up to k - 1 others
+        among the non-empty submaps adjacent to it in the AdjacencyMatrix, the one whose centre is nearest to the sensor position
+        (mapToRangeSensor_, what findClosestSubmap measures from) first; equally near: the lower id.  k <= 1: the active submap alone."""
+        active = self.getActiveSubmap()
+        out = [active]
+        if k <= 1:
+            return out
+        p0 = np.asarray(self.mapToRangeSensor_, dtype=np.float64)[:3, 3]
+        others = []
+        for i, s in enumerate(self.submaps_):
+            if i == self.activeSubmapIdx_ or s.isEmpty() or not self.adjacencyMatrix_.isAdjacent(s.id_, active.id_):
+                continue
+            others.append((float(np.linalg.norm(p0 - s.getMapToSubmapCenter())), s.id_, i))
+        others.sort()
+        return out + [self.submaps_[i] for _, _, i in others[:k - 1]]
+
     def getParameters(self) -> MapperParameters:
         return self.params_
 
