@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void pg_panel_kernel(double* __restrict__ L, s
     const int r = e / kPgNB, c = e % kPgNB;
     if (c <= r) base[(size_t)r * M + c] = A[r * kPgLds + c];
   }
-  if (t == 0 && bad) rec->err = bad;
+  if (t == 0 && bad && !rec->err) rec->err = bad;  // the first one: once a pivot has been replaced, later blocks fail in its wake
 }
 
 // L_ik = A_ik L_kk^-T for the row blocks i > k: one workgroup per row block, one thread per row

@@ -185,7 +185,7 @@ def optimize_pose_graph(nodes, edges, criteria: Criteria, option: Option, solve=
     H, b = compute_linear_system(nodes, edges, zeta)
     current_lambda = 1e-5 * (H.diagonal().max() if len(H) else 0.0)
     ni, rho = 2.0, 0.0
-    out = dict(line_process_weight=lpw, iterations=0, lm_steps=0, stop_reason=STOP_NONE, residual=current_residual, trace=[])
+    out = dict(line_process_weight=lpw, iterations=0, lm_steps=0, stop_reason=STOP_NONE, residual=current_residual, trace=[], norms=[])
     if len(b) and b.max() < crit.min_right_term:  # CheckRightTerm
         out["stop_reason"] = STOP_RIGHT_TERM
         return out
@@ -201,6 +201,7 @@ def optimize_pose_graph(nodes, edges, criteria: Criteria, option: Option, solve=
         while True:
             delta = solve(H + current_lambda * np.eye(len(H)), b)
             out["lm_steps"] += 1
+            out["norms"].append((np.linalg.norm(delta), np.linalg.norm(x)))  # what stop check 2 compares
             set_stop(np.linalg.norm(delta) < crit.min_relative_increment * (np.linalg.norm(x) + crit.min_relative_increment), STOP_REL_INCREMENT)
             if not stop:
                 nodes_new = update_pose_graph(nodes, delta)
@@ -235,6 +236,81 @@ def optimize_pose_graph(nodes, edges, criteria: Criteria, option: Option, solve=
         it += 1
     out.update(iterations=it, stop_reason=reason, residual=current_residual)
     return out
+
+
+def first_system(nodes, edges, option: Option):
+    """H, b and lambda of a pass's first LM step (the head of optimize_pose_graph); the confidences of `edges` are left as given"""
+    nodes = [np.array(T, dtype=np.float64) for T in nodes]
+    edges = [dataclasses.replace(e) for e in edges]
+    lpw = compute_line_process_weight(edges, option)
+    zeta = compute_zeta(nodes, edges)
+    update_confidence(edges, zeta, lpw, option)
+    H, b = compute_linear_system(nodes, edges, zeta)
+    return H, b, 1e-5 * H.diagonal().max()
+
+
+# ---- solvers for the solve= hook ------------------------------------------------------------------------------------------------------
+class NotPositiveDefinite(np.linalg.LinAlgError):
+    def __init__(self, row):
+        super().__init__(f"pivot of row {row} is not positive")
+        self.row = row
+
+
+def cholesky_lower(A) -> np.ndarray:
+    """plain LL^T, column by column; the first pivot that is not positive and finite raises NotPositiveDefinite(row)"""
+    A = np.asarray(A, dtype=np.float64)
+    m = len(A)
+    L = np.zeros((m, m))
+    for j in range(m):
+        d = A[j, j] - L[j, :j] @ L[j, :j]
+        if not d > 0.0 or not np.isfinite(d):
+            raise NotPositiveDefinite(j)
+        L[j, j] = np.sqrt(d)
+        L[j + 1:, j] = (A[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def solve_cholesky(A, b) -> np.ndarray:
+    """(L L^T) x = b by forward and back substitution: the device's method in serial order"""
+    L = cholesky_lower(A)
+    m = len(L)
+    y = np.zeros(m)
+    for j in range(m):
+        y[j] = (b[j] - L[j, :j] @ y[:j]) / L[j, j]
+    x = np.zeros(m)
+    for j in range(m - 1, -1, -1):
+        x[j] = (y[j] - L[j + 1:, j] @ x[j + 1:]) / L[j, j]
+    return x
+
+
+try:  # the residual of the refinement in 40 digits where mpmath is there and the system small enough for it; nothing depends on it
+    import mpmath as _mp
+except ImportError:
+    _mp = None
+MPMATH_MAX_ROWS = 130
+
+
+def _residual(A, b, x) -> np.ndarray:
+    """b - A x for a longdouble x, rounded to f64 once at the end"""
+    if _mp is not None and len(b) <= MPMATH_MAX_ROWS:
+        with _mp.workprec(140):
+            xs = [_mp.mpf(float(v)) + _mp.mpf(float(v - np.longdouble(float(v)))) for v in x]
+            return np.array([float(_mp.mpf(float(b[i])) - _mp.fdot(zip((float(a) for a in A[i]), xs))) for i in range(len(b))])
+    return (b.astype(np.longdouble) - A.astype(np.longdouble) @ x).astype(np.float64)
+
+
+def solve_refined(A, b, rounds=3) -> np.ndarray:
+    """an f64 LU solve, then iterative refinement: the residual in extended precision (np.longdouble, 64 mantissa bits on x86; mpmath for
+    small systems when it imports), the correction by the f64 solve, the sum kept in longdouble.  Accurate to f64 rounding of the true
+    solution while cond(A) 2^-53 is well below 1."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if not len(b):
+        return np.zeros(0)
+    x = np.linalg.solve(A, b).astype(np.longdouble)
+    for _ in range(rounds):
+        x = x + np.linalg.solve(A, _residual(A, b, x)).astype(np.longdouble)
+    return x.astype(np.float64)
 
 
 def _connected(n_nodes, edges) -> bool:  # ValidatePoseGraphConnectivity(pose_graph, false)
@@ -274,6 +350,7 @@ def global_optimization(nodes, edges, criteria: Criteria | None = None, option: 
         return res
     orig = [T.copy() for T in nodes]
     res["passes"].append(optimize_pose_graph(nodes, edges, criteria, option, solve))
+    res["poses_pass1"] = np.array(nodes)
     conf = np.array([e.confidence for e in edges])
     kept = np.array([(not e.uncertain) or e.confidence > option.edge_prune_threshold for e in edges], bool)
     pruned = [e for e, k in zip(edges, kept) if k]
@@ -339,3 +416,119 @@ def drift(poses, G) -> float:
     """mean translation error against ground truth after aligning node 0"""
     A = G[0] @ np.linalg.inv(poses[0])
     return float(np.mean([np.linalg.norm((A @ T)[:3, 3] - g[:3, 3]) for T, g in zip(poses, G)]))
+
+
+# ---- scenarios for the branches the figure-eight never takes (tests/test_pose_graph_edges_*.py) ------------------------------------------
+def scrambled_graph(n_nodes=30, seed=11, certain=False):
+    """The figure-eight with every start pose left-multiplied by V6toM4(N(0, [1, 1, 1, 5, 5, 5])): far enough from the solution that LM
+    rejects steps (rho <= 0), several in a row.  certain=True makes every edge certain, the gross outlier included."""
+    G, T0, E = figure_eight_graph(n_nodes=n_nodes)
+    rng = np.random.default_rng(seed)
+    T0 = np.array([vector6_to_matrix4(rng.normal(size=6) * [1.0, 1.0, 1.0, 5.0, 5.0, 5.0]) @ T for T in T0])
+    if certain:
+        E = [dataclasses.replace(e, uncertain=False) for e in E]
+    return G, T0, E
+
+
+def _noisy_edge(rng, G, s, t, noise, uncertain, n_points):
+    X = np.linalg.inv(G[t]) @ G[s] @ vector6_to_matrix4(rng.normal(size=6) * noise)
+    return Edge(int(s), int(t), X, information_from_points(rng.uniform(-8, 8, (n_points, 3))), bool(uncertain))
+
+
+def hub_graph(n, extra=None, seed=5, bundle=0, noise=0.01, n_points=60):
+    """Node 0 tied to every node, the edge direction alternating (every third one uncertain), plus `extra` (default 3 n) random edges,
+    half of them uncertain: H's first block column is dense, so the Cholesky factor fills in completely.  `bundle` further edges all lie
+    on the pair (1, 2), in alternating directions: one block list of that length.  Returns (ground truth, start poses, edges)."""
+    rng = np.random.default_rng(seed)
+    extra = 3 * n if extra is None else extra
+    G = [vector6_to_matrix4(rng.normal(size=6) * [0.3, 0.3, 1.0, 4.0, 4.0, 1.0]) for _ in range(n)]
+    E = []
+    for i in range(1, n):
+        s, t = (0, i) if i % 2 else (i, 0)
+        E.append(_noisy_edge(rng, G, s, t, noise, i % 3 == 0, n_points))
+    for _ in range(extra):
+        s, t = rng.integers(0, n, 2)
+        if s == t:
+            t = (s + 1) % n
+        E.append(_noisy_edge(rng, G, s, t, noise, rng.random() < 0.5, n_points))
+    for k in range(bundle):
+        E.append(_noisy_edge(rng, G, 1 + k % 2, 2 - k % 2, noise, k % 3 == 0, n_points))
+    T0 = np.array([T @ vector6_to_matrix4(rng.normal(size=6) * 2.0 * noise) for T in G])
+    return np.array(G), T0, E
+
+
+def _walk(rng, n):
+    G = [np.eye(4)]
+    for _ in range(n - 1):
+        G.append(G[-1] @ vector6_to_matrix4(rng.normal(size=6) * [0.02, 0.02, 0.2, 2.0, 0.5, 0.1]))
+    return G
+
+
+def multi_edge_graph(n=8, seed=2):
+    """A noisy odometry chain with a loop closure, three parallel edges on the pair (2, 5) -- 2 -> 5 certain, 5 -> 2 uncertain, 2 -> 5
+    uncertain -- and one uncertain self-edge 3 -> 3: block lists of length >= 3 with both signs, and source == target."""
+    rng = np.random.default_rng(seed)
+    G = _walk(rng, n)
+    E = [_noisy_edge(rng, G, i, i + 1, 0.01, False, 400) for i in range(n - 1)]
+    E.append(_noisy_edge(rng, G, n - 1, 0, 0.0, True, 400))
+    E.append(_noisy_edge(rng, G, 2, 5, 0.01, False, 400))
+    E.append(_noisy_edge(rng, G, 5, 2, 0.01, True, 400))
+    E.append(_noisy_edge(rng, G, 2, 5, 0.01, True, 400))
+    E.append(_noisy_edge(rng, G, 3, 3, 0.01, True, 400))
+    return np.array(G), np.array(G), E
+
+
+def gimbal_graph(n=10, seed=4):
+    """Nodes 1 and n - 2 stand at pitch +pi/2 and -pi/2 exactly (R00 = R10 = 0: TransformMatrix4dToVector6d's else branch), the others
+    are yaw-only with yaws of a radian and more, and every translation is small: |x| is made of the angles, so which branch computed
+    them decides stop check 2 (pose_graph_edge_cases.GIMBAL_INCREMENTS holds the min_relative_increment values that tell the branches apart)."""
+    rng = np.random.default_rng(seed)
+    G = []
+    for i in range(n):
+        T = rz(1.0 + 2.0 * rng.random())
+        T[:3, 3] = rng.normal(size=3) * 0.05
+        G.append(T)
+    for i, sgn in ((1, 1.0), (n - 2, -1.0)):
+        a = 0.3 + rng.random()
+        ca, sa = np.cos(a), np.sin(a)
+        G[i][:3, :3] = [[0.0, sgn * sa, sgn * ca], [0.0, ca, -sa], [-sgn, 0.0, 0.0]]  # Ry(sgn pi/2) Rx(a), its zeros exact
+    E = [_noisy_edge(rng, G, i, i + 1, 0.01, False, 400) for i in range(n - 1)]
+    E.append(_noisy_edge(rng, G, n - 1, 0, 0.0, True, 400))
+    E.append(_noisy_edge(rng, G, n // 2, 1, 0.0, True, 400))
+    return np.array(G), np.array(G), E
+
+
+def all_outliers_graph(n=6, seed=6):
+    """Every pair of nodes joined by an uncertain edge with a random transform kilometres and radians from the poses: every confidence
+    is ~1e-11 and the residual sits at its saturation value, so the first accepted step gains less than the relative-residual bound, the
+    pass ends there and pass 2 has no edges at all."""
+    rng = np.random.default_rng(seed)
+    G = _walk(rng, n)
+    E = []
+    for s in range(n):
+        for t in range(s):
+            X = vector6_to_matrix4(rng.normal(size=6) * [1.0, 1.0, 1.0, 2000.0, 2000.0, 2000.0])
+            E.append(Edge(s, t, X, information_from_points(rng.uniform(-8, 8, (400, 3))), True))
+    return np.array(G), np.array(G), E
+
+
+def leaf_cut_graph(n=8, seed=7):
+    """multi_edge_graph's chain and loop closure on nodes 0 .. n - 2; node n - 1 is a leaf held by one uncertain edge that is a kilometre
+    off: its confidence is ~1e-12, it is pruned, and in pass 2 the leaf has no edge (its pivots are lambda alone, its delta 0)."""
+    rng = np.random.default_rng(seed)
+    G = _walk(rng, n)
+    E = [_noisy_edge(rng, G, i, i + 1, 0.01, False, 400) for i in range(n - 2)]
+    E.append(_noisy_edge(rng, G, n - 2, 0, 0.0, True, 400))
+    leaf = _noisy_edge(rng, G, n - 1, n // 2, 0.0, True, 400)
+    leaf.transformation[:3, 3] += [1000.0, -300.0, 50.0]
+    E.append(leaf)
+    return np.array(G), np.array(G), E
+
+
+def all_uncertain(edges):
+    return [dataclasses.replace(e, uncertain=True) for e in edges]
+
+
+def recovered_delta(new, old) -> np.ndarray:
+    """the step of one UpdatePoseGraph read back from the poses: delta_i = TransformMatrix4dToVector6d(new_i old_i^-1)"""
+    return np.concatenate([matrix4_to_vector6(a @ np.linalg.inv(b)) for a, b in zip(new, old)])
