@@ -1299,10 +1299,13 @@ inline QuantumTable quantum_table(const IcpPassArgs& a) {
 #endif
 constexpr int kIcpBlock = O3DS_ICP_BLOCK, kIcpQ = kIcpBlock / 4;
 
-template <typename P4>
-void launch_accumulate(o3ds_handle h, const IcpPassArgs& a, bool crop, int nblocks) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->profiling == 1) {
+// profiling (o3ds_profile_enable(1)): one pass launch between two events of h->ev, taken from the handle or created on first use (a
+// failed creation is skipped silently: that launch goes unmeasured)
+struct LaunchBracket {
+  o3ds_handle h;
+  hipEvent_t e1 = nullptr;
+  LaunchBracket(o3ds_handle h_, bool on) : h(h_) {
+    if (h->profiling != 1 || !on) return;
     if (h->ev_used + 2 > h->ev.size()) {
       hipEvent_t a0, a1;
       if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) {
@@ -1311,12 +1314,23 @@ void launch_accumulate(o3ds_handle h, const IcpPassArgs& a, bool crop, int nbloc
       }
     }
     if (h->ev_used + 2 <= h->ev.size()) {
-      e0 = h->ev[h->ev_used];
+      const hipEvent_t e0 = h->ev[h->ev_used];
       e1 = h->ev[h->ev_used + 1];
       h->ev_used += 2;
       (void)hipEventRecord(e0, h->stream);
     }
   }
+  ~LaunchBracket() {
+    if (e1) (void)hipEventRecord(e1, h->stream);
+  }
+};
+
+#define DISPATCH(prec, fn, ...) ((prec) == O3DS_PRECISION_F64 ? fn<P4d>(__VA_ARGS__) : fn<P4f>(__VA_ARGS__))
+
+// the launchers pick the instantiation from the session: storage precision (launch_*), target crop, estimator
+template <typename P4>
+void launch_accumulate_t(o3ds_handle h, const IcpPassArgs& a, int nblocks) {
+  const bool crop = h->session_crop;
   // one geometry: kIcpBlock threads = kIcpBlock / 4 queries x 4 lanes (G = 2 / 8 were swept and dropped; 512 threads against 256: a launch costs 2.7 ns per
   // workgroup beyond the first 256 -- scripts/ubench/launch_shape.hip -- and a steady pass is 9.7 us instead of 10.2)
   if (a.keys_mode != 0) {  // target-sharded registration (o3ds_icp_nn_keys / o3ds_icp_accumulate_keys): the instantiation with the key code
@@ -1342,9 +1356,12 @@ void launch_accumulate(o3ds_handle h, const IcpPassArgs& a, bool crop, int nbloc
     else
       icp_accumulate_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
   }
-  if (e1) (void)hipEventRecord(e1, h->stream);
 }
 
+void launch_accumulate(o3ds_handle h, const IcpPassArgs& a, int nblocks) {
+  LaunchBracket scope(h, true);
+  DISPATCH(h->session_precision, launch_accumulate_t, h, a, nblocks);
+}
 
 // fused form: byte offsets inside d_fused
 constexpr size_t kFusedStateStride = 256;
@@ -1354,23 +1371,8 @@ constexpr size_t kFusedBytes = kFusedSlotsOff + 3 * kFusedSlotBufBytes;
 static_assert(sizeof(IcpStateDev) <= kFusedStateStride, "state slot too small");
 
 template <typename P4>
-void launch_fused(o3ds_handle h, const IcpFusedArgs& fa, bool crop, int nblocks, bool bracket) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->profiling == 1 && bracket) {
-    if (h->ev_used + 2 > h->ev.size()) {
-      hipEvent_t a0, a1;
-      if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) {
-        h->ev.push_back(a0);
-        h->ev.push_back(a1);
-      }
-    }
-    if (h->ev_used + 2 <= h->ev.size()) {
-      e0 = h->ev[h->ev_used];
-      e1 = h->ev[h->ev_used + 1];
-      h->ev_used += 2;
-      (void)hipEventRecord(e0, h->stream);
-    }
-  }
+void launch_fused_t(o3ds_handle h, const IcpFusedArgs& fa, int nblocks) {
+  const bool crop = h->session_crop;
   if (h->session_method == O3DS_ICP_GENERALIZED) {
     if (crop)
       icp_fused_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
@@ -1382,7 +1384,11 @@ void launch_fused(o3ds_handle h, const IcpFusedArgs& fa, bool crop, int nblocks,
     else
       icp_fused_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
   }
-  if (e1) (void)hipEventRecord(e1, h->stream);
+}
+
+void launch_fused(o3ds_handle h, const IcpFusedArgs& fa, int nblocks, bool bracket) {  // (a tail-only launch is not a pass: no bracket)
+  LaunchBracket scope(h, bracket);
+  DISPATCH(h->session_precision, launch_fused_t, h, fa, nblocks);
 }
 
 // the fused kernel serves ONE batch of kIcpQ queries per workgroup (no batch loop: icp_pass_body, kSingle); its records go to slot
@@ -1415,6 +1421,63 @@ int validate_icp(o3ds_handle h, const CloudRec* src, const CloudRec* tgt, const 
   if (src->precision != tgt->precision) return fail(h, O3DS_ERR_INVALID_ARG, "icp: source/target precision mismatch");
   if (p->max_iteration < 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp: negative max_iteration");
   return O3DS_OK;
+}
+
+// per-term bounds on the sums of |record terms| -> per-term quanta of the exact record sums (split_exact): 2^53 q >= 8 B_k.  g: the
+// target's grid (its box holds the matched points), r: the correspondence distance, n_src: the source's size as the host knows it
+void record_quanta(const GridDev& g, double r, int method, double gicp_epsilon, size_t n_src, double q_hi[kRec]) {
+  const double ex = std::max(std::fabs(g.ox), std::fabs(g.ox + g.nx * g.cell)), ey = std::max(std::fabs(g.oy), std::fabs(g.oy + g.ny * g.cell)),
+               ez = std::max(std::fabs(g.oz), std::fabs(g.oz + g.nz * g.cell));
+  const double P = std::max(1.0, std::sqrt(ex * ex + ey * ey + ez * ez) + r);  // a matched source point lies within r of the target's box
+  const double rr = std::max(r, 1e-3);
+  // headroom: 64 ranks of a sharded run may add up ("submap" mode: every rank contributes up to n correspondences).  The number of
+  // queries enters as a CONSTANT (2^24, or the next power of two above a larger scan), not as n_src: for the head of a lazy chain
+  // that is the exact count or the chain's upper bound, whichever the host happens to know when the registration starts, and a
+  // quantum that follows it makes the dropped bits -- below 2^-85 of a term's bound, but the whole last place of J^T r once that sum
+  // has converged to nothing -- a matter of timing: two-handle runs of the stream differed from one-handle runs by an ulp of a pose entry
+  // in every third run (round 6, scripts/debug_wobble.py), the two-kernel form, which waits for the count, never did.  (The other half
+  // of the same story is in the kernels: the queries are dealt out over the exact number the DEVICE holds, icp_kernels.hpp deal_count.)
+  size_t n_for_quantum = (size_t)1 << 24;
+  while (n_for_quantum < n_src) n_for_quantum <<= 1;
+  const double nn = 64.0 * (double)n_for_quantum;
+  double bound[kRec];
+  if (method == O3DS_ICP_GENERALIZED) {
+    const double gw = 4.0 * std::max(1.0, 0.5 / gicp_epsilon);  // |M^-1| <= 1 / (2 eps)
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j) bound[k++] = gw * (i < 3 ? P : 1.0) * (j < 3 ? P : 1.0);  // A^T M^-1 A, A = [-[p]x | I]
+    for (int i = 0; i < 6; ++i) bound[21 + i] = gw * (i < 3 ? P : 1.0) * rr;                 // A^T M^-1 d
+    bound[27] = gw * rr * rr;
+    bound[28] = 1.0;
+    bound[29] = rr * rr;
+    bound[30] = bound[31] = 1.0;
+  } else {
+    // the record terms are products of two per-query slots; slot magnitudes per method (icp_kernels.hpp, kTermA/B tables)
+    double slot[10];
+    const unsigned char *ta, *tb;
+    static const unsigned char A0[kRec] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9};
+    static const unsigned char B0[kRec] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 3, 4, 5, 4, 5, 5, 6, 6, 6, 6, 6, 6, 6, 7, 7, 9, 9};
+    static const unsigned char A1[kRec] = {3, 3, 3, 4, 4, 4, 5, 5, 5, 0, 1, 2, 3, 4, 5, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 8, 9, 9};
+    static const unsigned char B1[kRec] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 7, 7, 7, 7, 7, 7, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 7, 9, 9};
+    if (method == O3DS_ICP_POINT_TO_POINT) {  // also the information-matrix pass (same slots, q q^T terms bounded by p q^T's)
+      for (int i = 0; i < 6; ++i) slot[i] = P;  // p, q
+      slot[6] = 0.0, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
+      ta = A1, tb = B1;
+    } else {
+      for (int i = 0; i < 3; ++i) slot[i] = P, slot[3 + i] = 1.0;  // J = [p x n ; n], unit normals
+      slot[6] = rr, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
+      ta = A0, tb = B0;
+    }
+    for (int k = 0; k < kRec; ++k) bound[k] = std::max(slot[ta[k]] * slot[tb[k]], 1e-30);
+    if (method == O3DS_ICP_POINT_TO_POINT)
+      for (int k = 0; k < 9; ++k) bound[k] = P * P;  // information matrix: terms 0..8 are q_a q_b or q_a (<= P^2 either way)
+  }
+  const bool no_split = ab_getenv("O3DS_SUM_NO_SPLIT") != nullptr;  // diagnostic: plain f64 sums
+  for (int k = 0; k < kRec; ++k) {
+    int e = 0;
+    (void)std::frexp(nn * bound[k], &e);                    // n * bound < 2^e
+    q_hi[k] = no_split ? 0.0 : std::ldexp(1.0, e + 3 - 53);  // 2^53 q = 8 * 2^e
+  }
 }
 
 int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* crop, const double init[16],
@@ -1478,61 +1541,7 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   const double r = params->max_correspondence_distance;
   a.r2max = r * r;
   a.method = params->method;
-  {  // per-term bounds on the sums of |record terms| -> per-term quanta of the exact record sums (split_exact): 2^53 q >= 8 B_k
-    const GridDev& g = tgt->grid;
-    const double ex = std::max(std::fabs(g.ox), std::fabs(g.ox + g.nx * g.cell)), ey = std::max(std::fabs(g.oy), std::fabs(g.oy + g.ny * g.cell)),
-                 ez = std::max(std::fabs(g.oz), std::fabs(g.oz + g.nz * g.cell));
-    const double P = std::max(1.0, std::sqrt(ex * ex + ey * ey + ez * ez) + r);  // a matched source point lies within r of the target's box
-    const double rr = std::max(r, 1e-3);
-    // headroom: 64 ranks of a sharded run may add up ("submap" mode: every rank contributes up to n correspondences).  The number of
-    // queries enters as a CONSTANT (2^24, or the next power of two above a larger scan), not as src->n: for the head of a lazy chain
-    // that is the exact count or the chain's upper bound, whichever the host happens to know when the registration starts, and a
-    // quantum that follows it makes the dropped bits -- below 2^-85 of a term's bound, but the whole last place of J^T r once that sum
-    // has converged to nothing -- a matter of timing: two-handle runs of the stream differed from one-handle runs by an ulp of a pose entry
-    // in every third run (round 6, scripts/debug_wobble.py), the two-kernel form, which waits for the count, never did.  (The other half
-    // of the same story is in the kernels: the queries are dealt out over the exact number the DEVICE holds, icp_kernels.hpp deal_count.)
-    size_t n_for_quantum = (size_t)1 << 24;
-    while (n_for_quantum < src->n) n_for_quantum <<= 1;
-    const double nn = 64.0 * (double)n_for_quantum;
-    double bound[kRec];
-    if (params->method == O3DS_ICP_GENERALIZED) {
-      const double gw = 4.0 * std::max(1.0, 0.5 / h->gicp_epsilon);  // |M^-1| <= 1 / (2 eps)
-      int k = 0;
-      for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) bound[k++] = gw * (i < 3 ? P : 1.0) * (j < 3 ? P : 1.0);  // A^T M^-1 A, A = [-[p]x | I]
-      for (int i = 0; i < 6; ++i) bound[21 + i] = gw * (i < 3 ? P : 1.0) * rr;                 // A^T M^-1 d
-      bound[27] = gw * rr * rr;
-      bound[28] = 1.0;
-      bound[29] = rr * rr;
-      bound[30] = bound[31] = 1.0;
-    } else {
-      // the record terms are products of two per-query slots; slot magnitudes per method (icp_kernels.hpp, kTermA/B tables)
-      double slot[10];
-      const unsigned char *ta, *tb;
-      static const unsigned char A0[kRec] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9};
-      static const unsigned char B0[kRec] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 3, 4, 5, 4, 5, 5, 6, 6, 6, 6, 6, 6, 6, 7, 7, 9, 9};
-      static const unsigned char A1[kRec] = {3, 3, 3, 4, 4, 4, 5, 5, 5, 0, 1, 2, 3, 4, 5, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 8, 9, 9};
-      static const unsigned char B1[kRec] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 7, 7, 7, 7, 7, 7, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 7, 9, 9};
-      if (params->method == O3DS_ICP_POINT_TO_POINT) {  // also the information-matrix pass (same slots, q q^T terms bounded by p q^T's)
-        for (int i = 0; i < 6; ++i) slot[i] = P;  // p, q
-        slot[6] = 0.0, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
-        ta = A1, tb = B1;
-      } else {
-        for (int i = 0; i < 3; ++i) slot[i] = P, slot[3 + i] = 1.0;  // J = [p x n ; n], unit normals
-        slot[6] = rr, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
-        ta = A0, tb = B0;
-      }
-      for (int k = 0; k < kRec; ++k) bound[k] = std::max(slot[ta[k]] * slot[tb[k]], 1e-30);
-      if (params->method == O3DS_ICP_POINT_TO_POINT)
-        for (int k = 0; k < 9; ++k) bound[k] = P * P;  // information matrix: terms 0..8 are q_a q_b or q_a (<= P^2 either way)
-    }
-    const bool no_split = ab_getenv("O3DS_SUM_NO_SPLIT") != nullptr;  // diagnostic: plain f64 sums
-    for (int k = 0; k < kRec; ++k) {
-      int e = 0;
-      (void)std::frexp(nn * bound[k], &e);                      // n * bound < 2^e
-      a.q_hi[k] = no_split ? 0.0 : std::ldexp(1.0, e + 3 - 53);  // 2^53 q = 8 * 2^e
-    }
-  }
+  record_quanta(tgt->grid, r, params->method, h->gicp_epsilon, src->n, a.q_hi);
   a.kmax = std::max(1, (int)std::ceil(r / tgt->grid.cell));  // a neighbour within r is at most this many cells away
   a.nn_cache = h->d_nn_cache;
   a.set_pos = h->fused && h->sets ? h->d_set_pos : nullptr;
@@ -1573,13 +1582,77 @@ void copy_result(o3ds_handle h, o3ds_icp_result* out) {
 int read_state(o3ds_handle h, o3ds_icp_result* out, const IcpStateDev* d_from = nullptr) {
   HIP_TRY(hipMemcpyAsync(h->h_state, d_from ? d_from : h->d_state, sizeof(IcpStateDev), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (out) {
-    memcpy(out->transformation, h->h_state->T, sizeof(double) * 16);
-    out->fitness = h->h_state->fitness;
-    out->inlier_rmse = h->h_state->rmse;
-    out->iterations = h->h_state->iterations;
-    out->converged = h->h_state->converged;
-    out->n_corr = h->h_state->n_corr;
+  copy_result(h, out);
+  return O3DS_OK;
+}
+
+// the session's part of a fused launch's arguments (init, written by begin_session, is read by the first launch only); the caller adds
+// its own: range, slots, first, pass_index, states, seq, trace, stats
+IcpFusedArgs fused_args(o3ds_handle h, size_t n_src_total) {
+  IcpFusedArgs fa{};
+  fa.pass = h->pass;
+  fa.n_src_total = (unsigned long long)n_src_total;
+  fa.max_iter = h->params.max_iteration;
+  fa.rel_fitness = h->params.relative_fitness;
+  fa.rel_rmse = h->params.relative_rmse;
+  fa.init = *h->h_state;
+  return fa;
+}
+
+// launch j of a session writes its state here: the two slots at the head of d_fused alternate, launch j + 1 reads what launch j wrote
+IcpStateDev* fused_state_out(o3ds_handle h, int j) { return (IcpStateDev*)(h->d_fused + (size_t)(j & 1) * kFusedStateStride); }
+
+// one pass over a's range and, where d_record is given, the reduction of its workgroup rows into that record
+int accumulate_pass(o3ds_handle h, const IcpPassArgs& a, double* d_record) {
+  const int nb = pass_blocks(h, a.count);
+  launch_accumulate(h, a, nb);
+  if (d_record) icp_reduce_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, d_record, quantum_table(a));
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+// behind o3ds_icp_accumulate, o3ds_icp_nn_keys and o3ds_icp_accumulate_keys, which check their arguments: the session's pass over
+// source points first .. first + count.  keys_mode 0: search and accumulate, 1: search -> keys (no record), 2: keys -> accumulate
+int stepwise_pass(o3ds_handle h, size_t first, size_t count, int keys_mode, int rank, unsigned long long* d_keys, double* d_record) {
+  IcpPassArgs a = h->pass;
+  a.first = first;
+  a.count = count;
+  a.keys_mode = keys_mode;
+  a.keys_rank = rank;
+  a.keys = d_keys;
+  return accumulate_pass(h, a, d_record);
+}
+
+// the host-array forms: uploads both clouds, runs fn(source, target) on their ids and frees them; the error text of what failed first
+// survives the frees
+template <typename F>
+int with_uploaded_clouds(o3ds_handle h, const double* src_xyz, const double* src_normals, size_t n_src, const double* tgt_xyz,
+                         const double* tgt_normals, size_t n_tgt, F&& fn) {
+  o3ds_cloud s = 0, t = 0;
+  int rc = o3ds_cloud_upload(h, src_xyz, src_normals, n_src, &s);
+  if (rc) return rc;
+  rc = o3ds_cloud_upload(h, tgt_xyz, tgt_normals, n_tgt, &t);
+  if (!rc) rc = fn(s, t);
+  const std::string keep = h->err;
+  (void)o3ds_cloud_free(h, s);
+  if (t) (void)o3ds_cloud_free(h, t);
+  if (rc) h->err = keep;
+  return rc;
+}
+
+// the host loop of the two-launch forms: queue_pass() queues one correspondence pass and its one-workgroup tail.  The device loop
+// terminates itself (done flag); the host only looks between chunks of queued passes
+template <typename F>
+int two_launch_loop(o3ds_handle h, int total_passes, o3ds_icp_result* out, F&& queue_pass) {
+  int launched = 0;
+  while (launched < total_passes) {
+    const int chunk = std::min(total_passes - launched, launched == 0 ? 12 : 8);
+    for (int k = 0; k < chunk; ++k) queue_pass();
+    launched += chunk;
+    HIP_TRY(hipGetLastError());
+    const int rc = read_state(h, out);
+    if (rc) return rc;
+    if (h->h_state->done) break;
   }
   return O3DS_OK;
 }
@@ -2130,19 +2203,7 @@ int o3ds_icp_accumulate(o3ds_handle h, size_t first, size_t count, double* d_rec
   if (!h->session) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate: no session (call o3ds_icp_begin)");
   if (!d_record) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate: null record");
   if (first + count > h->session_n_src) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate: range outside source");
-  IcpPassArgs a = h->pass;
-  a.first = first;
-  a.count = count;
-  {
-    const int nb = pass_blocks(h, count);
-    if (h->session_precision == O3DS_PRECISION_F64)
-      launch_accumulate<P4d>(h, a, h->session_crop, nb);
-    else
-      launch_accumulate<P4f>(h, a, h->session_crop, nb);
-    icp_reduce_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, d_record, quantum_table(a));
-  }
-  HIP_TRY(hipGetLastError());
-  return O3DS_OK;
+  return stepwise_pass(h, first, count, 0, 0, nullptr, d_record);
 }
 
 // Partitioning B (one map split over the GPUs of a node): search pass -> keys; the caller MIN-all-reduces them; accumulate pass
@@ -2154,19 +2215,7 @@ int o3ds_icp_nn_keys(o3ds_handle h, size_t first, size_t count, int rank, unsign
   if (rank < 0 || rank > 15) return fail(h, O3DS_ERR_INVALID_ARG, "icp_nn_keys: rank must be 0..15 (4 bits of the key)");
   if (first + count > h->session_n_src) return fail(h, O3DS_ERR_INVALID_ARG, "icp_nn_keys: range outside source");
   if ((size_t)h->pass.n_tgt > ((size_t)1 << 28)) return fail(h, O3DS_ERR_INVALID_ARG, "icp_nn_keys: more than 2^28 target points per shard");
-  IcpPassArgs a = h->pass;
-  a.first = first;
-  a.count = count;
-  a.keys_mode = 1;
-  a.keys_rank = rank;
-  a.keys = d_keys;
-  const int nb = pass_blocks(h, count);
-  if (h->session_precision == O3DS_PRECISION_F64)
-    launch_accumulate<P4d>(h, a, h->session_crop, nb);
-  else
-    launch_accumulate<P4f>(h, a, h->session_crop, nb);
-  HIP_TRY(hipGetLastError());
-  return O3DS_OK;
+  return stepwise_pass(h, first, count, 1, rank, d_keys, nullptr);
 }
 
 int o3ds_icp_accumulate_keys(o3ds_handle h, size_t first, size_t count, int rank, const unsigned long long* d_keys, double* d_record) {
@@ -2176,20 +2225,7 @@ int o3ds_icp_accumulate_keys(o3ds_handle h, size_t first, size_t count, int rank
   if (!d_keys || !d_record) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate_keys: null argument");
   if (rank < 0 || rank > 15) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate_keys: rank must be 0..15");
   if (first + count > h->session_n_src) return fail(h, O3DS_ERR_INVALID_ARG, "icp_accumulate_keys: range outside source");
-  IcpPassArgs a = h->pass;
-  a.first = first;
-  a.count = count;
-  a.keys_mode = 2;
-  a.keys_rank = rank;
-  a.keys = const_cast<unsigned long long*>(d_keys);
-  const int nb = pass_blocks(h, count);
-  if (h->session_precision == O3DS_PRECISION_F64)
-    launch_accumulate<P4d>(h, a, h->session_crop, nb);
-  else
-    launch_accumulate<P4f>(h, a, h->session_crop, nb);
-  icp_reduce_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, d_record, quantum_table(a));
-  HIP_TRY(hipGetLastError());
-  return O3DS_OK;
+  return stepwise_pass(h, first, count, 2, rank, const_cast<unsigned long long*>(d_keys), d_record);
 }
 
 int o3ds_icp_update(o3ds_handle h, const double* d_record, uint64_t n_src_total) {
@@ -2211,30 +2247,20 @@ int o3ds_icp_pass(o3ds_handle h, size_t first, size_t count, size_t n_src_total,
   if (first + count > h->session_n_src) return fail(h, O3DS_ERR_INVALID_ARG, "icp_pass: range outside source");
   if (count > kFusedMaxQueries)
     return fail(h, O3DS_ERR_CAPACITY, "icp_pass: at most O3DS_ICP_PASS_MAX_QUERIES (262144) source points per call: use o3ds_icp_accumulate / o3ds_icp_update for larger shards");
-  IcpFusedArgs fa{};
-  fa.pass = h->pass;
+  IcpFusedArgs fa = fused_args(h, n_src_total);
   fa.pass.first = first;
   fa.pass.count = count;
-  fa.n_src_total = (unsigned long long)n_src_total;
-  fa.max_iter = h->params.max_iteration;
-  fa.rel_fitness = h->params.relative_fitness;
-  fa.rel_rmse = h->params.relative_rmse;
-  fa.init = *h->h_state;  // written by begin_session
   const int j = h->session_launches++;
   fa.first = j == 0;
   fa.pass_index = j;
   fa.state_in = h->session_state ? h->session_state : h->d_state;
-  fa.state_out = (IcpStateDev*)(h->d_fused + (size_t)(j & 1) * kFusedStateStride);
+  fa.state_out = fused_state_out(h, j);
   fa.state_host = nullptr;
   fa.slots_in = d_sums_in ? d_sums_in : d_sums_next;  // unused by the first launch
   fa.slots_out = d_sums_out;
   fa.slots_clear = d_sums_next;
   fa.trace = nullptr;
-  const int nb = fused_blocks(count);
-  if (h->session_precision == O3DS_PRECISION_F64)
-    launch_fused<P4d>(h, fa, h->session_crop, nb, true);
-  else
-    launch_fused<P4f>(h, fa, h->session_crop, nb, true);
+  launch_fused(h, fa, fused_blocks(count), true);
   h->session_state = fa.state_out;
   HIP_TRY(hipGetLastError());
   return O3DS_OK;
@@ -2246,27 +2272,18 @@ int o3ds_icp_pass_finish(o3ds_handle h, size_t n_src_total, const double* d_sums
   if (!h->session) return fail(h, O3DS_ERR_INVALID_ARG, "icp_pass_finish: no session");
   if (!out || !d_sums_in || !d_sums_scratch) return fail(h, O3DS_ERR_INVALID_ARG, "icp_pass_finish: null argument");
   if (h->session_launches == 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp_pass_finish: no pass was issued");
-  IcpFusedArgs fa{};  // the one-workgroup tail launch: folds the last pass, never reaches the body
-  fa.pass = h->pass;
+  IcpFusedArgs fa = fused_args(h, n_src_total);  // the one-workgroup tail launch: folds the last pass, never reaches the body
   fa.pass.count = 0;
-  fa.n_src_total = (unsigned long long)n_src_total;
-  fa.max_iter = h->params.max_iteration;
-  fa.rel_fitness = h->params.relative_fitness;
-  fa.rel_rmse = h->params.relative_rmse;
-  const int j = h->session_launches++;
   fa.first = 0;
   fa.state_in = h->session_state;
-  fa.state_out = (IcpStateDev*)(h->d_fused + (size_t)(j & 1) * kFusedStateStride);
+  fa.state_out = fused_state_out(h, h->session_launches++);
   fa.state_host = h->h_state_dev;
   fa.seq_host = pub_slot<unsigned long long>(h, kSeqSlot);
   fa.seq = ++h->fused_seq;
   fa.slots_in = d_sums_in;
   fa.slots_out = d_sums_scratch;  // a launch that still has iterations left would add an (empty) pass here
   fa.slots_clear = d_sums_scratch;
-  if (h->session_precision == O3DS_PRECISION_F64)
-    launch_fused<P4d>(h, fa, h->session_crop, 1, false);
-  else
-    launch_fused<P4f>(h, fa, h->session_crop, 1, false);
+  launch_fused(h, fa, 1, false);
   HIP_TRY(hipGetLastError());
   HIP_TRY(wait_fused_state(h, fa.seq));
   h->session = false;
@@ -2325,13 +2342,8 @@ int o3ds_information_matrix_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud tar
   a.method = kMethodInformation;
   double* d_record = nullptr;
   TMP_ALLOC(d_record, sizeof(double) * kRec);
-  const int nb = pass_blocks(h, a.count);
-  if (h->session_precision == O3DS_PRECISION_F64)
-    launch_accumulate<P4d>(h, a, h->session_crop, nb);
-  else
-    launch_accumulate<P4f>(h, a, h->session_crop, nb);
-  icp_reduce_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, d_record, quantum_table(a));
-  HIP_TRY(hipGetLastError());
+  rc = accumulate_pass(h, a, d_record);
+  if (rc) return rc;
   double rec[kRec];
   rc = read_back(h, {{rec, d_record, sizeof(rec)}});
   if (rc) return rc;
@@ -2352,16 +2364,9 @@ int o3ds_information_matrix(o3ds_handle h, const double* src_xyz, size_t n_src, 
   if (!T || !information) return fail(h, O3DS_ERR_INVALID_ARG, "information_matrix: null argument");
   if (!(max_correspondence_distance > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
   if (n_tgt == 0) return fail(h, O3DS_ERR_EMPTY, "information_matrix: empty target");
-  o3ds_cloud s = 0, t = 0;
-  int rc = o3ds_cloud_upload(h, src_xyz, nullptr, n_src, &s);
-  if (rc) return rc;
-  rc = o3ds_cloud_upload(h, tgt_xyz, nullptr, n_tgt, &t);
-  if (!rc) rc = o3ds_information_matrix_dev(h, s, t, nullptr, T, max_correspondence_distance, information);
-  const std::string keep = h->err;
-  (void)o3ds_cloud_free(h, s);
-  if (t) (void)o3ds_cloud_free(h, t);
-  if (rc) h->err = keep;
-  return rc;
+  return with_uploaded_clouds(h, src_xyz, nullptr, n_src, tgt_xyz, nullptr, n_tgt, [&](o3ds_cloud s, o3ds_cloud t) {
+    return o3ds_information_matrix_dev(h, s, t, nullptr, T, max_correspondence_distance, information);
+  });
 }
 
 int o3ds_icp_point_to_point_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* target_crop, const double init[16],
@@ -2380,16 +2385,8 @@ int o3ds_icp_point_to_point(o3ds_handle h, const double* src_xyz, size_t n_src, 
   if (!params || !out || !init) return fail(h, O3DS_ERR_INVALID_ARG, "icp: null argument");
   if (!(params->max_correspondence_distance > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
   if (n_tgt == 0) return fail(h, O3DS_ERR_EMPTY, "icp: empty target (map patch size is zero)");
-  o3ds_cloud s = 0, t = 0;
-  int rc = o3ds_cloud_upload(h, src_xyz, nullptr, n_src, &s);
-  if (rc) return rc;
-  rc = o3ds_cloud_upload(h, tgt_xyz, nullptr, n_tgt, &t);
-  if (!rc) rc = o3ds_icp_point_to_point_dev(h, s, t, nullptr, init, params, out);
-  const std::string keep = h->err;
-  (void)o3ds_cloud_free(h, s);
-  if (t) (void)o3ds_cloud_free(h, t);
-  if (rc) h->err = keep;
-  return rc;
+  return with_uploaded_clouds(h, src_xyz, nullptr, n_src, tgt_xyz, nullptr, n_tgt,
+                              [&](o3ds_cloud s, o3ds_cloud t) { return o3ds_icp_point_to_point_dev(h, s, t, nullptr, init, params, out); });
 }
 
 int o3ds_icp_generalized_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* target_crop, const double init[16],
@@ -2428,16 +2425,8 @@ int o3ds_icp_generalized(o3ds_handle h, const double* src_xyz, const double* src
   if (!params || !out || !init) return fail(h, O3DS_ERR_INVALID_ARG, "icp: null argument");
   if (!(params->max_correspondence_distance > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
   if (n_tgt == 0) return fail(h, O3DS_ERR_EMPTY, "icp: empty target (map patch size is zero)");
-  o3ds_cloud s = 0, t = 0;
-  int rc = o3ds_cloud_upload(h, src_xyz, src_normals, n_src, &s);
-  if (rc) return rc;
-  rc = o3ds_cloud_upload(h, tgt_xyz, tgt_normals, n_tgt, &t);
-  if (!rc) rc = o3ds_icp_generalized_dev(h, s, t, nullptr, init, params, out);
-  const std::string keep = h->err;
-  (void)o3ds_cloud_free(h, s);
-  if (t) (void)o3ds_cloud_free(h, t);
-  if (rc) h->err = keep;
-  return rc;
+  return with_uploaded_clouds(h, src_xyz, src_normals, n_src, tgt_xyz, tgt_normals, n_tgt,
+                              [&](o3ds_cloud s, o3ds_cloud t) { return o3ds_icp_generalized_dev(h, s, t, nullptr, init, params, out); });
 }
 
 int o3ds_icp_overlap_next(o3ds_handle h, o3ds_overlap_fn fn, void* arg) {
@@ -2470,14 +2459,8 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
   const IcpPassArgs a = h->pass;
   if (use_fused) {
     // launch j = [tail of pass j-1 in every workgroup's prologue] + pass j; launch max_iter+1 is prologue-only (one workgroup)
-    IcpFusedArgs fa{};
-    fa.pass = a;
-    fa.n_src_total = (unsigned long long)a.count;
-    fa.max_iter = params->max_iteration;
-    fa.rel_fitness = params->relative_fitness;
-    fa.rel_rmse = params->relative_rmse;
+    IcpFusedArgs fa = fused_args(h, a.count);
     const int nb = fused_blocks(a.count);
-    fa.init = *h->h_state;
     const int total = params->max_iteration + 2;
     // O3DS_FUSED_TRACE=<file>: phase timestamps of every workgroup of launch 5 (development aid, see scripts/fused_trace.py)
     const char* trace_path = ab_getenv("O3DS_FUSED_TRACE");
@@ -2503,11 +2486,10 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
       // handle needed plus one, then four at a time
       const int chunk = std::min(total - j, j == 0 ? h->fused_chunk_hint[target_crop ? 1 : 0] : 4);
       for (int k = 0; k < chunk; ++k, ++j) {
-        const int par = j & 1;
         fa.first = j == 0;
         fa.pass_index = j;
         fa.state_in = last;
-        fa.state_out = (IcpStateDev*)(h->d_fused + par * kFusedStateStride);
+        fa.state_out = fused_state_out(h, j);
         // slot buffers rotate with a launch counter that runs across registrations: launch g reads (g-1)%3, adds into g%3, clears (g+1)%3
         const unsigned long long g = h->fused_launches++;
         fa.slots_in = (const double*)(h->d_fused + kFusedSlotsOff + ((g + 2) % 3) * kFusedSlotBufBytes);
@@ -2519,10 +2501,7 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
         fa.state_host = k == chunk - 1 ? h->h_state_dev : nullptr;  // the launch the host waits for also writes the pinned copy
         fa.seq_host = pub_slot<unsigned long long>(h, kSeqSlot);
         if (fa.state_host) fa.seq = ++h->fused_seq;
-        if (h->session_precision == O3DS_PRECISION_F64)
-          launch_fused<P4d>(h, fa, h->session_crop, tail_only ? 1 : nb, !tail_only);
-        else
-          launch_fused<P4f>(h, fa, h->session_crop, tail_only ? 1 : nb, !tail_only);
+        launch_fused(h, fa, tail_only ? 1 : nb, !tail_only);
         last = fa.state_out;
       }
       {
@@ -2577,26 +2556,12 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
   }
   const int nb = pass_blocks(h, a.count);
   const int total_passes = params->max_iteration + 1;  // max_iter updates need max_iter+1 correspondence passes
-  int launched = 0;
-  while (launched < total_passes) {
-    // the device loop terminates itself (done flag); the host only checks between chunks of queued passes
-    const int chunk = std::min(total_passes - launched, launched == 0 ? 12 : 8);
-    for (int k = 0; k < chunk; ++k) {
-      if (h->session_precision == O3DS_PRECISION_F64)
-        launch_accumulate<P4d>(h, a, h->session_crop, nb);
-      else
-        launch_accumulate<P4f>(h, a, h->session_crop, nb);
-      icp_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, (unsigned long long)a.count,
-                                                            params->max_iteration, params->relative_fitness, params->relative_rmse,
-                                                            h->debug_update, h->session_method, quantum_table(a));
-    }
-    launched += chunk;
-    HIP_TRY(hipGetLastError());
-    rc = read_state(h, out);
-    if (rc) return rc;
-    if (h->h_state->done) break;
-  }
-  return O3DS_OK;
+  return two_launch_loop(h, total_passes, out, [&] {
+    launch_accumulate(h, a, nb);
+    icp_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, (unsigned long long)a.count,
+                                                          params->max_iteration, params->relative_fitness, params->relative_rmse,
+                                                          h->debug_update, h->session_method, quantum_table(a));
+  });
 }
 
 int o3ds_icp_point_to_plane(o3ds_handle h, const double* src_xyz, size_t n_src, const double* tgt_xyz, const double* tgt_normals,
@@ -2607,16 +2572,8 @@ int o3ds_icp_point_to_plane(o3ds_handle h, const double* src_xyz, size_t n_src, 
   if (!(params->max_correspondence_distance > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
   if (n_tgt == 0) return fail(h, O3DS_ERR_EMPTY, "icp: empty target (map patch size is zero)");
   if (!tgt_normals) return fail(h, O3DS_ERR_NO_NORMALS, "TransformationEstimationPointToPlane requires target normals");
-  o3ds_cloud s = 0, t = 0;
-  int rc = o3ds_cloud_upload(h, src_xyz, nullptr, n_src, &s);
-  if (rc) return rc;
-  rc = o3ds_cloud_upload(h, tgt_xyz, tgt_normals, n_tgt, &t);
-  if (!rc) rc = o3ds_icp_point_to_plane_dev(h, s, t, nullptr, init, params, out);
-  const std::string keep = h->err;
-  (void)o3ds_cloud_free(h, s);
-  if (t) (void)o3ds_cloud_free(h, t);
-  if (rc) h->err = keep;
-  return rc;
+  return with_uploaded_clouds(h, src_xyz, nullptr, n_src, tgt_xyz, tgt_normals, n_tgt,
+                              [&](o3ds_cloud s, o3ds_cloud t) { return o3ds_icp_point_to_plane_dev(h, s, t, nullptr, init, params, out); });
 }
 
 
@@ -3468,8 +3425,6 @@ int random_down_sample_t(o3ds_handle h, const CloudRec& in, double ratio, unsign
   dbg_sync(h, 4);
   return O3DS_OK;
 }
-
-#define DISPATCH(prec, fn, ...) ((prec) == O3DS_PRECISION_F64 ? fn<P4d>(__VA_ARGS__) : fn<P4f>(__VA_ARGS__))
 
 }  // namespace
 

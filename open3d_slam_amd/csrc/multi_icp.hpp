@@ -7,8 +7,9 @@
 namespace {
 
 template <typename P4>
-void launch_multi_accumulate(o3ds_handle h, const IcpMultiArgs& ma, bool crop, bool gicp, int nblocks) {
-  if (gicp) {
+void launch_multi_accumulate_t(o3ds_handle h, const IcpMultiArgs& ma, int nblocks) {
+  const bool crop = h->session_crop;
+  if (h->session_method == O3DS_ICP_GENERALIZED) {
     if (crop)
       icp_multi_accumulate_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
     else
@@ -19,6 +20,10 @@ void launch_multi_accumulate(o3ds_handle h, const IcpMultiArgs& ma, bool crop, b
     else
       icp_multi_accumulate_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
   }
+}
+
+void launch_multi_accumulate(o3ds_handle h, const IcpMultiArgs& ma, int nblocks) {
+  DISPATCH(h->session_precision, launch_multi_accumulate_t, h, ma, nblocks);
 }
 
 }  // namespace
@@ -35,8 +40,6 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
   if (!targets) return fail(h, O3DS_ERR_INVALID_ARG, "icp_register_multi: null target list");
   if (n_targets == 0 || n_targets > (size_t)kMultiMaxTargets)
     return fail(h, O3DS_ERR_INVALID_ARG, "icp_register_multi: between 1 and 16 targets");
-  if (params->method != O3DS_ICP_POINT_TO_PLANE && params->method != O3DS_ICP_GENERALIZED && params->method != O3DS_ICP_POINT_TO_POINT)
-    return fail(h, O3DS_ERR_INVALID_ARG, "icp: unknown method");
   CloudRec* src = find_cloud_lazy(h, source);
   if (!src) return fail(h, O3DS_ERR_INVALID_ARG, "icp_register_multi: unknown source cloud id");
   // ---- the list, before anything is touched: every id a cloud of this handle; a non-empty target with its index and normals
@@ -124,28 +127,13 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
   if (rc) return rc;
   ma.tgt = d_desc;
   ma.pass.partials = d_rows;
-  const bool gicp = params->method == O3DS_ICP_GENERALIZED;
   const unsigned long long den_mult = joint ? (unsigned long long)n_targets : 1ull;
   const int total_passes = params->max_iteration + 1;  // max_iter updates need max_iter + 1 correspondence passes
-  int launched = 0;
-  while (launched < total_passes) {
-    // the device loop terminates itself (done flag); the host only looks between chunks of queued passes, as o3ds_icp_register_dev does
-    const int chunk = std::min(total_passes - launched, launched == 0 ? 12 : 8);
-    for (int c = 0; c < chunk; ++c) {
-      if (h->session_precision == O3DS_PRECISION_F64)
-        launch_multi_accumulate<P4d>(h, ma, h->session_crop, gicp, nb);
-      else
-        launch_multi_accumulate<P4f>(h, ma, h->session_crop, gicp, nb);
-      icp_multi_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(d_rows, nrows, h->d_state, n_upper, ma.pass.count_dev, den_mult, params->max_iteration,
-                                                                  params->relative_fitness, params->relative_rmse, params->method, quantum_table(ma.pass));
-    }
-    launched += chunk;
-    HIP_TRY(hipGetLastError());
-    rc = read_state(h, out);
-    if (rc) return rc;
-    if (h->h_state->done) break;
-  }
-  return O3DS_OK;
+  return two_launch_loop(h, total_passes, out, [&] {  // the host loop of o3ds_icp_register_dev's two-launch form
+    launch_multi_accumulate(h, ma, nb);
+    icp_multi_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(d_rows, nrows, h->d_state, n_upper, ma.pass.count_dev, den_mult, params->max_iteration,
+                                                                params->relative_fitness, params->relative_rmse, params->method, quantum_table(ma.pass));
+  });
 }
 
 }  // extern "C"

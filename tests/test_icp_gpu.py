@@ -288,6 +288,36 @@ def test_two_launch_mode_is_bitwise_the_default(oracle, small_c2, backend_f32, m
         be.close()
 
 
+def test_profiling_brackets_every_pass_launch_and_nothing_else(small_c2, backend_f32, monkeypatch):
+    """profile_enable(1) puts a pair of events around every launch that runs a correspondence pass; profile_read counts the pairs.
+    max_iter=3 with tolerances of 0 runs all three iterations: four passes (three updates and the evaluation of the last pose).  The
+    default form queues them as four launches plus a one-workgroup tail that is not bracketed, the two-launch form (O3DS_ICP_MODE=launch)
+    as four pass launches whose update kernels are not bracketed: 4 either way.  The count was recorded from profile_read() of the commit
+    before the bracket became one helper of both launchers (4 and 4 on an MI355X) and is held exactly."""
+    src, tgt, nrm, _ = small_c2
+    monkeypatch.setenv("O3DS_ICP_MODE", "launch")
+    two_launch = backend.Backend(0, backend.PRECISION_F32, ab=True)
+    try:
+        for be in (backend_f32, two_launch):
+            s, t = be.upload(src), be.upload(tgt, nrm)
+            try:
+                be.profile_enable(1)
+                got = be.icp_register_dev(s, t, 1.0, max_iter=3, rel_fitness=0.0, rel_rmse=0.0)
+                n, ms = be.profile_read()
+                print("bracketed launches", n, "ms", ms)
+                assert got["iterations"] == 3
+                assert n == 4 and ms > 0.0
+                be.profile_enable(0)
+                be.icp_register_dev(s, t, 1.0, max_iter=3, rel_fitness=0.0, rel_rmse=0.0)
+                assert be.profile_read() == (0, 0.0)
+            finally:
+                be.profile_enable(0)
+                be.free(s)
+                be.free(t)
+    finally:
+        two_launch.close()
+
+
 def test_fused_prologue_kernel_mode(oracle, small_c2, monkeypatch):
     """Default form (O3DS_ICP_MODE=fused): ONE launch per pass -- the previous pass's tail (record fold, convergence test, 6x6 solve, T <- U*T) runs
     in every workgroup's prologue.  Same loop semantics (iterations / converged / early stop / empty set) as the oracle, both
