@@ -356,6 +356,44 @@ int o3ds_icp_register_sharded(o3ds_handle h, int partitioning, o3ds_cloud source
 int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3ds_cloud* targets, size_t n_targets,
                             const o3ds_crop* target_crop, const double init[16], const o3ds_icp_params* params, o3ds_icp_result* out);
 
+/* ---- SEVERAL INDEPENDENT registrations of one handle in one call: loop-closure refinements of a scan's candidates, the odometry
+ *      constraints between adjacent submaps, several initial guesses for one pair.  A capability beyond the reference, which runs them
+ *      one after another (PlaceRecognition.cpp:71-111, its `omp parallel for` is commented out).  The other axis of
+ *      o3ds_icp_register_multi: that is one problem with many targets, this is many problems, each with its own pose, state and
+ *      convergence.  One launch per pass serves every entry that is still running.
+ * Entry k IS the registration o3ds_icp_register_dev(h, entries[k].source, entries[k].target, entries[k].target_crop, entries[k].init,
+ * params, &out[k]): out[k] holds that call's values in every field (transformation, fitness, inlier_rmse, iterations, converged,
+ * n_corr), bit for bit, in both storage precisions and for the three estimators.  Grounds: the target index and the quanta of the exact
+ * sums are per entry and are the one-pair call's; the queries of an entry are dealt out in the same batches of 128 in the same order;
+ * the sums over the batches are exact and hence order-free; and searching every pass instead of keeping candidate sets does not change
+ * a bit of the matches.  `params` (method, radius, max_iteration, thresholds) is shared by the batch.  All clouds belong to `h` and have
+ * its precision.  Entries may repeat a source or a target (the same pair with different `init` is the multi-hypothesis case); some may
+ * carry a crop and others not.  A target without an index is indexed as the one-pair call would index it.  A cloud in persistent-map
+ * form that is the SOURCE of an entry is folded into array form before the batch starts (the one-pair call folds it when its turn comes).
+ * n_entries == 1 delegates to o3ds_icp_register_dev.  A function armed with o3ds_icp_overlap_next is NOT consumed by this call, whatever
+ * n_entries: it stays armed for the next one-pair registration.
+ * Whole-call errors, returned before anything is touched (the handle stays usable, out / status are not written):
+ *   O3DS_ERR_INVALID_ARG  a null pointer (entries, params, out, status); n_entries == 0 or > O3DS_BATCH_MAX_ENTRIES; an id that is not a
+ *                         cloud of `h`; a non-empty target without the normals the estimator needs; a source / target precision
+ *                         mismatch; max_correspondence_distance <= 0, an unknown method, a negative max_iteration.
+ *   O3DS_ERR_CAPACITY     (nothing is looped) a source of more than O3DS_ICP_PASS_MAX_QUERIES points; a total of more than
+ *                         O3DS_BATCH_MAX_WORKGROUPS workgroups per pass, sum over the entries of max(ceil(n_src_k / 128), 1).
+ * Per-entry outcomes go to status[k]: O3DS_OK; O3DS_ERR_EMPTY for an entry whose target is empty (as the one-pair call); otherwise the
+ * code the one-pair call returns for that entry (a generalized-ICP source without normals: O3DS_ERR_NO_NORMALS).  Such an entry is
+ * skipped, its out[k] is zeroed and the others run.  The function returns O3DS_OK when the batch ran, whatever the entries reported.
+ * Candidate sets and the fused loop are not used by this call: every pass is two launches and searches from the previous pass's match
+ * as its bound.  A batch of small sources fills the device where one of them cannot; a batch of large ones is better served by the
+ * one-pair call in a loop (DESIGN.md 7.5 has the measurements). */
+#define O3DS_BATCH_MAX_ENTRIES 64
+#define O3DS_BATCH_MAX_WORKGROUPS 65536
+typedef struct {
+  o3ds_cloud source, target;
+  const o3ds_crop* target_crop; /* may be NULL */
+  double init[16];              /* column-major, as everywhere */
+} o3ds_icp_batch_entry;
+int o3ds_icp_register_batch(o3ds_handle h, const o3ds_icp_batch_entry* entries, size_t n_entries, const o3ds_icp_params* params,
+                            o3ds_icp_result* out /* [n_entries] */, int* status /* [n_entries] */);
+
 /* ---- scan pre-processing: ScanToMapIcp::preprocess (ScanToMapRegistration.cpp:35-40),
  *      LidarOdometry::preprocess (Odometry.cpp:25-30) ------------------------------------------ */
 /* CroppingVolume::crop (croppers.cpp:76-106): stable compaction of points (+normals) inside the volume. */

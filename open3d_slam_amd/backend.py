@@ -47,6 +47,11 @@ _dp = C.POINTER(C.c_double)
 _H = C.c_void_p
 _CL = C.c_uint64
 
+
+class IcpBatchEntry(C.Structure):  # o3ds_icp_batch_entry
+    _fields_ = [("source", _CL), ("target", _CL), ("target_crop", C.POINTER(Crop)), ("init", C.c_double * 16)]
+
+
 # name -> (restype, argtypes); must list every symbol include/o3ds_backend.h declares
 class CarvingParams(C.Structure):  # o3ds_carving_params (SpaceCarvingParameters, Parameters.hpp:85-92)
     _fields_ = [("voxel_size", C.c_double), ("max_raytracing_length", C.c_double), ("truncation_distance", C.c_double),
@@ -170,6 +175,8 @@ SIGNATURES = {
     "o3ds_icp_register_sharded": (C.c_int, [_H, C.c_int, _CL, _CL, C.POINTER(Crop), _dp, C.POINTER(IcpParams), C.POINTER(IcpResult)]),
     "o3ds_icp_register_multi": (C.c_int, [_H, C.c_int, _CL, C.POINTER(_CL), C.c_size_t, C.POINTER(Crop), _dp, C.POINTER(IcpParams),
                                           C.POINTER(IcpResult)]),
+    "o3ds_icp_register_batch": (C.c_int, [_H, C.POINTER(IcpBatchEntry), C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult),
+                                          C.POINTER(C.c_int)]),
     "o3ds_crop_cloud": (C.c_int, [_H, _CL, C.POINTER(Crop), C.POINTER(_CL)]),
     "o3ds_voxel_down_sample": (C.c_int, [_H, _CL, C.c_double, C.POINTER(_CL)]),
     "o3ds_crop_voxel_down_sample": (C.c_int, [_H, _CL, C.POINTER(Crop), C.c_double, C.POINTER(_CL)]),
@@ -625,6 +632,83 @@ class Backend:
         self._ck(self.lib.o3ds_icp_register_multi(self.h, int(form), source, arr, len(ids), C.byref(crop) if crop else None, ip, C.byref(params),
                                                   C.byref(out)))
         return self._result(out)
+
+    # -- several independent registrations in one call (o3ds_backend.h, o3ds_icp_register_batch)
+    BATCH_MAX_ENTRIES, BATCH_MAX_WORKGROUPS = 64, 65536
+
+    ICP_PASS_MAX_QUERIES = 262144
+
+    def icp_register_batch(self, entries, params: IcpParams | None = None, split: bool = False):
+        """o3ds_icp_register_batch: `entries` is a sequence of (source, target, crop or None, init or None) -- or of dicts with those
+        keys (`crop` and `init` optional) --, `params` an IcpParams shared by the batch (Backend._params builds one).  Returns
+        (results, status): one result dict per entry in order (all fields zero where the entry did not run) and the per-entry
+        status codes (0, ERR_EMPTY for an empty target, otherwise the code of the one-pair call).
+        split=True serves a list of ANY shape with the same results (every entry is its one-pair call bit for bit either way): an
+        entry whose source exceeds ICP_PASS_MAX_QUERIES points goes through icp_register_dev (and raises what that raises), the
+        others go in as many batches as BATCH_MAX_ENTRIES and BATCH_MAX_WORKGROUPS ask for -- what the mirrors of the reference's
+        loops use, whose overlap clouds of whole submaps can be larger than one batch entry."""
+        if params is None:
+            raise ValueError("icp_register_batch: params (IcpParams) is required")
+        if split:
+            return self._icp_register_batch_split(list(entries), params)
+        rows = []
+        for e in entries:
+            if isinstance(e, dict):
+                rows.append((e["source"], e["target"], e.get("crop"), e.get("init")))
+            else:
+                e = tuple(e)
+                rows.append((e[0], e[1], e[2] if len(e) > 2 else None, e[3] if len(e) > 3 else None))
+        n = len(rows)
+        arr = (IcpBatchEntry * max(n, 1))()
+        keep = []  # the crops the entries point to
+        for k, (src, tgt, crop, init) in enumerate(rows):
+            arr[k].source = int(src)
+            arr[k].target = int(tgt)
+            if crop is not None:
+                keep.append(crop)
+                arr[k].target_crop = C.pointer(crop)
+            flat = _IDENTITY16 if init is None else colmajor(init)
+            for i in range(16):
+                arr[k].init[i] = flat[i]
+        out = (IcpResult * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        self._ck(self.lib.o3ds_icp_register_batch(self.h, arr, n, C.byref(params), out, status))
+        return [self._result(out[k]) for k in range(n)], [int(status[k]) for k in range(n)]
+
+    def _icp_register_batch_split(self, entries, params: IcpParams):
+        norm = []
+        for e in entries:
+            if isinstance(e, dict):
+                norm.append((e["source"], e["target"], e.get("crop"), e.get("init")))
+            else:
+                e = tuple(e)
+                norm.append((e[0], e[1], e[2] if len(e) > 2 else None, e[3] if len(e) > 3 else None))
+        results, status = [None] * len(norm), [OK] * len(norm)
+        chunk, chunk_wg = [], 0
+
+        def flush():
+            nonlocal chunk, chunk_wg
+            if chunk:
+                res, st = self.icp_register_batch([norm[k] for k in chunk], params)
+                for k, r, c in zip(chunk, res, st):
+                    results[k], status[k] = r, c
+            chunk, chunk_wg = [], 0
+
+        for k, (src, tgt, crop, init) in enumerate(norm):
+            n = self.size(src)[0]
+            if n > self.ICP_PASS_MAX_QUERIES:
+                flush()  # (keeps the order of the device work that of the list)
+                results[k] = self.icp_register_dev(src, tgt, params.max_correspondence_distance, init=init, max_iter=params.max_iteration,
+                                                   rel_fitness=params.relative_fitness, rel_rmse=params.relative_rmse, target_crop=crop,
+                                                   method=params.method)
+                continue
+            wg = max((n + 127) // 128, 1)
+            if len(chunk) == self.BATCH_MAX_ENTRIES or chunk_wg + wg > self.BATCH_MAX_WORKGROUPS:
+                flush()
+            chunk.append(k)
+            chunk_wg += wg
+        flush()
+        return results, status
 
     def set_gicp_epsilon(self, eps: float):
         self._ck(self.lib.o3ds_set_gicp_epsilon(self.h, float(eps)))

@@ -34,8 +34,48 @@ class CloudRegistration:  # CloudRegistration.hpp:19-27
     def registerClouds(self, source: PointCloud, target: PointCloud, init) -> RegistrationResult:
         raise NotImplementedError
 
+    def registerCloudsBatch(self, sources, targets, inits) -> list:
+        raise NotImplementedError
+
     def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:
         return None
+
+
+def _register_clouds_batch(reg, method: int, sources, targets, inits, target_crops=None) -> list:
+    """registerClouds of `reg` for every (sources[k], targets[k], inits[k]) in ONE o3ds_icp_register_batch call (a capability beyond the
+    reference): the results of the per-pair calls, bit for bit, in order.  Raises as the per-pair call raises: on what
+    the library refuses for the whole batch, and on the first entry that did not run (an empty target, a missing normal set).
+    Generalized ICP: a pair with a cloud that carries no normals takes the per-pair call, which estimates them on a copy
+    (o3ds_icp_generalized_dev) -- the batch entry point registers clouds as they are."""
+    sources, targets, inits = list(sources), list(targets), list(inits)
+    if not (len(sources) == len(targets) == len(inits)):
+        raise ValueError("registerCloudsBatch: sources, targets and inits differ in length")
+    if not sources:
+        return []
+    crops = list(target_crops) if target_crops is not None else [None] * len(sources)
+    be = sources[0].be
+    if method == _b.ICP_GENERALIZED:
+        single = [k for k, (s, t) in enumerate(zip(sources, targets)) if not (be.has_normals(s.id) and be.has_normals(t.id))]
+        if single:
+            out = [None] * len(sources)
+            for k in single:
+                out[k] = reg.registerClouds(sources[k], targets[k], inits[k], crops[k])
+            rest = [k for k in range(len(sources)) if out[k] is None]
+            done = _register_clouds_batch(reg, method, [sources[k] for k in rest], [targets[k] for k in rest], [inits[k] for k in rest],
+                                          [crops[k] for k in rest])
+            for k, r in zip(rest, done):
+                out[k] = r
+            return out
+    c = reg.icpConvergenceCriteria_
+    params = be._params(reg.maxCorrespondenceDistance_, c.max_iteration_, c.relative_fitness_, c.relative_rmse_, method)
+    try:
+        results, status = be.icp_register_batch([(s.id, t.id, crop, init) for s, t, crop, init in zip(sources, targets, crops, inits)], params, split=True)
+    except _b.BackendError as e:
+        raise RuntimeError(str(e)) from e
+    for k, st in enumerate(status):
+        if st != 0:
+            raise RuntimeError(f"registerCloudsBatch: entry {k} failed with status {st}")
+    return [RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"]) for r in results]
 
 
 class RegistrationIcpPointToPlane(CloudRegistration):  # CloudRegistration.hpp:29-42
@@ -57,6 +97,10 @@ class RegistrationIcpPointToPlane(CloudRegistration):  # CloudRegistration.hpp:2
         except _b.BackendError as e:
             raise RuntimeError(str(e)) from e
         return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+    def registerCloudsBatch(self, sources, targets, inits, target_crops=None) -> list:
+        """registerClouds for every pair, in one device call: the same results in order (see _register_clouds_batch)"""
+        return _register_clouds_batch(self, _b.ICP_POINT_TO_PLANE, sources, targets, inits, target_crops)
 
     def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:
         """CloudRegistration.cpp:49-56: assert_gt on both parameters, then EstimateNormals(Hybrid) + NormalizeNormals +
@@ -86,6 +130,10 @@ class RegistrationIcpGeneralized(CloudRegistration):  # CloudRegistration.hpp:56
             raise RuntimeError(str(e)) from e
         return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
 
+    def registerCloudsBatch(self, sources, targets, inits, target_crops=None) -> list:
+        """registerClouds for every pair, in one device call: the same results in order (see _register_clouds_batch)"""
+        return _register_clouds_batch(self, _b.ICP_GENERALIZED, sources, targets, inits, target_crops)
+
     def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:  # CloudRegistration.cpp:22-30
         if not self.maxRadiusNormalEstimation_ > 0.0:
             raise RuntimeError("maxRadiusNormalEstimation_")
@@ -109,6 +157,10 @@ class RegistrationIcpPointToPoint(CloudRegistration):  # CloudRegistration.hpp:3
         except _b.BackendError as e:
             raise RuntimeError(str(e)) from e
         return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+    def registerCloudsBatch(self, sources, targets, inits, target_crops=None) -> list:
+        """registerClouds for every pair, in one device call: the same results in order (see _register_clouds_batch)"""
+        return _register_clouds_batch(self, _b.ICP_POINT_TO_POINT, sources, targets, inits, target_crops)
 
     def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:  # base-class no-op (CloudRegistration.hpp:26)
         return None

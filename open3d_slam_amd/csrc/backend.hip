@@ -5239,3 +5239,4 @@ int o3ds_global_optimization(o3ds_handle h, double* node_poses, size_t n_nodes, 
 
 #include "sharded.hpp"
 #include "multi_icp.hpp"
+#include "batch_icp.hpp"

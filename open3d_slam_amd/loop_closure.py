@@ -14,8 +14,11 @@ from .submap_collection import computeOdometryConstraints
 
 
 class LoopClosure:
-    def __init__(self, be, mapper, params=None):
-        """mapper: a Mapper built with submaps=SubmapCollection(...); params: its MapperParameters (default: the mapper's)."""
+    def __init__(self, be, mapper, params=None, batchRegistrations: bool = False):
+        """mapper: a Mapper built with submaps=SubmapCollection(...); params: its MapperParameters (default: the mapper's).
+        batchRegistrations: the independent ICPs of a cycle -- the refinements of a finished submap's loop-closure candidates, the
+        odometry constraints -- run as batched registrations (PlaceRecognition.batchRefinement, computeOdometryConstraints(batch=True));
+        the constraints are the same.  Off by default: the call sequence of the reference."""
         if mapper.getSubmaps() is None:
             raise ValueError("LoopClosure needs a Mapper that maps into a SubmapCollection")
         self.be = be
@@ -27,11 +30,14 @@ class LoopClosure:
         self.lastLoopClosureConstraints_: list = []
         self.numLatestLoopClosureConstraints_ = 0
         self.isOptimizedGraphAvailable_ = False
+        self.batchRegistrations = bool(batchRegistrations)
+        if self.batchRegistrations:
+            self.submaps_.placeRecognition_.batchRefinement = True
         self.lastIncrement = None  # the dT handed to Mapper.loopClosureUpdate by the last update (diagnostics)
 
     def computeFeaturesIfReady(self):  # SlamWrapper.cpp:386-393
         if self.submaps_.numFinishedSubmaps() > 0:
-            self.submaps_.computeFeatures(self.submaps_.popFinishedSubmapIds())
+            self.submaps_.computeFeatures(self.submaps_.popFinishedSubmapIds(), batch=self.batchRegistrations)
 
     def attemptLoopClosuresIfReady(self):  # SlamWrapper.cpp:394-404
         if self.submaps_.numLoopClosureCandidates() > 0:
@@ -48,7 +54,7 @@ class LoopClosure:
         if not loopClosureConstraints:
             return []
         odometryConstraints = list(self.submaps_.getOdometryConstraints())
-        computeOdometryConstraints(self.be, self.submaps_, odometryConstraints)
+        computeOdometryConstraints(self.be, self.submaps_, odometryConstraints, batch=self.batchRegistrations)
         op = self.optimizationProblem_
         op.clearOdometryConstraints()
         op.insertLoopClosureConstraints(loopClosureConstraints)

@@ -12,6 +12,7 @@ import functools
 
 import numpy as np
 
+from . import backend as _b
 from .parameters import MapperParameters
 from .place_recognition import (ICP_RUN_UNTIL_CONVERGENCE_NUMBER_OF_ITERATIONS, VOXEL_EXPANSION_FACTOR_OVERLAP_COMPUTATION,
                                 VOXEL_SIZE_CORRESPONDENCE_SEARCH_IF_MAP_VOXEL_SIZE_IS_ZERO, Constraint, getMapVoxelSize)
@@ -214,6 +215,55 @@ def buildConstraint(be, sourceIdx: int, targetIdx: int, submaps, params: MapperP
             c.release()
     return Constraint(sourceToTarget_=T, sourceSubmapIdx_=sourceIdx, targetSubmapIdx_=targetIdx, informationMatrix_=info,
                       isInformationMatrixValid_=isEstimateInformationMatrix, isOdometryConstraint_=True)
+
+
+def buildConstraintsBatch(be, pairs, submaps, params: MapperParameters, isComputeOverlap: bool, icpMaxCorrespondenceDistance: float,
+                          voxelSizeOverlapCompute: float, isEstimateInformationMatrix: bool) -> list:
+    """buildConstraint with ICP refinement for every (sourceIdx, targetIdx) of `pairs`, the registrations in ONE device call
+    (o3ds_icp_register_batch, a capability beyond the reference): the overlap crops of all pairs first, one batch of point-to-plane
+    ICPs from identity, then the information matrices in order.  Every entry is its one-pair registration bit for bit, so the
+    constraints are those of buildConstraint called pair by pair."""
+    held, clouds = [], []
+    try:
+        for sourceIdx, targetIdx in pairs:
+            source = submaps[sourceIdx].getMapPointCloud()
+            target = submaps[targetIdx].getMapPointCloud()
+            if isComputeOverlap:
+                i_s, i_t = be.overlap_indices(source.id, target.id, np.eye(4), voxelSizeOverlapCompute, 1)
+                source = PointCloud(be, be.select_by_index(source.id, i_s.astype(np.uint32)))
+                held.append(source)
+                target = PointCloud(be, be.select_by_index(target.id, i_t.astype(np.uint32)))
+                held.append(target)
+            clouds.append((source, target))
+        p = be._params(icpMaxCorrespondenceDistance, ICP_RUN_UNTIL_CONVERGENCE_NUMBER_OF_ITERATIONS, 1e-6, 1e-6, _b.ICP_POINT_TO_PLANE)
+        results, status = be.icp_register_batch([(s.id, t.id, None, np.eye(4)) for s, t in clouds], p, split=True)
+        for k, st in enumerate(status):
+            if st != 0:
+                raise _b.BackendError(st, f"buildConstraintsBatch: the registration of pair {pairs[k]} did not run")
+        out = []
+        for (sourceIdx, targetIdx), (source, target), r in zip(pairs, clouds, results):
+            T = np.array(r["transformation"])
+            info = np.eye(6)
+            if isEstimateInformationMatrix:
+                info = be.information_matrix_dev(source.id, target.id, icpMaxCorrespondenceDistance, T)
+            out.append(Constraint(sourceToTarget_=T, sourceSubmapIdx_=sourceIdx, targetSubmapIdx_=targetIdx, informationMatrix_=info,
+                                  isInformationMatrixValid_=isEstimateInformationMatrix, isOdometryConstraint_=True))
+        return out
+    finally:
+        for c in held:
+            c.release()
+
+
+def buildOdometryConstraintsBatch(be, pairs, submaps, params: MapperParameters) -> list:
+    """buildOdometryConstraint for every pair; with isRefineOdometryConstraintsBetweenSubmaps_ the pairs' ICPs go in one batch."""
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    if not params.isRefineOdometryConstraintsBetweenSubmaps_:  # nothing to batch: the per-pair form
+        return [buildOdometryConstraint(be, s, t, submaps, params) for s, t in pairs]
+    v = getMapVoxelSize(params.mapBuilder_, VOXEL_SIZE_CORRESPONDENCE_SEARCH_IF_MAP_VOXEL_SIZE_IS_ZERO)
+    return buildConstraintsBatch(be, pairs, submaps, params, True, VOXEL_EXPANSION_FACTOR_ICP_CORRESPONDENCE_DISTANCE * v,
+                                 VOXEL_EXPANSION_FACTOR_OVERLAP_COMPUTATION * v, True)
 
 
 def buildOdometryConstraint(be, sourceIdx: int, targetIdx: int, submaps, params: MapperParameters) -> Constraint:

@@ -77,8 +77,11 @@ def getMapVoxelSize(mapBuilder, valueIfZero: float) -> float:  # helpers.cpp:343
 
 
 class PlaceRecognition:
-    def __init__(self, be, params: MapperParameters | None = None, seed: int = 0):
+    def __init__(self, be, params: MapperParameters | None = None, seed: int = 0, batchRefinement: bool = False):
+        """batchRefinement: refine the candidates that pass the RANSAC gates with ONE batched registration instead of one ICP per
+        candidate (a capability beyond the reference; the constraints are the sequential form's, bit for bit).  Off by default."""
         self.be = be
+        self.batchRefinement = bool(batchRefinement)
         self.seed = int(seed)  # RANSAC's draws (Open3D seeds from std::random_device; here the seed is the caller's)
         self.lastRansacResult = None  # the RANSAC result of the last candidate examined (diagnostics)
         self.setParameters(params if params is not None else MapperParameters())
@@ -118,6 +121,8 @@ class PlaceRecognition:
         source = sourceSubmap.getMapPointCloud()
         src_idx = sourceSubmap.id_ if sourceSubmapIdx is None else sourceSubmapIdx
         ids = candidateIdxs if candidateIdxs is not None else [s.id_ for s in candidateSubmaps]
+        if self.batchRefinement:
+            return self._buildLoopClosureConstraintsBatch(sourceSubmap, candidateSubmaps, ids, src_idx, timestamp)
         for target_submap, tid in zip(candidateSubmaps, ids):
             r = self.ransac(sourceSubmap, target_submap)
             self.lastRansacResult = r
@@ -144,4 +149,48 @@ class PlaceRecognition:
             finally:
                 src_ov.release()
                 tgt_ov.release()
+        return constraints
+
+    def _buildLoopClosureConstraintsBatch(self, sourceSubmap, candidateSubmaps, ids, src_idx: int, timestamp: float) -> list:
+        """buildLoopClosureConstraints with the refinements of all candidates in one device call: the RANSAC step, both of its gates and
+        the overlap selection run for every candidate first; the survivors are refined by one registerCloudsBatch, each from its own
+        RANSAC transform; the fitness and consistency gates and the information matrices follow in candidate order.  Every entry of
+        the batch is its one-pair registration bit for bit (o3ds_icp_register_batch), so the list is the sequential form's."""
+        be = self.be
+        cfg = self.params_.placeRecognition_
+        source = sourceSubmap.getMapPointCloud()
+        constraints = []
+        survivors = []  # (tid, RANSAC transform, source overlap, target overlap)
+        try:
+            for target_submap, tid in zip(candidateSubmaps, ids):
+                r = self.ransac(sourceSubmap, target_submap)
+                self.lastRansacResult = r
+                if r["n_corr"] < cfg.ransacMinCorrespondenceSetSize_:
+                    continue
+                if not self.isRegistrationConsistent(r["transformation"]):
+                    continue
+                target = target_submap.getMapPointCloud()
+                voxel = VOXEL_EXPANSION_FACTOR_OVERLAP_COMPUTATION * getMapVoxelSize(
+                    self.params_.mapBuilder_, VOXEL_SIZE_CORRESPONDENCE_SEARCH_IF_MAP_VOXEL_SIZE_IS_ZERO)
+                i_s, i_t = be.overlap_indices(source.id, target.id, r["transformation"], voxel, 1)
+                src_ov = PointCloud(be, be.select_by_index(source.id, i_s.astype(np.uint32)))
+                survivors.append([tid, r["transformation"], src_ov, None])
+                survivors[-1][3] = PointCloud(be, be.select_by_index(target.id, i_t.astype(np.uint32)))
+            if not survivors:
+                return constraints
+            icps = self.cloudRegistration.registerCloudsBatch([s[2] for s in survivors], [s[3] for s in survivors], [s[1] for s in survivors])
+            for (tid, _, src_ov, tgt_ov), icp in zip(survivors, icps):
+                if icp.fitness_ < cfg.minRefinementFitness_:
+                    continue
+                if not self.isRegistrationConsistent(icp.transformation_):
+                    continue
+                info = be.information_matrix_dev(src_ov.id, tgt_ov.id, cfg.maxIcpCorrespondenceDistance_, icp.transformation_)
+                constraints.append(Constraint(sourceToTarget_=np.array(icp.transformation_), sourceSubmapIdx_=src_idx, targetSubmapIdx_=tid,
+                                              informationMatrix_=info, isInformationMatrixValid_=True, isOdometryConstraint_=False,
+                                              timestamp_=timestamp))
+        finally:
+            for _, _, src_ov, tgt_ov in survivors:
+                src_ov.release()
+                if tgt_ov is not None:
+                    tgt_ov.release()
         return constraints

@@ -14,7 +14,7 @@ import math
 import numpy as np
 
 from .adjacency_matrix import AdjacencyMatrix
-from .optimization_problem import applyOptimizedTransforms, buildOdometryConstraint
+from .optimization_problem import applyOptimizedTransforms, buildOdometryConstraint, buildOdometryConstraintsBatch
 from .parameters import MapperParameters
 from .place_recognition import PlaceRecognition
 from .pointcloud import PointCloud
@@ -38,11 +38,22 @@ def _hasConstraint(sourceIdx: int, targetIdx: int, constraints) -> bool:  # cons
     return any(c.sourceSubmapIdx_ == sourceIdx and c.targetSubmapIdx_ == targetIdx for c in constraints)
 
 
-def computeOdometryConstraints(be, submaps: "SubmapCollection", constraints: list, candidates=None) -> None:
+def computeOdometryConstraints(be, submaps: "SubmapCollection", constraints: list, candidates=None, batch: bool = False) -> None:
     """constraint_builders.cpp:92-118.  candidates given: the odometry constraint (parent -> submap) of every candidate but submap 0
     (the form SubmapCollection::computeFeatures uses); None: of every submap 1..N-1 whose pair does not touch the active submap (the
-    form of the loop-closure worker).  Constraints already in `constraints` (same source and target) are not built again."""
+    form of the loop-closure worker).  Constraints already in `constraints` (same source and target) are not built again.
+    batch (a capability beyond the reference, off by default): the pairs are collected first and, with
+    isRefineOdometryConstraintsBetweenSubmaps_, their ICPs run as one batched registration; the constraints appended are the same."""
     params = submaps.getParameters()
+    pairs = []  # batch: the (source, target) pairs in the order the loop below would build them
+
+    def build(source, target):
+        if batch:
+            if (source, target) not in pairs:  # (the sequential form sees its own earlier constraint in `constraints`)
+                pairs.append((source, target))
+        else:
+            constraints.append(buildOdometryConstraint(be, source, target, submaps.submaps_, params))
+
     if candidates is not None:
         for candidate in candidates:
             if candidate.submapId_ < 1:
@@ -50,13 +61,15 @@ def computeOdometryConstraints(be, submaps: "SubmapCollection", constraints: lis
             target = candidate.submapId_
             source = submaps.getSubmap(target).parentId_
             if not _hasConstraint(source, target, constraints):
-                constraints.append(buildOdometryConstraint(be, source, target, submaps.submaps_, params))
-        return
-    active = submaps.getActiveSubmap().id_
-    for target in range(1, submaps.getNumSubmaps()):
-        source = submaps.getSubmap(target).parentId_
-        if not _hasConstraint(source, target, constraints) and source != active and target != active:
-            constraints.append(buildOdometryConstraint(be, source, target, submaps.submaps_, params))
+                build(source, target)
+    else:
+        active = submaps.getActiveSubmap().id_
+        for target in range(1, submaps.getNumSubmaps()):
+            source = submaps.getSubmap(target).parentId_
+            if not _hasConstraint(source, target, constraints) and source != active and target != active:
+                build(source, target)
+    if batch:
+        constraints.extend(buildOdometryConstraintsBatch(be, pairs, submaps.submaps_, params))
 
 
 def getLoopClosureCandidatesIdxs(submaps, adjMatrix: AdjacencyMatrix, lastFinishedSubmapIdx: int, activeSubmapIdx: int,
@@ -299,11 +312,11 @@ class SubmapCollection:
         return True
 
     # -- loop closure (SubmapCollection.cpp:219-267, 284-335)
-    def computeFeatures(self, finishedSubmapIds):
+    def computeFeatures(self, finishedSubmapIds, batch: bool = False):
         for tid in finishedSubmapIds:
             self.submaps_[tid.submapId_].computeFeatures()
             self.loopClosureCandidatesIdxs_.append(tid)
-        computeOdometryConstraints(self.be, self, self.odometryConstraints_, candidates=finishedSubmapIds)
+        computeOdometryConstraints(self.be, self, self.odometryConstraints_, candidates=finishedSubmapIds, batch=batch)
 
     def getLoopClosureCandidatesIdxs(self, lastFinishedSubmapIdx: int) -> list:
         return getLoopClosureCandidatesIdxs(self.submaps_, self.adjacencyMatrix_, lastFinishedSubmapIdx, self.activeSubmapIdx_,
