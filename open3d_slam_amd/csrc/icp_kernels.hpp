@@ -1790,7 +1790,9 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
                                                double* s_U /* [16] */, double* s_T /* [16] */, int* s_go,
                                                unsigned long long* tr = nullptr /* 8 timestamps, development aid */,
                                                int method = O3DS_ICP_POINT_TO_PLANE,
-                                               float* s_margin = nullptr /* [2]: |R - I|_F and |t| of the update (candidate-set margin) */) {
+                                               float* s_margin = nullptr /* [2]: |R - I|_F and |t| of the update (candidate-set margin) */,
+                                               bool fold_only = false /* uniform; the caller has seen iterations >= max_iter in the state: no
+                                               update can be applied (go = 0 below), so wavefront 0 skips the solve whose result nobody reads */) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #define O3DS_TSTAMP(k)                                       \
   do {                                                       \
@@ -1799,7 +1801,7 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
   O3DS_TSTAMP(0);
   const double count = s_rec[kRecCount];
   double tnew = 0.0;
-  if (wv == 0) {
+  if (wv == 0 && !fold_only) {
     if (lane < 16) s_T[lane] = st->T[lane];
     if (lane < 8) s_x[lane] = 0.0;
     lds_wave_sync();
@@ -1887,7 +1889,7 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
     if (lane < 16) st->T[lane] = tnew;
     if (lane == 0) st->iterations += 1;
   }
-  if (s_margin && wv == 2 && lane == 0) {  // how far the update moves a point p: at most |R - I|_F |p| + |t| (an idle wavefront's work)
+  if (s_margin && !fold_only && wv == 2 && lane == 0) {  // how far the update moves a point p: at most |R - I|_F |p| + |t| (an idle wavefront's work)
     double w2 = 0.0, t2 = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -2085,7 +2087,8 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   O3DS_STAMP(1);
   if (!first) {
     icp_step_block(s_out, &s_st, n_src_total, fa.max_iter, fa.rel_fitness, fa.rel_rmse, s_x, s_sc, s_U, s_T, &s_go,
-                   fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 8 : nullptr, fa.pass.method, s_margin);
+                   fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 8 : nullptr, fa.pass.method, s_margin,
+                   /* fold_only: the last launch of a registration that ran out of iterations */ s_st.iterations >= fa.max_iter);
     lds_barrier();
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
