@@ -145,6 +145,10 @@ int o3ds_cloud_size(o3ds_handle h, o3ds_cloud c, size_t* n, int* has_normals);
  * built by the registration that is the fourth against the same index (an index a stream rebuilds every frame never gets one); it
  * changes no result, only how fast the search runs. */
 int o3ds_cloud_index_replica(o3ds_handle h, o3ds_cloud c, size_t* elements);
+/* Whether the cloud is a map in its PERSISTENT form right now (o3ds_map_insert_scan): persistent = 1 or 0.  Never waits,
+ * never folds, changes nothing -- the only way to tell which form a map is in; the form changes no result, only what an insertion costs.
+ * O3DS_ERR_INVALID_ARG for an unknown id. */
+int o3ds_cloud_is_persistent_map(o3ds_handle h, o3ds_cloud c, int* persistent);
 /* What is known of the size without waiting: lower <= n <= upper (equal once the number has arrived).  The reference's emptiness checks
  * (assert_gt(cloud.size(), 0), ScanToMapRegistration.cpp:51-52; preProcessedScan.IsEmpty(), Submap.cpp:41) are decided by the bounds:
  * a VoxelDownSample result whose input had a point inside the volume has lower = 1. */
@@ -545,9 +549,14 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
 /* Submap::insertScan's tail (Submap.cpp:66-75): map += T * scan, voxelizeWithinCroppingVolume(map_voxel_size, map_builder_crop)
  * (helpers.cpp:115-183), and -- max_corr_hint > 0 -- the map's search index for the next registration.  The RESULT is the reference's: the
  * array [points outside the volume in their previous order | one mean per voxel inside it, in voxel-key order], bit for bit in f64
- * storage.  HOW it is kept is the backend's: from its second insertion on a map with an index and without colours stays in a PERSISTENT
- * form (slot arrays + voxel hash + row-paged index) that an insertion updates only where the scan falls -- the call queues
- * eight kernels over the scan and returns, nothing is proportional to the map's size and nothing comes back to the host -- and turns into
+ * storage.  HOW it is kept is the backend's: from its second insertion on a map with an index stays in a PERSISTENT form (slot arrays +
+ * voxel hash + row-paged index; o3ds_cloud_is_persistent_map tells) that an insertion updates only where the scan falls --
+ * the call queues eight kernels over the scan and returns, nothing is proportional to the map's size and nothing comes back to the host.
+ * Colours follow [O3D] PointCloud::operator+= in that form as in the array: (1) coloured map, coloured scan: persistent, every slot
+ * carries its colour (a voxel's: that of its last member in cloud order, see o3ds_cloud_set_colors); (2) uncoloured non-empty map,
+ * coloured scan: persistent, the scan's colours are ignored as += drops them; (3) coloured map, uncoloured scan: the map is folded and
+ * this insertion takes the array form, which drops the map's colours as += does -- later insertions re-enter the persistent form,
+ * uncoloured.  o3ds_cloud_has_colors answers without folding.  The persistent form turns into
  * the array above when somebody asks for it: o3ds_cloud_download*, o3ds_map_carve with another voxel size, o3ds_overlap_indices,
  * o3ds_estimate_normals ON the map, a registration with the map as its SOURCE, any call that reads or rewrites the map as an array
  * (that fold sorts the live points once, O(N log N)).  o3ds_cloud_size answers from the device's counters (live = slots - dead) and

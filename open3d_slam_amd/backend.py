@@ -125,6 +125,7 @@ SIGNATURES = {
     "o3ds_cloud_free": (C.c_int, [_H, _CL]),
     "o3ds_cloud_size": (C.c_int, [_H, _CL, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "o3ds_cloud_index_replica": (C.c_int, [_H, _CL, C.POINTER(C.c_size_t)]),
+    "o3ds_cloud_is_persistent_map": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
     "o3ds_cloud_download": (C.c_int, [_H, _CL, _dp, _dp, C.c_size_t]),
     "o3ds_cloud_set_colors": (C.c_int, [_H, _CL, _dp]),
     "o3ds_cloud_has_colors": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
@@ -424,6 +425,12 @@ class Backend:
         n = C.c_size_t(0)
         self._ck(self.lib.o3ds_cloud_index_replica(self.h, cid, C.byref(n)))
         return int(n.value)
+
+    def is_persistent_map(self, cid: int) -> bool:
+        """whether the cloud is a map in its persistent form right now (never waits, never folds)"""
+        p = C.c_int(0)
+        self._ck(self.lib.o3ds_cloud_is_persistent_map(self.h, cid, C.byref(p)))
+        return bool(p.value)
 
     # -- ICP
     @staticmethod

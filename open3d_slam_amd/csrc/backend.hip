@@ -2036,6 +2036,15 @@ int o3ds_cloud_index_replica(o3ds_handle h, o3ds_cloud id, size_t* elements) {
   return O3DS_OK;
 }
 
+int o3ds_cloud_is_persistent_map(o3ds_handle h, o3ds_cloud id, int* persistent) {
+  CHECK_HANDLE(h);
+  auto it = h->clouds.find(id);  // (not even find_cloud_lazy: nothing is waited for, nothing changes)
+  if (it == h->clouds.end()) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_is_persistent_map: unknown cloud id");
+  if (!persistent) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_is_persistent_map: null output");
+  *persistent = it->second.pm != nullptr;
+  return O3DS_OK;
+}
+
 int o3ds_cloud_size_bound(o3ds_handle h, o3ds_cloud id, size_t* lower, size_t* upper) {
   CHECK_HANDLE(h);
   CloudRec* c = find_cloud_lazy(h, id);
@@ -2153,7 +2162,7 @@ int o3ds_cloud_set_colors(o3ds_handle h, o3ds_cloud id, const double* rgb) {
 
 int o3ds_cloud_has_colors(o3ds_handle h, o3ds_cloud id, int* has_colors) {
   CHECK_HANDLE(h);
-  CloudRec* c = find_cloud(h, id);
+  CloudRec* c = find_cloud_lazy(h, id);  // (known without the cloud's size, and without folding a persistent map)
   if (!c || !has_colors) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_has_colors: bad argument");
   *has_colors = c->col != nullptr;
   return O3DS_OK;
@@ -3784,9 +3793,17 @@ int pm_enter_t(o3ds_handle h, CloudRec& c, double voxel, double max_corr_hint, s
     c.cap = want_cap;
   }
   const size_t cap = c.cap;
+  if (c.col) {  // the colour slots: always a block of their own size (an array's colours are allocated for its points, whatever room pts / nrm have)
+    void* nc = nullptr;
+    HIP_TRY(dev_alloc(h, &nc, sizeof(P4) * cap));
+    HIP_TRY(hipMemcpyAsync(nc, c.col, sizeof(P4) * n, hipMemcpyDeviceToDevice, h->stream));
+    dev_free(h, c.col);
+    c.col = nc;
+  }
   PmDev& d = pm->dev;
   d.pts = c.pts;
   d.nrm = c.nrm;
+  d.col = c.col;
   d.cap = cap;
   PM_ALLOC(d.slot, sizeof(PmSlot) * cap);
   size_t hcap = 1024;
@@ -3949,6 +3966,7 @@ int pm_insert_t(o3ds_handle h, CloudRec& c, const CloudRec& scan, const double T
   PmDev d = pm->dev;
   const size_t ms = scan.n;  // (an upper bound when the scan's size is still in flight)
   const bool has_nrm = c.nrm != nullptr;
+  const P4* scan_col = c.col ? (const P4*)scan.col : nullptr;  // (an uncoloured map ignores a scan's colours, as operator+= does)
   const int t_now = pm->t + 1;
   // scratch: the voxel table of VoxelDownSample, the chained scan's tiles
   size_t tcap = 1024;
@@ -4008,10 +4026,10 @@ int pm_insert_t(o3ds_handle h, CloudRec& c, const CloudRec& scan, const double T
                                                             placed, placed_nrm, lead_slot, run_next, run_len);
   vox_order_kernel<<<(unsigned int)n_tiles, kBlock, 0, h->stream>>>(lead_slot, n_scan, t, h->d_tiles, h->d_ticket, h->ticket_base, h->scan_gen, order, groups_pub);
   h->ticket_base += (unsigned int)n_tiles;
-  pm_group_kernel<P4><<<grid_for(ms), kBlock, 0, h->stream>>>(d, groups, order, run_next, run_len, starts, piece, placed, placed_nrm, t, crop, t_now, group_key);
+  pm_group_kernel<P4><<<grid_for(ms), kBlock, 0, h->stream>>>(d, groups, order, run_next, run_len, starts, piece, placed, placed_nrm, scan_col, t, crop, t_now, group_key);
   h->voxtab_clean = true;
-  pm_merge_kernel<P4><<<512, 64, 0, h->stream>>>(d, piece, run_next, run_len, placed, placed_nrm, group_key, crop, t_now);
-  pm_misc_kernel<P4><<<256, kBlock, 0, h->stream>>>(d, placed, placed_nrm, crop, t_now);
+  pm_merge_kernel<P4><<<512, 64, 0, h->stream>>>(d, piece, run_next, run_len, placed, placed_nrm, scan_col, group_key, crop, t_now);
+  pm_misc_kernel<P4><<<256, kBlock, 0, h->stream>>>(d, placed, placed_nrm, scan_col, crop, t_now);
   const unsigned int row_blocks = (unsigned int)std::min<size_t>(std::max<size_t>(ms / 8, 64), 2048);
   pm_rows_kernel<P4><<<row_blocks, kBlock, sizeof(int) * 3 * (size_t)(d.grid.nx + 1), h->stream>>>(d);
   pm_place_new_kernel<P4><<<grid_for(ms), kBlock, 0, h->stream>>>(d);
@@ -4061,22 +4079,25 @@ int pm_exit_t(o3ds_handle h, CloudRec& c) {
   rc = read_back(h, {{&n_pass, d_np, sizeof(n_pass)}});
   if (rc) return rc;
   const size_t room = live + std::max<size_t>(live / 4, (size_t)1 << 18);
-  void *np = nullptr, *nn = nullptr;
+  void *np = nullptr, *nn = nullptr, *nc = nullptr;
   if (live > 0) {
     HIP_TRY(dev_alloc(h, &np, sizeof(P4) * room));
-    if (c.nrm && dev_alloc(h, &nn, sizeof(P4) * room) != hipSuccess) {
+    if ((c.nrm && dev_alloc(h, &nn, sizeof(P4) * room) != hipSuccess) || (c.col && dev_alloc(h, &nc, sizeof(P4) * live) != hipSuccess)) {
       dev_free(h, np);
+      if (nn) dev_free(h, nn);
       return fail(h, O3DS_ERR_OOM, "persistent map: out of device memory");
     }
-    pm_permute_kernel<P4><<<grid_for(live), kBlock, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, v0, live, (P4*)np, (P4*)nn);
+    pm_permute_kernel<P4><<<grid_for(live), kBlock, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, (const P4*)c.col, v0, live, (P4*)np, (P4*)nn, (P4*)nc);
     HIP_TRY(hipGetLastError());
   }
   pm_release(h, c);
   free_index(h, c);
   free_points(h, c);
   if (c.nrm) dev_free(h, c.nrm);
+  if (c.col) dev_free(h, c.col);
   c.pts = np;
   c.nrm = nn;
+  c.col = nc;
   c.n = live;
   c.cap = live > 0 ? room : 0;
   c.vox_first = (long long)n_pass;
@@ -4465,10 +4486,12 @@ int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const d
   if (m->precision != s->precision) return fail(h, O3DS_ERR_INVALID_ARG, "map_insert_scan: precision mismatch");
   int rc = O3DS_OK;
   // ---- the persistent form (map_kernels.hpp): work proportional to the scan.  It takes a map with a known layout [pass-through block | voxel
-  // block in key order] -- what the first insertion into a map (below) or a fold leaves --, a search index being wanted, no colours, and map
-  // and scan agreeing on normals ([O3D] operator+= drops the map's normals otherwise).
+  // block in key order] -- what the first insertion into a map (below) or a fold leaves --, a search index being wanted, and map and scan
+  // agreeing on normals ([O3D] operator+= drops the map's normals otherwise).  Colours follow operator+= too (append_t): a coloured map takes
+  // a coloured scan with its colours, an uncoloured one takes any scan and ignores its colours, and an uncoloured scan into a coloured map
+  // drops the map's colours -- the map is folded and takes the array form for that insertion (later ones re-enter, uncoloured).
   static const bool no_pm = ab_getenv("O3DS_NO_PERSISTENT_MAP") != nullptr;  // A/B and the bitwise tests: the array form at every insertion
-  const bool pm_ok = !no_pm && map_voxel_size > 0.0 && max_corr_hint > 0.0 && !m->col && !s->col && m->n > 0 && (m->nrm != nullptr) == (s->nrm != nullptr) &&
+  const bool pm_ok = !no_pm && map_voxel_size > 0.0 && max_corr_hint > 0.0 && (!m->col || s->col) && m->n > 0 && (m->nrm != nullptr) == (s->nrm != nullptr) &&
                      m->n + s->n < ((size_t)1 << 30);
   const CropDev cd = to_dev(map_builder_crop);
   CloudRec placed;

@@ -6,7 +6,7 @@
 // rebuild of the search index: ~230 us per scan at 1 M points, linear in N.  But an insertion CHANGES only what the scan touches.  A voxel
 // that holds one point and receives none keeps it: mean of one point p is p / 1 = p exactly (only its normal is re-normalised, see below).
 // So the map is kept as
-//   * slot arrays      pts / nrm [cap]: a point lives in one slot from its creation to its death; new points are appended;
+//   * slot arrays      pts / nrm / col [cap]: a point lives in one slot from its creation to its death; new points are appended;
 //   * a voxel hash     key floor(p * (1 / v)) (VoxelHashMap.hpp:47-50) -> chain of the slots whose point has that key.  Nearly every
 //                      chain has one member; two points share a voxel only if they were never inside a volume together (points outside
 //                      pass through unmerged) or a mean was rounded across a voxel face;
@@ -28,6 +28,11 @@
 // reference re-normalises EVERY point inside the volume at EVERY insertion.  A slot whose normal is not yet a fixed point is kept on a list
 // and re-normalised at each insertion that has it inside the volume until it is; all others need no work.  (2) A voxel with several old
 // members sums them in map order, which for the persistent form means the order of pm_view_key (the same function the view uses).
+// (3) Colours.  AccumulatedPoint::AddPoint ASSIGNS the colour (helpers.cpp:40-42), so a voxel mean shows the colour of the LAST of its members
+// in that same order -- the last scan point if the voxel received any, the last old member otherwise -- and there is no arithmetic on
+// colours.  The walk that sums a voxel's members remembers where the last one's colour is (PmAcc::col) and pm_store copies it: one load and
+// one store per written slot.  A slot that nothing wrote keeps its colour like its point; the scan's colours are read where the scan has
+// them (placing a scan copies them unchanged, so no placed copy is made); the paged index carries none.
 #pragma once
 #include "cloud_kernels.hpp"
 #include "common.hpp"
@@ -61,6 +66,7 @@ struct alignas(16) PmHash {
 struct PmDev {
   void* pts;  // P4[cap]
   void* nrm;  // P4[cap] or null
+  void* col;  // P4[cap] or null: the colour of every slot (not in the paged index: the registration never reads colours)
   struct PmSlot* slot;       // [cap] per-slot record (one cache line per slot: as separate arrays an insertion touched five lines per voxel)
   size_t cap;
   // voxel hash (open addressing, never deleted from: a chain may be empty)
@@ -369,7 +375,7 @@ __global__ __launch_bounds__(kBlock) void pm_hash_init_kernel(PmHash* __restrict
     hh[i] = e;
   }
 }
-// per slot of the base [pass block | voxel block in key order]: history, hash chain, settled or not
+// per slot of the base [pass block | voxel block in key order]: history, hash chain, settled or not (its colour is the array's: nothing to do)
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_enter_kernel(PmDev m, int n) {
   int* err = m.counters + kPmError;
@@ -535,12 +541,13 @@ __device__ __forceinline__ void pm_row_push(const PmDev& m, int s, unsigned long
 // the mean of a voxel's members written where it belongs: point, normal, history, search index (in place: the mean of points of one voxel
 // lies in that voxel, hence in the same index cell), settled or not; `fresh`: the slot is new (its index entry comes with its row)
 template <typename P4>
-__device__ __forceinline__ void pm_store(const PmDev& m, int s, const P4& op, const P4& on, bool has_nrm, int t, unsigned long long key, bool fresh,
-                                         int known_pos = -1) {
+__device__ __forceinline__ void pm_store(const PmDev& m, int s, const P4& op, const P4& on, bool has_nrm, const P4& oc, bool has_col, int t,
+                                         unsigned long long key, bool fresh, int known_pos = -1) {
   P4 o = op;
   o.i = (typename Scalar<P4>::index)s;
   ((P4*)m.pts)[s] = o;
   if (has_nrm) ((P4*)m.nrm)[s] = on;
+  if (has_col) ((P4*)m.col)[s] = oc;
   m.slot[s].stamp = t;
   m.slot[s].okey = key;
   m.slot[s].out_checked = -1;  // (whatever pm_view_key remembered of the slot's history belonged to the point it held before)
@@ -571,8 +578,11 @@ __device__ __forceinline__ void pm_kill(const PmDev& m, int s) {
 struct PmAcc {
   double sx = 0, sy = 0, sz = 0, nx = 0, ny = 0, nz = 0;
   int cnt = 0;
+  const void* col = nullptr;  // color_ is ASSIGNED by every AddPoint (helpers.cpp:40-42), never summed: the last member's stays.  Kept as its
+                              // address (null: the map has no colours) -- one load per voxel, by mean(), not one per member
   template <typename P4>
-  __device__ __forceinline__ void add(const P4& p, bool has_n, const P4& nq) {
+  __device__ __forceinline__ void add(const P4& p, bool has_n, const P4& nq, const P4* c) {
+    col = c;
     sx += (double)p.x;
     sy += (double)p.y;
     sz += (double)p.z;
@@ -587,8 +597,12 @@ struct PmAcc {
     ++cnt;
   }
   template <typename P4>
-  __device__ __forceinline__ void mean(P4* op, P4* on) {
+  __device__ __forceinline__ void mean(P4* op, P4* on, P4* oc) {
     using R = typename Scalar<P4>::type;
+    if (col) {  // untouched (field by field: an aggregate copy through a conditional branch goes through scratch memory)
+      const P4* c = (const P4*)col;
+      oc->x = c->x, oc->y = c->y, oc->z = c->z, oc->i = c->i;
+    }
     const double c = (double)cnt;
     op->x = (R)(sx / c);
     op->y = (R)(sy / c);
@@ -616,11 +630,12 @@ __device__ __forceinline__ void pm_check_face(const PmDev& m, int s, const P4& o
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_group_kernel(PmDev m, CountRef g_in, const int* __restrict__ order, const int* __restrict__ run_next,
                                                           const int* __restrict__ run_len, uint32_t* __restrict__ starts, int2* __restrict__ piece,
-                                                          const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, VoxTable t, CropDev crop,
-                                                          int t_now, unsigned long long* __restrict__ group_key) {
+                                                          const P4* __restrict__ placed, const P4* __restrict__ placed_nrm,
+                                                          const P4* __restrict__ scan_col /* the scan's colours (placing copies them unchanged); null: the map has none */,
+                                                          VoxTable t, CropDev crop, int t_now, unsigned long long* __restrict__ group_key) {
   const size_t g = count_of(g_in);
   const int lane = threadIdx.x & 63;
-  const bool has_nrm = m.nrm != nullptr;
+  const bool has_nrm = m.nrm != nullptr, has_col = m.col != nullptr;
   for (size_t r0 = (size_t)blockIdx.x * kBlock; r0 < g; r0 += (size_t)gridDim.x * kBlock) {  // whole wavefronts iterate together
     const size_t r = r0 + threadIdx.x;
     const bool have = r < g;
@@ -701,7 +716,7 @@ __global__ __launch_bounds__(kBlock) void pm_group_kernel(PmDev m, CountRef g_in
       continue;
     }
     PmAcc acc;
-    if (n_old_in == 1) acc.add(old_p, has_nrm, old_n);
+    if (n_old_in == 1) acc.add(old_p, has_nrm, old_n, has_col ? (const P4*)m.col + old_slot : nullptr);
     int prev = -1;
     for (int j = 0; j < k; ++j) {
       const int st = kk ? (int)starts[b + j] : next_run(run_next, head, prev);
@@ -717,11 +732,11 @@ __global__ __launch_bounds__(kBlock) void pm_group_kernel(PmDev m, CountRef g_in
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (q + u < len) acc.add(pp[u], has_nrm, nn[u]);
+          if (q + u < len) acc.add(pp[u], has_nrm, nn[u], has_col ? scan_col + (st + q + u) : nullptr);
       }
     }
-    P4 op, on;
-    acc.mean(&op, &on);
+    P4 op, on, oc{};
+    acc.mean(&op, &on, &oc);  // (the colour: the voxel's last scan point's)
     int s = old_slot;
     const bool fresh = s < 0;
     if (fresh) {
@@ -731,7 +746,7 @@ __global__ __launch_bounds__(kBlock) void pm_group_kernel(PmDev m, CountRef g_in
       m.h[e].head = s;
       if (n_live > 0 && !(atomicOr(&m.h[e].info, 1u) & 1u)) pm_push64(m.multi[0], m.counters + kPmMultiOut, m.list_cap, key, m.counters + kPmError);
     }
-    pm_store(m, s, op, on, has_nrm, t_now, key, fresh);
+    pm_store(m, s, op, on, has_nrm, oc, has_col, t_now, key, fresh);
     if (fresh) pm_row_push(m, s, pm_key(op, m.inv_voxel));  // (the cell of where the mean really is: pm_check_face re-hashes it if that is another voxel)
     pm_check_face(m, s, op, key);
   }
@@ -807,14 +822,14 @@ __device__ __forceinline__ int pm_gather_old(const PmDev& m, unsigned int e, con
 template <typename P4>
 __device__ __forceinline__ void pm_merge_old(const PmDev& m, unsigned int e, unsigned long long key, const PmOld& o, int n_old, int group /* -1: no scan points */,
                                              const int2* __restrict__ piece, const int* __restrict__ run_next, const int* __restrict__ run_len,
-                                             const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, int t_now) {
-  const bool has_nrm = m.nrm != nullptr;
+                                             const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, const P4* __restrict__ scan_col, int t_now) {
+  const bool has_nrm = m.nrm != nullptr, has_col = m.col != nullptr;
   PmAcc acc;
   for (int j = 0; j < n_old; ++j) {
     const P4 p = ((const P4*)m.pts)[o.slot[j]];
     P4 q{};
     if (has_nrm) q = ((const P4*)m.nrm)[o.slot[j]];
-    acc.add(p, has_nrm, q);
+    acc.add(p, has_nrm, q, has_col ? (const P4*)m.col + o.slot[j] : nullptr);
   }
   if (group >= 0) {
     const int2 pc = piece[group];  // {head of the run list, number of runs}
@@ -826,17 +841,17 @@ __device__ __forceinline__ void pm_merge_old(const PmDev& m, unsigned int e, uns
       for (int q = 0; q < len; ++q) {
         P4 nq{};
         if (has_nrm) nq = placed_nrm[st + q];
-        acc.add(placed[st + q], has_nrm, nq);
+        acc.add(placed[st + q], has_nrm, nq, has_col ? scan_col + (st + q) : nullptr);
       }
     }
   }
-  P4 op, on;
-  acc.mean(&op, &on);
+  P4 op, on, oc{};
+  acc.mean(&op, &on, &oc);  // (the colour of the last member added: the last scan point if the voxel received any, else the last old member)
   for (int j = 1; j < n_old; ++j) {
     pm_unlink(m, e, o.slot[j]);
     pm_kill<P4>(m, o.slot[j]);
   }
-  pm_store(m, o.slot[0], op, on, has_nrm, t_now, key, false);
+  pm_store(m, o.slot[0], op, on, has_nrm, oc, has_col, t_now, key, false);
   pm_check_face(m, o.slot[0], op, key);
 }
 // the same for a voxel with more old members inside the volume than the sorted list holds (a map that entered with many raw points per
@@ -844,8 +859,8 @@ __device__ __forceinline__ void pm_merge_old(const PmDev& m, unsigned int e, uns
 template <typename P4>
 __device__ __forceinline__ void pm_merge_many(const PmDev& m, unsigned int e, unsigned long long key, const CropDev& crop, int group,
                                               const int2* __restrict__ piece, const int* __restrict__ run_next, const int* __restrict__ run_len,
-                                              const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, int t_now) {
-  const bool has_nrm = m.nrm != nullptr;
+                                              const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, const P4* __restrict__ scan_col, int t_now) {
+  const bool has_nrm = m.nrm != nullptr, has_col = m.col != nullptr;
   PmAcc acc;
   unsigned long long last_hi = 0, last_lo = 0;
   int first = -1;
@@ -865,7 +880,7 @@ __device__ __forceinline__ void pm_merge_many(const PmDev& m, unsigned int e, un
     const P4 p = ((const P4*)m.pts)[best];
     P4 q{};
     if (has_nrm) q = ((const P4*)m.nrm)[best];
-    acc.add(p, has_nrm, q);
+    acc.add(p, has_nrm, q, has_col ? (const P4*)m.col + best : nullptr);
     if (first == -1) first = best;
     last_hi = bh, last_lo = bl;
   }
@@ -880,12 +895,12 @@ __device__ __forceinline__ void pm_merge_many(const PmDev& m, unsigned int e, un
       for (int q = 0; q < len; ++q) {
         P4 nq{};
         if (has_nrm) nq = placed_nrm[st + q];
-        acc.add(placed[st + q], has_nrm, nq);
+        acc.add(placed[st + q], has_nrm, nq, has_col ? scan_col + (st + q) : nullptr);
       }
     }
   }
-  P4 op, on;
-  acc.mean(&op, &on);
+  P4 op, on, oc{};
+  acc.mean(&op, &on, &oc);  // (the colour of the last member added: the last scan point if the voxel received any, else the last old member)
   for (int s = m.h[e].head; s != -1;) {  // the other members inside the volume die
     const int nxt = m.slot[s].hnext;
     const P4 p = ((const P4*)m.pts)[s];
@@ -895,7 +910,7 @@ __device__ __forceinline__ void pm_merge_many(const PmDev& m, unsigned int e, un
     }
     s = nxt;
   }
-  pm_store(m, first, op, on, has_nrm, t_now, key, false);
+  pm_store(m, first, op, on, has_nrm, oc, has_col, t_now, key, false);
   pm_check_face(m, first, op, key);
 }
 
@@ -984,9 +999,9 @@ __device__ __forceinline__ int pm_nodes_order(const PmDev& m, const PmNodes& nd,
 template <typename P4>
 __device__ __forceinline__ void pm_nodes_finish(const PmDev& m, unsigned int e, unsigned long long key, PmNodes& nd, int cnt, PmOld& o /* LDS */, int n, int np,
                                                 int group, const int2* __restrict__ piece, const int* __restrict__ run_next,
-                                                const int* __restrict__ run_len, const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, int t_now) {
+                                                const int* __restrict__ run_len, const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, const P4* __restrict__ scan_col, int t_now) {
   using R = typename Scalar<P4>::type;
-  const bool has_nrm = m.nrm != nullptr;
+  const bool has_nrm = m.nrm != nullptr, has_col = m.col != nullptr;
   for (int a = 1; a < np; ++a) {  // the pass-through members by their histories (insertion sort of the first np entries)
     const unsigned long long h = o.hi[a], l = o.lo[a];
     const int sl = o.slot[a];
@@ -1008,7 +1023,7 @@ __device__ __forceinline__ void pm_nodes_finish(const PmDev& m, unsigned int e, 
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      if (j0 + u < n) acc.add(pp[u], has_nrm, qq[u]);
+      if (j0 + u < n) acc.add(pp[u], has_nrm, qq[u], has_col ? (const P4*)m.col + nd.n[o.slot[j0 + u]].s : nullptr);
   }
   if (group >= 0) {
     const int2 pc = piece[group];  // {head of the run list, number of runs}
@@ -1020,12 +1035,12 @@ __device__ __forceinline__ void pm_nodes_finish(const PmDev& m, unsigned int e, 
       for (int q = 0; q < len; ++q) {
         P4 nq{};
         if (has_nrm) nq = placed_nrm[st + q];
-        acc.add(placed[st + q], has_nrm, nq);
+        acc.add(placed[st + q], has_nrm, nq, has_col ? scan_col + (st + q) : nullptr);
       }
     }
   }
-  P4 op, on;
-  acc.mean(&op, &on);
+  P4 op, on, oc{};
+  acc.mean(&op, &on, &oc);  // (the colour of the last member added: the last scan point if the voxel received any, else the last old member)
   P4 far;  // (pm_kill's sentinel)
   far.x = far.y = far.z = sizeof(R) == 4 ? (R)3.0e38f : (R)1.0e300;
   far.i = (typename Scalar<P4>::index)0x7fffffff;
@@ -1055,13 +1070,13 @@ __device__ __forceinline__ void pm_nodes_finish(const PmDev& m, unsigned int e, 
   }
   if (gap) m.slot[prev_s].hnext = -1;  // (the member that stays is never the one that went: prev_s is a slot)
   const PmNode keep = nd.n[o.slot[0]];
-  pm_store(m, keep.s, op, on, has_nrm, t_now, key, false, keep.pos);
+  pm_store(m, keep.s, op, on, has_nrm, oc, has_col, t_now, key, false, keep.pos);
   pm_check_face(m, keep.s, op, key);
 }
 
 template <typename P4>
 __global__ __launch_bounds__(64) void pm_merge_kernel(PmDev m, const int2* __restrict__ piece, const int* __restrict__ run_next, const int* __restrict__ run_len,
-                                                      const P4* __restrict__ placed, const P4* __restrict__ placed_nrm,
+                                                      const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, const P4* __restrict__ scan_col,
                                                       const unsigned long long* __restrict__ group_key /* [groups] key of group r */, CropDev crop, int t_now) {
   __shared__ PmOld s_old[64];
   __shared__ PmNodes s_nodes[64];
@@ -1088,9 +1103,9 @@ __global__ __launch_bounds__(64) void pm_merge_kernel(PmDev m, const int2* __res
       } else {  // a chain longer than the table
         const int n_old = pm_gather_old<P4>(m, e, crop, t_now, o);
         if (n_old > kPmMaxOld)
-          pm_merge_many<P4>(m, e, key, crop, group, piece, run_next, run_len, placed, placed_nrm, t_now);
+          pm_merge_many<P4>(m, e, key, crop, group, piece, run_next, run_len, placed, placed_nrm, scan_col, t_now);
         else
-          pm_merge_old<P4>(m, e, key, o, n_old, group, piece, run_next, run_len, placed, placed_nrm, t_now);
+          pm_merge_old<P4>(m, e, key, o, n_old, group, piece, run_next, run_len, placed, placed_nrm, scan_col, t_now);
       }
     } else if (i < n_complex + n_multi) {
       // a voxel on the multi list.  One the scan touched has been dealt with: its group saw the whole chain (a complex group of this very
@@ -1124,9 +1139,9 @@ __global__ __launch_bounds__(64) void pm_merge_kernel(PmDev m, const int2* __res
             if (!touched && inside > 1) {
               const int n_old = pm_gather_old<P4>(m, e, crop, t_now, o);
               if (n_old > kPmMaxOld)
-                pm_merge_many<P4>(m, e, key, crop, -1, piece, run_next, run_len, placed, placed_nrm, t_now);
+                pm_merge_many<P4>(m, e, key, crop, -1, piece, run_next, run_len, placed, placed_nrm, scan_col, t_now);
               else if (n_old > 1)
-                pm_merge_old<P4>(m, e, key, o, n_old, -1, piece, run_next, run_len, placed, placed_nrm, t_now);
+                pm_merge_old<P4>(m, e, key, o, n_old, -1, piece, run_next, run_len, placed, placed_nrm, scan_col, t_now);
               live -= inside - 1;
             }
           }
@@ -1143,7 +1158,7 @@ __global__ __launch_bounds__(64) void pm_merge_kernel(PmDev m, const int2* __res
     }
     // (c) per lane again
     if (merge) {
-      pm_nodes_finish<P4>(m, e, key, nd, cnt, o, n, np, group, piece, run_next, run_len, placed, placed_nrm, t_now);
+      pm_nodes_finish<P4>(m, e, key, nd, cnt, o, n, np, group, piece, run_next, run_len, placed, placed_nrm, scan_col, t_now);
       live -= inside - 1;
     }
     if (listed && live <= 1) {  // settled: off the list
@@ -1159,7 +1174,8 @@ __global__ __launch_bounds__(64) void pm_merge_kernel(PmDev m, const int2* __res
 // through, i.e. join the map as they were placed) and the means that were rounded across a voxel face (chain of the old key -> chain of
 // the key they have now; the index entry of an old slot is killed and comes back with the rows, a new slot is on its row's list already).
 template <typename P4>
-__global__ __launch_bounds__(kBlock) void pm_misc_kernel(PmDev m, const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, CropDev crop, int t_now) {
+__global__ __launch_bounds__(kBlock) void pm_misc_kernel(PmDev m, const P4* __restrict__ placed, const P4* __restrict__ placed_nrm, const P4* __restrict__ scan_col,
+                                                     CropDev crop, int t_now) {
   int* err = m.counters + kPmError;
   const bool has_nrm = m.nrm != nullptr;
   const int cap = m.list_cap;
@@ -1196,6 +1212,7 @@ __global__ __launch_bounds__(kBlock) void pm_misc_kernel(PmDev m, const P4* __re
       on = placed_nrm[si];
       ((P4*)m.nrm)[s] = on;
     }
+    if (m.col) ((P4*)m.col)[s] = scan_col[si];  // (it passes through with its colour, helpers.cpp:156-162)
     m.slot[s].stamp = t_now;
     m.slot[s].okey = kPmRaw | (unsigned long long)si;
     m.slot[s].out_checked = -1;
@@ -1556,13 +1573,15 @@ __global__ __launch_bounds__(kBlock) void pm_gather_u64_kernel(const unsigned lo
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) out[i] = in[idx[i]];
 }
 template <typename P4>
-__global__ __launch_bounds__(kBlock) void pm_permute_kernel(const P4* __restrict__ pts, const P4* __restrict__ nrm, const uint32_t* __restrict__ idx, size_t n,
-                                                            P4* __restrict__ out_pts, P4* __restrict__ out_nrm) {
+__global__ __launch_bounds__(kBlock) void pm_permute_kernel(const P4* __restrict__ pts, const P4* __restrict__ nrm, const P4* __restrict__ col,
+                                                            const uint32_t* __restrict__ idx, size_t n, P4* __restrict__ out_pts, P4* __restrict__ out_nrm,
+                                                            P4* __restrict__ out_col) {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     P4 p = pts[idx[i]];
     p.i = (typename Scalar<P4>::index)i;
     out_pts[i] = p;
     if (nrm) out_nrm[i] = nrm[idx[i]];
+    if (col) out_col[i] = col[idx[i]];
   }
 }
 
