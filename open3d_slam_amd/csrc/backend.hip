@@ -1568,15 +1568,17 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   return O3DS_OK;
 }
 
+void state_result(const IcpStateDev& s, o3ds_icp_result* out) {
+  memcpy(out->transformation, s.T, sizeof(double) * 16);
+  out->fitness = s.fitness;
+  out->inlier_rmse = s.rmse;
+  out->iterations = s.iterations;
+  out->converged = s.converged;
+  out->n_corr = s.n_corr;
+}
+
 void copy_result(o3ds_handle h, o3ds_icp_result* out) {
-  if (out) {
-    memcpy(out->transformation, h->h_state->T, sizeof(double) * 16);
-    out->fitness = h->h_state->fitness;
-    out->inlier_rmse = h->h_state->rmse;
-    out->iterations = h->h_state->iterations;
-    out->converged = h->h_state->converged;
-    out->n_corr = h->h_state->n_corr;
-  }
+  if (out) state_result(*h->h_state, out);
 }
 
 int read_state(o3ds_handle h, o3ds_icp_result* out, const IcpStateDev* d_from = nullptr) {
@@ -1640,21 +1642,45 @@ int with_uploaded_clouds(o3ds_handle h, const double* src_xyz, const double* src
   return rc;
 }
 
-// the host loop of the two-launch forms: queue_pass() queues one correspondence pass and its one-workgroup tail.  The device loop
-// terminates itself (done flag); the host only looks between chunks of queued passes
-template <typename F>
-int two_launch_loop(o3ds_handle h, int total_passes, o3ds_icp_result* out, F&& queue_pass) {
+// the host loop of the two-launch forms: queue_pass() queues one correspondence pass and its tail.  The device loops terminate
+// themselves (done flags); the host only looks between chunks of queued passes -- after 12 passes, then every 8 -- with look(&done),
+// which reads the state(s) back and answers whether every loop has terminated
+template <typename L, typename F>
+int two_launch_loop(o3ds_handle h, int total_passes, L&& look, F&& queue_pass) {
   int launched = 0;
   while (launched < total_passes) {
     const int chunk = std::min(total_passes - launched, launched == 0 ? 12 : 8);
     for (int k = 0; k < chunk; ++k) queue_pass();
     launched += chunk;
     HIP_TRY(hipGetLastError());
-    const int rc = read_state(h, out);
-    if (rc) return rc;
-    if (h->h_state->done) break;
+    bool done = false;
+    const int rc = look(&done);
+    if (rc || done) return rc;
   }
   return O3DS_OK;
+}
+
+// the look of the forms with one state, the handle's: into h->h_state and, as a result, into out
+auto look_at_session_state(o3ds_handle h, o3ds_icp_result* out) {
+  return [h, out](bool* done) {
+    const int rc = read_state(h, out);
+    *done = h->h_state->done;
+    return rc;
+  };
+}
+
+// one pair through o3ds_icp_register_dev from inside another entry point (a list of one is the existing call, bit for bit): a function
+// armed with o3ds_icp_overlap_next is put aside for the call and stays armed
+int register_one_pair(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* target_crop, const double init[16],
+                      const o3ds_icp_params* params, o3ds_icp_result* out) {
+  const o3ds_overlap_fn fn = h->overlap_fn;
+  void* const arg = h->overlap_arg;
+  h->overlap_fn = nullptr;
+  h->overlap_arg = nullptr;
+  const int rc = o3ds_icp_register_dev(h, source, target, target_crop, init, params, out);
+  h->overlap_fn = fn;
+  h->overlap_arg = arg;
+  return rc;
 }
 
 }  // namespace
@@ -2565,7 +2591,7 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
   }
   const int nb = pass_blocks(h, a.count);
   const int total_passes = params->max_iteration + 1;  // max_iter updates need max_iter+1 correspondence passes
-  return two_launch_loop(h, total_passes, out, [&] {
+  return two_launch_loop(h, total_passes, look_at_session_state(h, out), [&] {
     launch_accumulate(h, a, nb);
     icp_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, (unsigned long long)a.count,
                                                           params->max_iteration, params->relative_fitness, params->relative_rmse,

@@ -28,34 +28,6 @@ void launch_batch_accumulate(o3ds_handle h, int precision, const IcpBatchArgs& b
   DISPATCH(precision, launch_batch_accumulate_t, h, ba, nblocks, crop, gicp);
 }
 
-void batch_result(const IcpStateDev& s, o3ds_icp_result* out) {
-  memcpy(out->transformation, s.T, sizeof(double) * 16);
-  out->fitness = s.fitness;
-  out->inlier_rmse = s.rmse;
-  out->iterations = s.iterations;
-  out->converged = s.converged;
-  out->n_corr = s.n_corr;
-}
-
-// the host loop of the two-launch forms (two_launch_loop) over a table of states: the device loops terminate themselves entry by
-// entry (done flags); the host looks at all of them between chunks of queued passes -- after 12 passes, then every 8
-template <typename F>
-int batch_two_launch_loop(o3ds_handle h, int total_passes, const IcpStateDev* d_states, std::vector<IcpStateDev>& states, F&& queue_pass) {
-  int launched = 0;
-  while (launched < total_passes) {
-    const int chunk = std::min(total_passes - launched, launched == 0 ? 12 : 8);
-    for (int k = 0; k < chunk; ++k) queue_pass();
-    launched += chunk;
-    HIP_TRY(hipGetLastError());
-    const int rc = read_back(h, {{states.data(), d_states, sizeof(IcpStateDev) * states.size()}});
-    if (rc) return rc;
-    bool all_done = true;
-    for (const IcpStateDev& s : states) all_done = all_done && s.done;
-    if (all_done) break;
-  }
-  return O3DS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,15 +62,9 @@ int o3ds_icp_register_batch(o3ds_handle h, const o3ds_icp_batch_entry* entries, 
     if (!empty[k] && !t->nrm && params->method != O3DS_ICP_POINT_TO_POINT)
       return fail(h, O3DS_ERR_INVALID_ARG, "icp_register_batch: entry " + std::to_string(k) + ": target has no normals (the estimator needs them)");
   }
-  if (n_entries == 1) {  // the existing call, bit for bit; a function armed with o3ds_icp_overlap_next stays armed
-    const o3ds_overlap_fn fn = h->overlap_fn;
-    void* const arg = h->overlap_arg;
-    h->overlap_fn = nullptr;
-    h->overlap_arg = nullptr;
-    status[0] = o3ds_icp_register_dev(h, entries[0].source, entries[0].target, entries[0].target_crop, entries[0].init, params, &out[0]);
+  if (n_entries == 1) {
+    status[0] = register_one_pair(h, entries[0].source, entries[0].target, entries[0].target_crop, entries[0].init, params, &out[0]);
     if (status[0]) memset(&out[0], 0, sizeof(o3ds_icp_result));
-    h->overlap_fn = fn;
-    h->overlap_arg = arg;
     return O3DS_OK;
   }
   // ---- capacity: one batch of kIcpQ queries per workgroup (the partition of the fused loop), one partial row per workgroup
@@ -180,13 +146,18 @@ int o3ds_icp_register_batch(o3ds_handle h, const o3ds_icp_batch_entry* entries, 
   ba.n_entries = (int)n_live;
   const bool gicp = params->method == O3DS_ICP_GENERALIZED;
   const int total_passes = params->max_iteration + 1;  // max_iter updates need max_iter + 1 correspondence passes
-  rc = batch_two_launch_loop(h, total_passes, d_states, states, [&] {
+  const auto look = [&](bool* done) {  // all states in one pinned copy; done: every entry's loop has terminated
+    const int rb = read_back(h, {{states.data(), d_states, sizeof(IcpStateDev) * n_live}});
+    *done = std::all_of(states.begin(), states.end(), [](const IcpStateDev& s) { return s.done != 0; });
+    return rb;
+  };
+  rc = two_launch_loop(h, total_passes, look, [&] {
     launch_batch_accumulate(h, precision, ba, total_blocks, any_crop, gicp);
     icp_batch_reduce_update_kernel<<<(int)n_live, kUpdBlock, 0, h->stream>>>(ba, params->max_iteration, params->relative_fitness, params->relative_rmse,
                                                                             params->method);
   });
   if (rc) return rc;
-  for (size_t s = 0; s < n_live; ++s) batch_result(states[s], &out[entry_of[s]]);
+  for (size_t s = 0; s < n_live; ++s) state_result(states[s], &out[entry_of[s]]);
   return O3DS_OK;
 }
 

@@ -60,16 +60,7 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
     if (!t->nrm && params->method != O3DS_ICP_POINT_TO_POINT)
       return fail(h, O3DS_ERR_INVALID_ARG, "icp_register_multi: target " + std::to_string(k) + " has no normals (the estimator needs them)");
   }
-  if (n_targets == 1) {  // the existing call, bit for bit; a function armed with o3ds_icp_overlap_next stays armed
-    const o3ds_overlap_fn fn = h->overlap_fn;
-    void* const arg = h->overlap_arg;
-    h->overlap_fn = nullptr;
-    h->overlap_arg = nullptr;
-    const int rc1 = o3ds_icp_register_dev(h, source, targets[0], target_crop, init, params, out);
-    h->overlap_fn = fn;
-    h->overlap_arg = arg;
-    return rc1;
-  }
+  if (n_targets == 1) return register_one_pair(h, source, targets[0], target_crop, init, params, out);
   if (n_slots == 0) return fail(h, O3DS_ERR_EMPTY, "icp: empty target (map patch size is zero)");
   const bool joint = form == O3DS_MULTI_JOINT;
   // ---- capacity: one batch of kIcpQ queries per workgroup (the partition of the fused loop), one partial row per workgroup (UNION) or per
@@ -129,7 +120,7 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
   ma.pass.partials = d_rows;
   const unsigned long long den_mult = joint ? (unsigned long long)n_targets : 1ull;
   const int total_passes = params->max_iteration + 1;  // max_iter updates need max_iter + 1 correspondence passes
-  return two_launch_loop(h, total_passes, out, [&] {  // the host loop of o3ds_icp_register_dev's two-launch form
+  return two_launch_loop(h, total_passes, look_at_session_state(h, out), [&] {  // the host loop of o3ds_icp_register_dev's two-launch form
     launch_multi_accumulate(h, ma, nb);
     icp_multi_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(d_rows, nrows, h->d_state, n_upper, ma.pass.count_dev, den_mult, params->max_iteration,
                                                                 params->relative_fitness, params->relative_rmse, params->method, quantum_table(ma.pass));

@@ -7,7 +7,7 @@
   K x register_dev     K one-target registrations in sequence (what JOINT replaces in device time).
 Every registration ends with the host reading the final state, so host wall time around the call (after a stream synchronise) spans
 the device work; each row is the median of --reps runs after --warmup, with the spread (min .. max).
-    python scripts/multi_submap_timing.py [--reps 15] [--warmup 3] [--out profiles/multi_submap.txt]"""
+    python scripts/multi_submap_timing.py [--reps 15] [--warmup 3] [--ks 1 2 4 8] [--out profiles/multi_submap.txt]"""
 import argparse
 import os
 import sys
@@ -45,10 +45,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "multi_submap.txt"))
     ap.add_argument("--points", type=int, default=1_000_000)
+    ap.add_argument("--ks", type=int, nargs="+", default=[1, 2, 4, 8])
     a = ap.parse_args()
     scene = syn.make_scene()
     src, tgt0, nrm0, _ = syn.config2_inputs(n_map=a.points, n_az=4096)
-    maps = [(tgt0, nrm0)] + [syn.sample_map(scene, a.points, seed=syn.SEED_MAP + k) for k in range(1, 8)]
+    maps = [(tgt0, nrm0)] + [syn.sample_map(scene, a.points, seed=syn.SEED_MAP + k) for k in range(1, max(a.ks))]
     be = backend.Backend(0)
     lines = [f"multi_submap_timing: {a.points} points per map, scan {len(src)} points, 10 iterations, median of {a.reps} runs after {a.warmup} (min .. max)"]
     s = be.upload(src)
@@ -61,7 +62,7 @@ def main():
     everything = backend.make_crop(backend.CROP_MAX_RADIUS, rmax=1e9)
     for method, name in ((backend.ICP_POINT_TO_PLANE, "point-to-plane"), (backend.ICP_GENERALIZED, "generalized")):
         params = backend.Backend._params(R, 10, 0.0, 0.0, method)
-        for K in (1, 2, 4, 8):
+        for K in a.ks:
             sub = ids[:K]
             t_union = timed(be, lambda: be.icp_register_multi(s, sub, form=be.MULTI_UNION, params=params), a.reps, a.warmup)
             t_joint = timed(be, lambda: be.icp_register_multi(s, sub, form=be.MULTI_JOINT, params=params), a.reps, a.warmup)

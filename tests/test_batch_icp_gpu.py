@@ -157,6 +157,45 @@ def test_an_entry_without_correspondences_is_the_one_pair_result_and_disturbs_no
         be.close()
 
 
+# ------------------------------------------------------------------------------------------------- 4b. every query goes to stage 3
+def far_grid_inputs():
+    """A flat 64 x 64 grid (spacing 0.05 m, z = 0, normals +z) and 129 points 0.8 m above its interior: one full workgroup of 128
+    queries and one with a single live query."""
+    g = 0.05 * np.arange(64)
+    tgt = np.stack([np.repeat(g, 64), np.tile(g, 64), np.zeros(64 * 64)], axis=1)  # x-major: rows [:2048] are the half x < 1.6
+    up = np.tile([0.0, 0.0, 1.0], (len(tgt), 1))
+    rng = np.random.default_rng(23)
+    src = np.column_stack([rng.uniform(0.8, 2.35, 129), rng.uniform(0.8, 2.35, 129), np.full(129, 0.8)])
+    return tgt, up, src
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("method", (backend.ICP_POINT_TO_PLANE, backend.ICP_GENERALIZED))
+def test_a_batch_whose_every_query_goes_to_stage_3_is_its_one_pair_calls(precision, method):
+    """Pass 0 of every entry runs the workgroup-pooled stage-3 search for every query.  The index cell is r / 4 = 0.25 m for the
+    correspondence distance r = 1 m, and stages 1 and 2 prove a match only within 2.5 cells = 0.625 r of the query (the stage
+    description above nn_search_group in icp_kernels.hpp).  The queries start 0.8 m above the target plane and at least 0.8 m inside its
+    border, and an initial guess moves no point by more than 0.09 m (rotations of at most 1 degree in total, 0.0175 rad x 3.42 m from
+    the origin, and at most 0.03 m of translation), so every nearest target point is between 0.71 r and 0.9 r away: unresolved after
+    stage 2, with a match inside the radius for stage 3 to find."""
+    tgt, up, src = far_grid_inputs()
+    be = B(0, precision=precision)
+    try:
+        s = be.upload(src, np.tile([0.0, 0.0, 1.0], (len(src), 1)))  # (generalized ICP builds its covariances from the normals)
+        t = be.upload(tgt, up)
+        inits = [syn.make_pose([0.02, -0.01, 0.01], [0.0, 0.0, 0.5]), syn.make_pose([-0.01, 0.02, -0.02], [0.5, -0.5, 0.0]),
+                 syn.make_pose([0.0, 0.0, 0.02], [-0.4, 0.2, 0.4])]
+        entries = [(s, t, None, T) for T in inits]
+        refs = [_one_pair(be, e, 3, method, rel=0.0) for e in entries]
+        assert all(r["n_corr"] > 0 and r["iterations"] == 3 for r in refs), refs
+        got, status = be.icp_register_batch(entries, _params(3, method, rel=0.0))
+        assert status == [0, 0, 0]
+        for k, (g, r) in enumerate(zip(got, refs)):
+            assert _bits(g) == _bits(r), (k, g, r)
+    finally:
+        be.close()
+
+
 # ------------------------------------------------------------------------------------------------- 5. several guesses for one pair
 def test_several_initial_guesses_for_one_pair(inputs):
     """Every entry is its one-pair call; the ones that reach the optimum end within 1e-3 m / rad of the ground truth (f32 storage).

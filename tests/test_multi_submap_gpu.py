@@ -213,6 +213,57 @@ def test_union_under_a_crop_is_the_registration_against_the_cropped_targets(scen
         be.close()
 
 
+# ------------------------------------------------------------------------------------------------- 8b. every query goes to stage 3
+def _far_grid_inputs():
+    """A flat 64 x 64 grid (spacing 0.05 m, z = 0, normals +z) and 129 points 0.8 m above its interior: one full workgroup of 128
+    queries and one with a single live query."""
+    g = 0.05 * np.arange(64)
+    tgt = np.stack([np.repeat(g, 64), np.tile(g, 64), np.zeros(64 * 64)], axis=1)  # x-major: rows [:2048] are the half x < 1.6
+    up = np.tile([0.0, 0.0, 1.0], (len(tgt), 1))
+    rng = np.random.default_rng(23)
+    src = np.column_stack([rng.uniform(0.8, 2.35, 129), rng.uniform(0.8, 2.35, 129), np.full(129, 0.8)])
+    return tgt, up, src
+
+
+@pytest.mark.parametrize("precision", [backend.PRECISION_F64, backend.PRECISION_F32])
+@pytest.mark.parametrize("method", [backend.ICP_POINT_TO_PLANE, backend.ICP_GENERALIZED])
+def test_both_forms_when_every_query_goes_to_stage_3(precision, method):
+    """Pass 0 runs the workgroup-pooled stage-3 search for every query, in every slot.  The index cell is r / 4 = 0.25 m for the
+    correspondence distance r = 1 m, and stages 1 and 2 prove a match only within 2.5 cells = 0.625 r of the query (the stage
+    description above nn_search_group in icp_kernels.hpp).  The queries start 0.8 m above the target plane and at least 0.8 m inside its
+    border, and the initial guess moves no point by more than 0.09 m (a rotation of 1 degree in total, 0.0175 rad x 3.42 m from the
+    origin, and 0.03 m of translation at most), so every nearest target point is between 0.71 r and 0.9 r away: unresolved after
+    stage 2, with a match inside the radius for stage 3 to find.  The same holds in each half of the grid for the queries above it; a
+    query above the other half finds nothing or a farther point there, also in stage 3.
+    JOINT over two copies of the grid is the one-target pose bit for bit; UNION over the two halves is the registration against the
+    appended copy, compared as test_union_is_the_registration_against_the_appended_copy compares."""
+    tgt, up, src = _far_grid_inputs()
+    init = syn.make_pose([0.02, -0.01, 0.01], [0.5, -0.5, 0.0])
+    be = B(0, precision=precision)
+    try:
+        s = be.upload(src, np.tile([0.0, 0.0, 1.0], (len(src), 1)))  # (generalized ICP builds its covariances from the normals)
+        t = _target(be, tgt, up)
+        ref = be.icp_register_dev(s, t, R, init=init, max_iter=3, rel_fitness=0.0, rel_rmse=0.0, method=method)
+        assert ref["iterations"] == 3 and ref["n_corr"] > 0, ref
+        got = be.icp_register_multi(s, [t, t], form=JOINT, init=init, params=_params(3, method))
+        assert got["transformation"].tobytes() == ref["transformation"].tobytes()
+        assert (got["fitness"], got["inlier_rmse"], got["iterations"]) == (ref["fitness"], ref["inlier_rmse"], ref["iterations"])
+        assert got["n_corr"] == 2 * ref["n_corr"]
+        halves = [_target(be, tgt[:2048], up[:2048]), _target(be, tgt[2048:], up[2048:])]
+        cat = _appended(be, halves)
+        ref = be.icp_register_dev(s, cat, R, init=init, max_iter=3, rel_fitness=0.0, rel_rmse=0.0, method=method)
+        got = be.icp_register_multi(s, halves, form=UNION, init=init, params=_params(3, method))
+        print(f"precision={precision} method={method}: n_corr {got['n_corr']}/{ref['n_corr']}  iterations {got['iterations']}/{ref['iterations']}")
+        assert got["iterations"] == ref["iterations"] == 3
+        assert got["n_corr"] == ref["n_corr"] > 0
+        if precision == backend.PRECISION_F64:
+            assert _bits(got) == _bits(ref)  # exact, order-free sums over the same correspondences
+        else:
+            _close(got, ref, len(src), 1e-3)
+    finally:
+        be.close()
+
+
 # ------------------------------------------------------------------------------------------------- 9. determinism
 @pytest.mark.parametrize("form", [UNION, JOINT])
 def test_the_same_call_gives_the_same_bits(scene_inputs, form):
