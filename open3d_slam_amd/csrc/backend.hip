@@ -17,6 +17,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -589,6 +590,8 @@ inline int grid_for(size_t n, int cap = 4096) {
 }
 
 size_t p4_size(int precision) { return precision == O3DS_PRECISION_F64 ? sizeof(P4d) : sizeof(P4f); }
+// fn<P4> of the storage precision
+#define DISPATCH(prec, fn, ...) ((prec) == O3DS_PRECISION_F64 ? fn<P4d>(__VA_ARGS__) : fn<P4f>(__VA_ARGS__))
 
 void cloud_ready(o3ds_handle h, CloudRec& c);
 int resolve_count(o3ds_handle h, CloudRec& c, bool block);
@@ -770,13 +773,14 @@ struct CloudGuard {
 // exclusive scan of m ints (in -> out) with the hand-written 3-phase scan; in may alias out
 // pub: null, or a device-visible address (the handle's pinned block) that also receives out[m - 1] -- the total, when the input ends in a
 // zero sentinel -- from the kernel that finishes that element
-template <typename T>
-int exclusive_scan_t(o3ds_handle h, const T* in, T* out, size_t m, T* pub = nullptr) {
+// local(nb, sums, pub): the launch of the first phase, which reads the input (an array: exclusive_scan_t, a functor: exclusive_scan_fn)
+template <typename T, typename L>
+int exclusive_scan_phases(o3ds_handle h, T* out, size_t m, T* pub, L&& local) {
   if (m == 0) return O3DS_OK;
   const int nb = (int)((m + kScanPerBlock - 1) / kScanPerBlock);
   T* sums = nullptr;
   TMP_ALLOC(sums, sizeof(T) * (size_t)nb);
-  scan_local_kernel<T><<<nb, kBlock, 0, h->stream>>>(in, out, sums, m, nb == 1 ? pub : nullptr);
+  local(nb, sums, nb == 1 ? pub : nullptr);
   if (nb > 1 && nb <= kScanFusedBlocks) {
     scan_add_fused_kernel<T><<<nb, kBlock, 0, h->stream>>>(out, sums, m, pub);
   } else if (nb > 1) {
@@ -786,6 +790,14 @@ int exclusive_scan_t(o3ds_handle h, const T* in, T* out, size_t m, T* pub = null
   HIP_TRY(hipGetLastError());
   dbg_sync(h, 1);
   return O3DS_OK;  // results are stream-ordered; callers that need a value on the host copy it back and synchronise
+}
+template <typename T>
+int exclusive_scan_t(o3ds_handle h, const T* in, T* out, size_t m, T* pub = nullptr) {
+  return exclusive_scan_phases<T>(h, out, m, pub, [&](int nb, T* sums, T* p) { scan_local_kernel<T><<<nb, kBlock, 0, h->stream>>>(in, out, sums, m, p); });
+}
+template <typename T, typename Fn>
+int exclusive_scan_fn(o3ds_handle h, Fn in, T* out, size_t m, T* pub = nullptr) {  // the input is in(i), i < m
+  return exclusive_scan_phases<T>(h, out, m, pub, [&](int nb, T* sums, T* p) { scan_local_fn_kernel<T, Fn><<<nb, kBlock, 0, h->stream>>>(in, out, sums, m, p); });
 }
 int exclusive_scan_int(o3ds_handle h, const int* in, int* out, size_t m, int* pub = nullptr) { return exclusive_scan_t<int>(h, in, out, m, pub); }
 
@@ -798,6 +810,158 @@ int wait_stream(o3ds_handle h) {
   HIP_TRY(hipStreamSynchronize(h->stream));
   return O3DS_OK;
 }
+
+// ---- what the cloud and map operations share ------------------------------------------------------------------------
+// n (key, value) pairs in ascending order of the key bits [0, end_bit), equal keys in their order of arrival: rocPRIM's radix sort,
+// its temporary (its own ping-pong buffers of n keys and values among it: about 12 bytes per pair) from the arena.  `keep`: a caller
+// that sorts the same number of pairs again hands the same SortTemp to both calls, and the second sort runs in the first one's temporary
+struct SortTemp {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+int sort_pairs(o3ds_handle h, unsigned long long* k_in, unsigned long long* k_out, uint32_t* v_in, uint32_t* v_out, size_t n, unsigned int end_bit = 64,
+               SortTemp* keep = nullptr) {
+  SortTemp own;
+  SortTemp& t = keep ? *keep : own;
+  if (!t.p) {
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t.bytes, k_in, k_out, v_in, v_out, n, 0, end_bit, h->stream));
+    TMP_ALLOC(t.p, t.bytes ? t.bytes : 16);
+  }
+  HIP_TRY(rocprim::radix_sort_pairs(t.p, t.bytes, k_in, k_out, v_in, v_out, n, 0, end_bit, h->stream));
+  return O3DS_OK;
+}
+
+// head[0..n] (1 where a segment starts, head[n] = 0: the sentinel) -> seg_id[0..n], its exclusive scan, which ends with the number of
+// segments: read back into *n_seg (null: not wanted)
+int segment_ids(o3ds_handle h, const int* head, int* seg_id, size_t n, int* n_seg) {
+  const int rc = exclusive_scan_int(h, head, seg_id, n + 1);
+  if (rc || !n_seg) return rc;
+  return read_back(h, {{n_seg, seg_id + n, sizeof(int)}});
+}
+// ... of keys in ascending order: a segment is a run of equal keys
+int key_segments(o3ds_handle h, const unsigned long long* sorted_keys, size_t n, int* head, int* seg_id, int* n_seg) {
+  segment_head_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(sorted_keys, n, head);  // also writes the sentinel head[n] = 0
+  return segment_ids(h, head, seg_id, n, n_seg);
+}
+
+// the upper three rows of a pose (4 x 4, column-major) as the kernels take them; null: the identity
+Mat34 mat34(const double* T) {
+  Mat34 M;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) M.m[r * 4 + c] = T ? T[c * 4 + r] : (r == c ? 1.0 : 0.0);
+  return M;
+}
+
+// Scratch the handle owns and grows on demand (d_cells, d_voxtab, d_tiles, d_nn_cache): room for `want` elements in *ptr.  A block that
+// is too small is given back -- behind a synchronisation: work in flight may still use it -- and one of `new_cap` elements (`new_bytes`
+// bytes) is allocated; *fresh: the block is new, nothing is known of its contents.  An allocation that fails is the caller's to report
+// (or to live with: build_replica_t): it finds *ptr null.
+template <typename T>
+int handle_scratch(o3ds_handle h, T** ptr, size_t* cap, size_t want, size_t new_cap, size_t new_bytes, bool* fresh) {
+  *fresh = false;
+  if (*cap >= want) return O3DS_OK;
+  if (*ptr) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+  }
+  if (hipMalloc((void**)ptr, new_bytes) != hipSuccess) {
+    *ptr = nullptr;
+    return O3DS_OK;
+  }
+  *cap = new_cap;
+  *fresh = true;
+  return O3DS_OK;
+}
+// debugging / A/B aid: do not rely on self-cleaning scratch -- every block with a clean flag is cleared before every use
+bool always_clear() {
+  static const bool on = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;
+  return on;
+}
+// per-cell counters for a table of ncell cells: the handle's block of zeros (ncell + 1: the scan's sentinel stays zero), counted up by
+// a count kernel, read by the scan, counted back down to zero by the scatter -- after which the caller sets cells_clean again (stream
+// order: whoever counts next runs after that scatter).  h->d_cells is null when the allocation failed.
+int cell_counters(o3ds_handle h, size_t ncell) {
+  bool fresh = false;
+  const int rc = handle_scratch(h, &h->d_cells, &h->cells_cap, ncell + 1, ncell + 1 + ncell / 4, sizeof(int) * (ncell + 1 + ncell / 4), &fresh);
+  if (rc || !h->d_cells) return rc;
+  if (fresh) h->cells_clean = false;
+  if (!h->cells_clean || always_clear()) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
+  h->cells_clean = false;
+  return O3DS_OK;
+}
+// the scratch of vox_insert_kernel / pm_place_kernel and vox_order_kernel for n points.  The handle's voxel table: all 0xff between calls
+// (vox_mean_kernel / pm_group_kernel empty the slots a call used, after which the caller sets voxtab_clean again), grown to the largest
+// cloud seen.  The chained scan's tile records: kept across calls, never cleared (they carry the call's number, see vox_order_kernel)
+int vox_scratch(o3ds_handle h, size_t n, const char* what, VoxTable* table, size_t* n_tiles) {
+  size_t cap = 1024;
+  while (cap < 2 * n) cap <<= 1;
+  bool fresh = false;
+  int rc = handle_scratch(h, &h->d_voxtab, &h->voxtab_cap, cap, cap, kVoxSlotBytes * cap + 16, &fresh);
+  if (rc) return rc;
+  if (!h->d_voxtab) return fail(h, O3DS_ERR_OOM, std::string(what) + ": voxel table allocation failed");
+  if (fresh) h->voxtab_clean = false;
+  cap = h->voxtab_cap;
+  unsigned char* tab = h->d_voxtab;
+  *table = VoxTable{(VoxSlot*)tab, (unsigned int*)(tab + kVoxSlotBytes * cap), (unsigned int)(cap - 1)};
+  if (!h->voxtab_clean || always_clear()) HIP_TRY(hipMemsetAsync(tab, 0xff, kVoxSlotBytes * cap + 16, h->stream));
+  h->voxtab_clean = false;
+  *n_tiles = (n + kVoxTile - 1) / kVoxTile;
+  const size_t tiles = std::max<size_t>(*n_tiles + *n_tiles / 4, 1024);
+  rc = handle_scratch(h, &h->d_tiles, &h->tiles_cap, *n_tiles, tiles, sizeof(unsigned long long) * tiles, &fresh);
+  if (rc) return rc;
+  if (!h->d_tiles) return fail(h, O3DS_ERR_OOM, std::string(what) + ": scan state allocation failed");
+  if (fresh) {
+    const hipError_t e = hipMemsetAsync(h->d_tiles, 0, sizeof(unsigned long long) * tiles, h->stream);
+    if (e != hipSuccess) h->tiles_cap = 0;  // (never zeroed: the next call must not take it for a block in use)
+    HIP_TRY(e);
+  }
+  return O3DS_OK;
+}
+
+// the points (+ normals) of `in` whose flag is `which` -- m of its first n, to the positions `pos` -- and then its colours, which ride along
+// as a second attribute array through the same kernel; the arrays are allocated here, unless the caller has done so before its own launches
+template <typename P4>
+int compact_cloud(o3ds_handle h, const CloudRec& in, size_t n, const int* flags, const int* pos, int which, size_t m, void** pts, void** nrm, void** col) {
+  if (!*pts) HIP_TRY(dev_alloc(h, pts, sizeof(P4) * m));
+  if (in.nrm && !*nrm) HIP_TRY(dev_alloc(h, nrm, sizeof(P4) * m));
+  compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, n, flags, pos, which, (P4*)*pts, (P4*)*nrm);
+  if (in.col) {
+    if (!*col) HIP_TRY(dev_alloc(h, col, sizeof(P4) * m));
+    compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)in.col, nullptr, n, flags, pos, which, (P4*)*col, nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+// ... and the points idx[0..m) of `in`, in that order, as the arrays of `out`
+template <typename P4>
+int gather_cloud(o3ds_handle h, const CloudRec& in, const uint32_t* idx, size_t m, CloudRec& out) {
+  HIP_TRY(dev_alloc(h, &out.pts, sizeof(P4) * m));
+  if (in.nrm) HIP_TRY(dev_alloc(h, &out.nrm, sizeof(P4) * m));
+  gather_kernel<P4><<<grid_for(m), kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, idx, m, (P4*)out.pts, (P4*)out.nrm);
+  if (in.col) {
+    HIP_TRY(dev_alloc(h, &out.col, sizeof(P4) * m));
+    gather_kernel<P4><<<grid_for(m), kBlock, 0, h->stream>>>((const P4*)in.col, nullptr, idx, m, (P4*)out.col, nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+// a cloud's arrays are replaced by new ones (a carve, an append, a fold): n points in arrays with room for `cap` (0: exactly n); its
+// index goes, the vox_first / vox_count layout is the caller's to set
+void replace_arrays(o3ds_handle h, CloudRec& c, void* pts, void* nrm, void* col, size_t n, size_t cap) {
+  free_index(h, c);
+  free_points(h, c);
+  if (c.nrm) dev_free(h, c.nrm);
+  if (c.col) dev_free(h, c.col);
+  c.pts = pts;
+  c.nrm = nrm;
+  c.col = col;
+  c.n = n;
+  c.cap = cap;
+}
+
 // The fused registration loop's wait.  The launch the host waits for writes the state into pinned memory and then, with a system-scope
 // release, the stamp `seq` into a pinned word (icp_fused_kernel); every earlier launch of the stream has completed by then, and once the
 // loop is done the rest of that launch is workgroups returning.  Watching the word hands the result over as it is written instead of
@@ -904,23 +1068,9 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
   g.nz = (int)nz;
   int *counts = nullptr, *cell_id = nullptr, *cell_start = nullptr;
   void *spts = nullptr, *snrm = nullptr;
-  // per-cell counters: the handle's block of zeros (ncell + 1: the scan's sentinel stays zero); counted up by cell_count_kernel, read
-  // by the scan, counted back down to zero by scatter_kernel
-  if (h->cells_cap < ncell + 1) {
-    if (h->d_cells) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_cells);
-      h->d_cells = nullptr;
-      h->cells_cap = 0;
-    }
-    const size_t cap = ncell + 1 + ncell / 4;
-    if (hipMalloc((void**)&h->d_cells, sizeof(int) * cap) != hipSuccess) return fail(h, O3DS_ERR_OOM, "build_index: cell counters allocation failed");
-    h->cells_cap = cap;
-    h->cells_clean = false;
-  }
-  static const bool always_clear = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;  // debugging / A/B aid: do not rely on self-cleaning scratch
-  if (!h->cells_clean || always_clear) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
-  h->cells_clean = false;
+  rc = cell_counters(h, ncell);  // counted up by cell_count_kernel, counted back down to zero by scatter_kernel
+  if (rc) return rc;
+  if (!h->d_cells) return fail(h, O3DS_ERR_OOM, "build_index: cell counters allocation failed");
   counts = h->d_cells;
   TMP_ALLOC(cell_id, sizeof(int) * n);
   HIP_TRY(dev_alloc(h, (void**)&cell_start, sizeof(int) * (ncell + 1 + 4)));  // +4: the search reads rows as unaligned 16-B vectors
@@ -963,9 +1113,7 @@ double index_cell_div() {
   return d;
 }
 
-int build_index(o3ds_handle h, CloudRec& c, double cell) {
-  return c.precision == O3DS_PRECISION_F64 ? build_index_t<P4d>(h, c, cell) : build_index_t<P4f>(h, c, cell);
-}
+int build_index(o3ds_handle h, CloudRec& c, double cell) { return DISPATCH(c.precision, build_index_t, h, c, cell); }
 
 // The neighbourhood-major replica of an index (GridDev::rpts), built from its cell-sorted points: one count, one scan and one scatter
 // (replica_count_kernel / replica_scatter_kernel).  Not built when it does not fit (kReplicaMaxBytes, kMaxCells) or the memory is not there:
@@ -984,26 +1132,12 @@ int build_replica_t(o3ds_handle h, CloudRec& c) {
     if (rpts) dev_free(h, rpts);
     return O3DS_OK;
   }
-  // counters: the handle's block of zeros, as in build_grid_t (counted up, scanned, counted back down to zero by the scatter)
-  if (h->cells_cap < rcell + 1) {
-    if (h->d_cells) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_cells);
-      h->d_cells = nullptr;
-      h->cells_cap = 0;
-    }
-    const size_t cap = rcell + 1 + rcell / 4;
-    if (hipMalloc((void**)&h->d_cells, sizeof(int) * cap) != hipSuccess) {
-      (void)hipGetLastError();
-      dev_free(h, rstart), dev_free(h, rpts), dev_free(h, rpos);
-      return O3DS_OK;
-    }
-    h->cells_cap = cap;
-    h->cells_clean = false;
+  const int rs = cell_counters(h, rcell);  // as in build_grid_t
+  if (rs || !h->d_cells) {  // (no memory for the counters: no replica, no error)
+    (void)hipGetLastError();
+    dev_free(h, rstart), dev_free(h, rpts), dev_free(h, rpos);
+    return rs;
   }
-  static const bool always_clear = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;
-  if (!h->cells_clean || always_clear) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
-  h->cells_clean = false;
   int* rcounts = h->d_cells;
   const int* n_dev = c.lazy_slot >= 0 ? cnt_word(h, c.lazy_slot) : nullptr;
   replica_count_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)c.spts, n, g, rcounts, n_dev);
@@ -1034,7 +1168,7 @@ int maybe_build_replica(o3ds_handle h, CloudRec& c) {
   const char* e = ab_getenv("O3DS_NN_REPLICA_AFTER");
   const int after = e ? std::max(1, atoi(e)) : kReplicaAfterRegs;
   if (++c.index_regs < after) return O3DS_OK;
-  return c.precision == O3DS_PRECISION_F64 ? build_replica_t<P4d>(h, c) : build_replica_t<P4f>(h, c);
+  return DISPATCH(c.precision, build_replica_t, h, c);
 }
 
 // f32 storage: the caller's doubles are narrowed on their way into the pinned ring (the narrowing the device would do: round to nearest
@@ -1246,10 +1380,7 @@ int dense_insert_t(o3ds_handle h, DenseRec& d, const CloudRec& c, const double T
   if (c.n == 0) return O3DS_OK;
   int rc = dense_reserve(h, d, c.n);
   if (rc) return rc;
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int col = 0; col < 4; ++col) M.m[r * 4 + col] = T ? T[col * 4 + r] : (r == col ? 1.0 : 0.0);
-  dense_insert_kernel<P4><<<grid_for(c.n), kBlock, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, (const P4*)c.col, c.n, M, 1.0 / d.voxel, d.dev);
+  dense_insert_kernel<P4><<<grid_for(c.n), kBlock, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, (const P4*)c.col, c.n, mat34(T), 1.0 / d.voxel, d.dev);
   HIP_TRY(hipGetLastError());
   if (c.nrm) d.has_normals = true;  // isHasNormals_, Voxel.cpp:80-83
   if (c.col) d.has_colors = true;   // isHasColors_, Voxel.cpp:84-87
@@ -1271,11 +1402,8 @@ int dense_to_cloud_t(o3ds_handle h, DenseRec& d, CloudRec& out) {
   TMP_ALLOC(s0, sizeof(uint32_t) * used);
   TMP_ALLOC(s1, sizeof(uint32_t) * used);
   dense_list_kernel<<<grid_for(d.cap), kBlock, 0, h->stream>>>(d.dev, d.cap, flag, pos, k0, s0);
-  size_t temp_bytes = 0;  // ascending key order: the table order depends on how insertions interleaved, the output must not
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, s0, s1, used, 0, 64, h->stream));
-  void* temp = nullptr;
-  TMP_ALLOC(temp, temp_bytes ? temp_bytes : 16);
-  HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, s0, s1, used, 0, 64, h->stream));
+  rc = sort_pairs(h, k0, k1, s0, s1, used);  // ascending key order: the table order depends on how insertions interleaved, the output must not
+  if (rc) return rc;
   out.n = used;
   HIP_TRY(dev_alloc(h, (void**)&out.pts, sizeof(P4) * used));
   if (d.has_normals) HIP_TRY(dev_alloc(h, (void**)&out.nrm, sizeof(P4) * used));
@@ -1325,37 +1453,27 @@ struct LaunchBracket {
   }
 };
 
-#define DISPATCH(prec, fn, ...) ((prec) == O3DS_PRECISION_F64 ? fn<P4d>(__VA_ARGS__) : fn<P4f>(__VA_ARGS__))
+// The pass kernels are instantiated per target crop and estimator (generalized ICP or not): launch(crop, gicp) is called with the two as
+// compile-time constants, std::true_type / std::false_type
+template <typename F>
+void with_crop_and_estimator(bool crop, bool gicp, F&& launch) {
+  if (gicp)
+    crop ? launch(std::true_type{}, std::true_type{}) : launch(std::false_type{}, std::true_type{});
+  else
+    crop ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
+}
 
 // the launchers pick the instantiation from the session: storage precision (launch_*), target crop, estimator
 template <typename P4>
 void launch_accumulate_t(o3ds_handle h, const IcpPassArgs& a, int nblocks) {
-  const bool crop = h->session_crop;
   // one geometry: kIcpBlock threads = kIcpBlock / 4 queries x 4 lanes (G = 2 / 8 were swept and dropped; 512 threads against 256: a launch costs 2.7 ns per
   // workgroup beyond the first 256 -- scripts/ubench/launch_shape.hip -- and a steady pass is 9.7 us instead of 10.2)
-  if (a.keys_mode != 0) {  // target-sharded registration (o3ds_icp_nn_keys / o3ds_icp_accumulate_keys): the instantiation with the key code
-    if (h->session_method == O3DS_ICP_GENERALIZED) {
-      if (crop)
-        icp_accumulate_kernel<P4, true, kIcpBlock, 4, true, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-      else
-        icp_accumulate_kernel<P4, false, kIcpBlock, 4, true, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-    } else {
-      if (crop)
-        icp_accumulate_kernel<P4, true, kIcpBlock, 4, false, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-      else
-        icp_accumulate_kernel<P4, false, kIcpBlock, 4, false, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-    }
-  } else if (h->session_method == O3DS_ICP_GENERALIZED) {
-    if (crop)
-      icp_accumulate_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
+  with_crop_and_estimator(h->session_crop, h->session_method == O3DS_ICP_GENERALIZED, [&](auto crop, auto gicp) {
+    if (a.keys_mode != 0)  // target-sharded registration (o3ds_icp_nn_keys / o3ds_icp_accumulate_keys): the instantiation with the key code
+      icp_accumulate_kernel<P4, decltype(crop)::value, kIcpBlock, 4, decltype(gicp)::value, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
     else
-      icp_accumulate_kernel<P4, false, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-  } else {
-    if (crop)
-      icp_accumulate_kernel<P4, true, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-    else
-      icp_accumulate_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
-  }
+      icp_accumulate_kernel<P4, decltype(crop)::value, kIcpBlock, 4, decltype(gicp)::value><<<nblocks, kIcpBlock, 0, h->stream>>>(a);
+  });
 }
 
 void launch_accumulate(o3ds_handle h, const IcpPassArgs& a, int nblocks) {
@@ -1372,18 +1490,9 @@ static_assert(sizeof(IcpStateDev) <= kFusedStateStride, "state slot too small");
 
 template <typename P4>
 void launch_fused_t(o3ds_handle h, const IcpFusedArgs& fa, int nblocks) {
-  const bool crop = h->session_crop;
-  if (h->session_method == O3DS_ICP_GENERALIZED) {
-    if (crop)
-      icp_fused_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
-    else
-      icp_fused_kernel<P4, false, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
-  } else {
-    if (crop)
-      icp_fused_kernel<P4, true, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
-    else
-      icp_fused_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
-  }
+  with_crop_and_estimator(h->session_crop, h->session_method == O3DS_ICP_GENERALIZED, [&](auto crop, auto gicp) {
+    icp_fused_kernel<P4, decltype(crop)::value, kIcpBlock, 4, decltype(gicp)::value><<<nblocks, kIcpBlock, 0, h->stream>>>(fa.state_in, fa.slots_in, fa.first, fa);
+  });
 }
 
 void launch_fused(o3ds_handle h, const IcpFusedArgs& fa, int nblocks, bool bracket) {  // (a tail-only launch is not a pass: no bracket)
@@ -1455,18 +1564,14 @@ void record_quanta(const GridDev& g, double r, int method, double gicp_epsilon, 
     // the record terms are products of two per-query slots; slot magnitudes per method (icp_kernels.hpp, kTermA/B tables)
     double slot[10];
     const unsigned char *ta, *tb;
-    static const unsigned char A0[kRec] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9};
-    static const unsigned char B0[kRec] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 3, 4, 5, 4, 5, 5, 6, 6, 6, 6, 6, 6, 6, 7, 7, 9, 9};
-    static const unsigned char A1[kRec] = {3, 3, 3, 4, 4, 4, 5, 5, 5, 0, 1, 2, 3, 4, 5, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 8, 9, 9};
-    static const unsigned char B1[kRec] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 7, 7, 7, 7, 7, 7, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 9, 7, 7, 9, 9};
     if (method == O3DS_ICP_POINT_TO_POINT) {  // also the information-matrix pass (same slots, q q^T terms bounded by p q^T's)
       for (int i = 0; i < 6; ++i) slot[i] = P;  // p, q
       slot[6] = 0.0, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
-      ta = A1, tb = B1;
+      ta = kTermA_p2p, tb = kTermB_p2p;
     } else {
       for (int i = 0; i < 3; ++i) slot[i] = P, slot[3 + i] = 1.0;  // J = [p x n ; n], unit normals
       slot[6] = rr, slot[7] = 1.0, slot[8] = rr * rr, slot[9] = 0.0;
-      ta = A0, tb = B0;
+      ta = kTermA, tb = kTermB;
     }
     for (int k = 0; k < kRec; ++k) bound[k] = std::max(slot[ta[k]] * slot[tb[k]], 1e-30);
     if (method == O3DS_ICP_POINT_TO_POINT)
@@ -1500,25 +1605,22 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
     rc = build_index(h, *tgt, params->max_correspondence_distance / index_cell_div());
     if (rc) return rc;
   }
-  if (src->n > h->nn_cache_cap) {
-    if (h->d_nn_cache) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_nn_cache);
-      h->d_nn_cache = nullptr;
-      h->nn_cache_cap = 0;
-    }
-    const size_t cap = (std::max<size_t>(src->n + src->n / 4, 1 << 16) + 7) & ~(size_t)7;
-    if (hipMalloc((void**)&h->d_nn_cache, cap * sizeof(int)) != hipSuccess) return fail(h, O3DS_ERR_OOM, "icp: match cache allocation failed");
+  const size_t cap = (std::max<size_t>(src->n + src->n / 4, 1 << 16) + 7) & ~(size_t)7;
+  bool fresh_cache = false;
+  rc = handle_scratch(h, &h->d_nn_cache, &h->nn_cache_cap, src->n, cap, cap * sizeof(int), &fresh_cache);
+  if (rc) return rc;
+  if (!h->d_nn_cache) return fail(h, O3DS_ERR_OOM, "icp: match cache allocation failed");
+  if (fresh_cache) {  // the candidate sets are sized with it (the synchronisation above covers them)
     if (h->d_set_pos) (void)hipFree(h->d_set_pos);
     h->d_set_pos = nullptr;
     h->d_set_ref = nullptr;
     if (hipMalloc((void**)&h->d_set_pos, cap * (kSetCap * sizeof(int) + 4 * sizeof(double))) != hipSuccess) {
       (void)hipFree(h->d_nn_cache);
       h->d_nn_cache = nullptr;
+      h->nn_cache_cap = 0;
       return fail(h, O3DS_ERR_OOM, "icp: candidate-set allocation failed");
     }
     h->d_set_ref = (char*)h->d_set_pos + cap * kSetCap * sizeof(int);  // (cap is a multiple of 4: 32-byte aligned)
-    h->nn_cache_cap = cap;
   }
   IcpStateDev st{};
   memcpy(st.T, init, sizeof(double) * 16);
@@ -1881,7 +1983,7 @@ int o3ds_cloud_upload(o3ds_handle h, const double* xyz, const double* normals, s
   if (n > 0x7fffffffull) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_upload: more than 2^31-1 points");
   HIP_TRY(hipSetDevice(h->device));
   CloudRec c;
-  int rc = h->precision == O3DS_PRECISION_F64 ? upload_t<P4d>(h, xyz, normals, n, c) : upload_t<P4f>(h, xyz, normals, n, c);
+  int rc = DISPATCH(h->precision, upload_t, h, xyz, normals, n, c);
   if (rc) {
     free_cloud(h, c);
     return rc;
@@ -2092,7 +2194,7 @@ int o3ds_cloud_download(o3ds_handle h, o3ds_cloud id, double* xyz, double* norma
   CloudRec* c = find_cloud(h, id);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download: unknown cloud id");
   if (capacity < c->n) return fail(h, O3DS_ERR_CAPACITY, "cloud_download: capacity < cloud size");
-  return c->precision == O3DS_PRECISION_F64 ? download_t<P4d>(h, *c, xyz, normals) : download_t<P4f>(h, *c, xyz, normals);
+  return DISPATCH(c->precision, download_t, h, *c, xyz, normals);
 }
 
 int o3ds_cloud_download_f32(o3ds_handle h, o3ds_cloud id, void* data, size_t capacity, size_t point_step, size_t off_x, size_t off_y,
@@ -2665,15 +2767,8 @@ int crop_t(o3ds_handle h, const CloudRec& in, const CropDev& crop, CloudRec& out
   const int total = pub_value<int>(h, 0);
   out.n = (size_t)total;
   if (total > 0) {
-    HIP_TRY(dev_alloc(h, (void**)&out.pts, sizeof(P4) * out.n));
-    if (in.nrm) HIP_TRY(dev_alloc(h, (void**)&out.nrm, sizeof(P4) * out.n));
-    compact_kernel<P4><<<grid_for(in.n), kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, in.n, flags, pos, 1, (P4*)out.pts,
-                                                               (P4*)out.nrm);
-    if (in.col) {  // colours ride along as a second attribute array through the same kernel
-      HIP_TRY(dev_alloc(h, (void**)&out.col, sizeof(P4) * out.n));
-      compact_kernel<P4><<<grid_for(in.n), kBlock, 0, h->stream>>>((const P4*)in.col, nullptr, in.n, flags, pos, 1, (P4*)out.col, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
+    rc = compact_cloud<P4>(h, in, in.n, flags, pos, 1, out.n, &out.pts, &out.nrm, &out.col);
+    if (rc) return rc;
   }
   dbg_sync(h, 4);
   return O3DS_OK;
@@ -2734,22 +2829,10 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
   }
   if (out.has_box) box_inflate(out);
   if (table_path) {
-    size_t cap = 1024;
-    while (cap < 2 * n) cap <<= 1;
-    // the handle's table: all 0xff between calls (vox_mean_kernel empties the slots a call used), grown to the largest cloud seen
-    if (h->voxtab_cap < cap) {
-      if (h->d_voxtab) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_voxtab);
-        h->d_voxtab = nullptr;
-        h->voxtab_cap = 0;
-      }
-      if (hipMalloc((void**)&h->d_voxtab, kVoxSlotBytes * cap + 16) != hipSuccess) return fail(h, O3DS_ERR_OOM, "VoxelDownSample: voxel table allocation failed");
-      h->voxtab_cap = cap;
-      h->voxtab_clean = false;
-    }
-    cap = h->voxtab_cap;
-    unsigned char* tab = h->d_voxtab;
+    VoxTable t{};
+    size_t n_tiles = 0;
+    const int rs = vox_scratch(h, n, "VoxelDownSample", &t, &n_tiles);
+    if (rs) return rs;
     int *lead_slot = nullptr, *run_next = nullptr, *run_len = nullptr, *order = nullptr;
     uint32_t* starts = nullptr;
     int2* piece = nullptr;
@@ -2759,24 +2842,6 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
     TMP_ALLOC(order, sizeof(int) * n);
     TMP_ALLOC(starts, sizeof(uint32_t) * n);
     if (in.col) TMP_ALLOC(piece, sizeof(int2) * n);
-    VoxTable t{(VoxSlot*)tab, (unsigned int*)(tab + kVoxSlotBytes * cap), (unsigned int)(cap - 1)};
-    static const bool always_clear = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;
-    if (!h->voxtab_clean || always_clear) HIP_TRY(hipMemsetAsync(tab, 0xff, kVoxSlotBytes * cap + 16, h->stream));
-    h->voxtab_clean = false;
-    // the chained scan's tile records (kept across calls, see vox_order_kernel)
-    const size_t n_tiles = (n + kVoxTile - 1) / kVoxTile;
-    if (h->tiles_cap < n_tiles) {
-      if (h->d_tiles) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_tiles);
-        h->d_tiles = nullptr;
-        h->tiles_cap = 0;
-      }
-      const size_t want = std::max<size_t>(n_tiles + n_tiles / 4, 1024);
-      if (hipMalloc((void**)&h->d_tiles, sizeof(unsigned long long) * want) != hipSuccess) return fail(h, O3DS_ERR_OOM, "VoxelDownSample: scan state allocation failed");
-      HIP_TRY(hipMemsetAsync(h->d_tiles, 0, sizeof(unsigned long long) * want, h->stream));
-      h->tiles_cap = want;
-    }
     // the size of the result: an upper bound here, the number of voxels in a device word and a pinned record when vox_order_kernel has run
     out.n = n;
     out.n_lower = 1;  // (the box is not empty: at least one point lies inside the volume, hence at least one voxel)
@@ -2854,11 +2919,8 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
         TMP_ALLOC(xv2, sizeof(uint32_t) * nx);
         static const bool lib_sort = ab_getenv("O3DS_MERGE_LIBRARY_SORT") != nullptr;  // A/B: rocPRIM's radix sort of the same pairs
         if (lib_sort) {
-          size_t tb = 0;
-          HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, xk, xk2, xv, xv2, nx, 0, 63, h->stream));
-          void* tmp = nullptr;
-          TMP_ALLOC(tmp, tb ? tb : 16);
-          HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, xk, xk2, xv, xv2, nx, 0, 63, h->stream));
+          rcs = sort_pairs(h, xk, xk2, xv, xv2, nx, 63);
+          if (rcs) return rcs;
           xks = xk2, xvs = xv2;
         } else {
           unsigned long long *ka = xk2, *kb = xk;  // the tile sort reads xk / xv and writes the second pair of buffers; passes ping-pong
@@ -2895,11 +2957,8 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
   }
   if (!merged) {
     voxel_key_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)in.pts, n, mode, ox, oy, oz, voxel, crop, k0, v0, filter ? 1 : 0);
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-    void* temp = nullptr;
-    TMP_ALLOC(temp, temp_bytes ? temp_bytes : 16);
-    HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
+    const int rs = sort_pairs(h, k0, k1, v0, v1, n);
+    if (rs) return rs;
   }
   segment_head_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, n, head);  // also writes the sentinel head[n] = 0
   if (!merged) first_pass_kernel<<<1, 64, 0, h->stream>>>(k1, n, pub_slot<unsigned long long>(h, 3));
@@ -3120,7 +3179,7 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
 }
 
 int gicp_knn_normals(o3ds_handle h, CloudRec& c) {
-  return c.precision == O3DS_PRECISION_F64 ? normals_t<P4d>(h, c, 0.0, 20, true) : normals_t<P4f>(h, c, 0.0, 20, true);
+  return DISPATCH(c.precision, normals_t, h, c, 0.0, 20, true);
 }
 
 template <typename P4>
@@ -3129,12 +3188,9 @@ int transform_t(o3ds_handle h, const CloudRec& in, const double T[16], CloudRec&
   out.n = in.n;
   box_transform(out, in, T);
   if (in.n == 0) return O3DS_OK;
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) M.m[r * 4 + c] = T[c * 4 + r];
   HIP_TRY(dev_alloc(h, (void**)&out.pts, sizeof(P4) * in.n));
   if (in.nrm) HIP_TRY(dev_alloc(h, (void**)&out.nrm, sizeof(P4) * in.n));
-  transform_kernel<P4><<<grid_for(in.n), kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, in.n, M, T[3], T[7], T[11], T[15],
+  transform_kernel<P4><<<grid_for(in.n), kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, in.n, mat34(T), T[3], T[7], T[11], T[15],
                                                                (P4*)out.pts, (P4*)out.nrm, 0);
   if (in.col) {
     HIP_TRY(dev_alloc(h, (void**)&out.col, sizeof(P4) * in.n));
@@ -3182,39 +3238,19 @@ int carve_t(o3ds_handle h, CloudRec& map, const CloudRec& scan, const double T[1
   if (try_partition) {
     int* rank = nullptr;
     TMP_ALLOC(rank, sizeof(int) * (n + 1));
-    {
-      const size_t ms = n + 1;
-      const int nbs = (int)((ms + kScanPerBlock - 1) / kScanPerBlock);
-      int* sums = nullptr;
-      TMP_ALLOC(sums, sizeof(int) * (size_t)nbs);
-      scan_local_fn_kernel<int, KeyInsideFlag><<<nbs, kBlock, 0, h->stream>>>(KeyInsideFlag{k0, n}, rank, sums, ms, nullptr);
-      if (nbs > 1 && nbs <= kScanFusedBlocks) {
-        scan_add_fused_kernel<int><<<nbs, kBlock, 0, h->stream>>>(rank, sums, ms, nullptr);
-      } else if (nbs > 1) {
-        scan_sums_kernel<int><<<1, kBlock, 0, h->stream>>>(sums, nbs);
-        scan_add_kernel<int><<<nbs, kBlock, 0, h->stream>>>(rank, sums, ms, nullptr);
-      }
-    }
+    rc = exclusive_scan_fn<int>(h, KeyInsideFlag{k0, n}, rank, n + 1);
+    if (rc) return rc;
     partition_keys_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k0, rank, n, k1, v1);
     int* d_unsorted = pub_slot<int>(h, 2);
     *(volatile int*)(h->h_pin + kPubOff + 32) = 0;  // (nothing in flight writes the slot: every use ends in a synchronisation)
     segment_head_check_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, n, head, d_unsorted);
-    rc = exclusive_scan_int(h, head, seg_id, n + 1);
-    if (rc) return rc;
-    rc = read_back(h, {{&n_seg, seg_id + n, sizeof(int)}});
+    rc = segment_ids(h, head, seg_id, n, &n_seg);
     if (rc) return rc;
     sorted_ok = pub_value<int>(h, 2) == 0;
   }
   if (!sorted_ok) {
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-    void* temp = nullptr;
-    TMP_ALLOC(temp, temp_bytes ? temp_bytes : 16);
-    HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-    segment_head_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, n, head);  // also writes the sentinel head[n] = 0
-    rc = exclusive_scan_int(h, head, seg_id, n + 1);
-    if (rc) return rc;
-    rc = read_back(h, {{&n_seg, seg_id + n, sizeof(int)}});
+    rc = sort_pairs(h, k0, k1, v0, v1, n);
+    if (!rc) rc = key_segments(h, k1, n, head, seg_id, &n_seg);
     if (rc) return rc;
   }
   TMP_ALLOC(seg_start, sizeof(int) * ((size_t)n_seg + 1));
@@ -3233,10 +3269,7 @@ int carve_t(o3ds_handle h, CloudRec& map, const CloudRec& scan, const double T[1
   TMP_ALLOC(pos, sizeof(int) * (n + 1));
   fill_int_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(keep, n, 1);
   HIP_TRY(hipMemsetAsync(keep + n, 0, sizeof(int), h->stream));
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) M.m[r * 4 + c] = T[c * 4 + r];
-  carve_rays_kernel<P4><<<grid_for(scan.n), kBlock, 0, h->stream>>>((const P4*)scan.pts, scan.n, M, T[12], T[13], T[14], cp.voxel_size,
+  carve_rays_kernel<P4><<<grid_for(scan.n), kBlock, 0, h->stream>>>((const P4*)scan.pts, scan.n, mat34(T), T[12], T[13], T[14], cp.voxel_size,
                                                                    cp.max_raytracing_length, cp.truncation_distance,
                                                                    cp.min_dot_product_with_normal, tkey, tseg, (unsigned int)(tsize - 1), seg_start,
                                                                    (size_t)n_seg, n, v1, (const P4*)map.nrm, keep, block_bits);
@@ -3254,36 +3287,17 @@ int carve_t(o3ds_handle h, CloudRec& map, const CloudRec& scan, const double T[1
   if (removed) {  // map->SelectByIndex(idxsToRemove) (Submap.cpp:119): the same flags and positions, the other side of the compaction
     removed->precision = map.precision;
     removed->n = *n_removed;
-    HIP_TRY(dev_alloc(h, (void**)&removed->pts, sizeof(P4) * removed->n));
-    if (map.nrm) HIP_TRY(dev_alloc(h, (void**)&removed->nrm, sizeof(P4) * removed->n));
-    compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)map.pts, (const P4*)map.nrm, n, keep, pos, 0, (P4*)removed->pts, (P4*)removed->nrm);
-    if (map.col) {
-      HIP_TRY(dev_alloc(h, (void**)&removed->col, sizeof(P4) * removed->n));
-      compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)map.col, nullptr, n, keep, pos, 0, (P4*)removed->col, nullptr);
-    }
+    rc = compact_cloud<P4>(h, map, n, keep, pos, 0, removed->n, &removed->pts, &removed->nrm, &removed->col);
+    if (rc) return rc;
     box_copy(*removed, map);
   }
   void *np = nullptr, *nn = nullptr, *nc = nullptr;
   if (total > 0) {
-    HIP_TRY(dev_alloc(h, (void**)&np, sizeof(P4) * (size_t)total));
-    if (map.nrm) HIP_TRY(dev_alloc(h, (void**)&nn, sizeof(P4) * (size_t)total));
-    compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)map.pts, (const P4*)map.nrm, n, keep, pos, 1, (P4*)np, (P4*)nn);
-    if (map.col) {
-      HIP_TRY(dev_alloc(h, (void**)&nc, sizeof(P4) * (size_t)total));
-      compact_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)map.col, nullptr, n, keep, pos, 1, (P4*)nc, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
+    rc = compact_cloud<P4>(h, map, n, keep, pos, 1, (size_t)total, &np, &nn, &nc);
+    if (rc) return rc;
   }
-  free_index(h, map);
-  free_points(h, map);
+  replace_arrays(h, map, np, nn, nc, (size_t)total, 0);
   drop_ingest_box(h, map);
-  if (map.nrm) dev_free(h, map.nrm);
-  if (map.col) dev_free(h, map.col);
-  map.pts = np;
-  map.nrm = nn;
-  map.col = nc;
-  map.n = (size_t)total;
-  map.cap = 0;
   if (layout) {
     map.vox_first = (long long)kept_outside;
     map.vox_count = (size_t)total - (size_t)kept_outside;
@@ -3301,11 +3315,9 @@ int overlap_t(o3ds_handle h, const CloudRec& src, const CloudRec& tgt, const dou
   const size_t ns = src.n, nt = tgt.n, n = ns + nt;
   if (ns == 0 || nt == 0) return O3DS_OK;  // no voxel can hold points of both clouds
   CloudRec moved;
+  CloudGuard moved_guard(h, moved);
   int rc = transform_t<P4>(h, src, T, moved);  // sourceTransformed.Transform(sourceToTarget)
-  if (rc) {
-    free_cloud(h, moved);
-    return rc;
-  }
+  if (rc) return rc;
   unsigned long long *k0 = nullptr, *k1 = nullptr, *d_out = nullptr;
   uint32_t *v0 = nullptr, *v1 = nullptr;
   int *head = nullptr, *seg_id = nullptr, *cnt = nullptr, *flag = nullptr, *pos = nullptr;
@@ -3319,18 +3331,11 @@ int overlap_t(o3ds_handle h, const CloudRec& src, const CloudRec& tgt, const dou
   voxel_key_kernel<P4><<<grid_for(nt), kBlock, 0, h->stream>>>((const P4*)tgt.pts, nt, 1, 0.0, 0.0, 0.0, voxel, none, k0, v0);
   voxel_key_kernel<P4><<<grid_for(ns), kBlock, 0, h->stream>>>((const P4*)moved.pts, ns, 1, 0.0, 0.0, 0.0, voxel, none, k0 + nt, v0 + nt);
   overlap_tag_kernel<<<grid_for(ns), kBlock, 0, h->stream>>>(v0 + nt, ns);
-  size_t temp_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-  void* temp = nullptr;
-  TMP_ALLOC(temp, temp_bytes ? temp_bytes : 16);
-  HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
+  rc = sort_pairs(h, k0, k1, v0, v1, n);
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(head + n, 0, sizeof(int), h->stream));
-  segment_head_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, n, head);
-  rc = exclusive_scan_int(h, head, seg_id, n + 1);
-  if (rc) {
-    free_cloud(h, moved);
-    return rc;
-  }
+  rc = key_segments(h, k1, n, head, seg_id, nullptr);
+  if (rc) return rc;
   TMP_ALLOC(cnt, sizeof(int) * 2 * n);  // at most n segments: [0, n) source counts, [n, 2n) target counts
   HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * n, h->stream));
   overlap_count_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(v1, head, seg_id, n, cnt, cnt + n);
@@ -3343,7 +3348,6 @@ int overlap_t(o3ds_handle h, const CloudRec& src, const CloudRec& tgt, const dou
                                                              flag_t);
   rc = exclusive_scan_int(h, flag_s, pos, ns + 1);
   if (!rc) rc = exclusive_scan_int(h, flag_t, pos + ns + 1, nt + 1);
-  free_cloud(h, moved);
   if (rc) return rc;
   int tot[2] = {0, 0};
   rc = read_back(h, {{&tot[0], pos + ns, sizeof(int)}, {&tot[1], pos + ns + 1 + nt, sizeof(int)}});
@@ -3387,16 +3391,8 @@ int append_t(o3ds_handle h, CloudRec& map, const CloudRec& add) {
   HIP_TRY(hipGetLastError());
   dbg_sync(h, 32);
   guard.release();
-  free_index(h, map);
-  free_points(h, map);
+  replace_arrays(h, map, np, nn, nc, n, 0);
   drop_ingest_box(h, map);
-  if (map.nrm) dev_free(h, map.nrm);
-  if (map.col) dev_free(h, map.col);
-  map.pts = np;
-  map.nrm = nn;
-  map.col = nc;
-  map.n = n;
-  map.cap = 0;
   box_copy(map, joined);
   return O3DS_OK;
 }
@@ -3439,7 +3435,7 @@ int random_down_sample_t(o3ds_handle h, const CloudRec& in, double ratio, unsign
   int *flags = nullptr, *pos = nullptr;
   TMP_ALLOC(flags, sizeof(int) * (bound + 1));
   TMP_ALLOC(pos, sizeof(int) * (bound + 1));
-  HIP_TRY(dev_alloc(h, (void**)&out.pts, sizeof(P4) * k_bound));
+  HIP_TRY(dev_alloc(h, (void**)&out.pts, sizeof(P4) * k_bound));  // (before anything is launched: a draw whose result has nowhere to go is not started)
   if (in.nrm) HIP_TRY(dev_alloc(h, (void**)&out.nrm, sizeof(P4) * k_bound));
   if (in.col) HIP_TRY(dev_alloc(h, (void**)&out.col, sizeof(P4) * k_bound));
   const unsigned int g = grid_for(bound);
@@ -3454,13 +3450,50 @@ int random_down_sample_t(o3ds_handle h, const CloudRec& in, double ratio, unsign
   draw_flag_kernel<<<grid_for(bound + 1), kBlock, 0, h->stream>>>(n_ref, seed, st, flags);
   int rc = exclusive_scan_int(h, flags, pos, bound + 1);
   if (rc) return rc;
-  compact_kernel<P4><<<g, kBlock, 0, h->stream>>>((const P4*)in.pts, (const P4*)in.nrm, bound, flags, pos, 1, (P4*)out.pts, (P4*)out.nrm);
-  if (in.col) compact_kernel<P4><<<g, kBlock, 0, h->stream>>>((const P4*)in.col, nullptr, bound, flags, pos, 1, (P4*)out.col, nullptr);
-  HIP_TRY(hipGetLastError());
+  rc = compact_cloud<P4>(h, in, bound, flags, pos, 1, k_bound, &out.pts, &out.nrm, &out.col);
+  if (rc) return rc;
   dbg_sync(h, 4);
   return O3DS_OK;
 }
 
+// behind o3ds_dense_map_carve, which checks its arguments: the voxels of `d` that the rays of scan `c` (placed by scan_pose; null: as it is) see through are erased
+template <typename P4>
+int dense_carve_t(o3ds_handle h, DenseRec& d, const CloudRec& c, const double* scan_pose, const double sp[3], double neighborhood_radius,
+                  double max_raytracing_length, double truncation_distance, size_t* n_removed) {
+  const size_t n = c.n;
+  // removeDuplicatePointsWithinSameVoxels on the PLACED scan: keys of the placed points, stable sort, heads of the key segments
+  CloudRec placed;
+  CloudGuard placed_guard(h, placed);
+  int rc = transform_t<P4>(h, c, scan_pose ? scan_pose : kIdentity16, placed);
+  if (rc) return rc;
+  unsigned long long *k0 = nullptr, *k1 = nullptr, *d_removed = nullptr;
+  uint32_t *v0 = nullptr, *v1 = nullptr;
+  int *first = nullptr, *mark = nullptr;
+  TMP_ALLOC(k0, sizeof(unsigned long long) * n);
+  TMP_ALLOC(k1, sizeof(unsigned long long) * n);
+  TMP_ALLOC(v0, sizeof(uint32_t) * n);
+  TMP_ALLOC(v1, sizeof(uint32_t) * n);
+  TMP_ALLOC(first, sizeof(int) * n);
+  TMP_ALLOC(mark, sizeof(int) * d.cap);
+  TMP_ALLOC(d_removed, sizeof(unsigned long long));
+  CropDev none{};
+  voxel_key_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)placed.pts, n, 1, 0.0, 0.0, 0.0, d.voxel, none, k0, v0);
+  rc = sort_pairs(h, k0, k1, v0, v1, n);
+  if (rc) return rc;
+  first_of_voxel_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, v1, n, first);
+  HIP_TRY(hipMemsetAsync(mark, 0, sizeof(int) * d.cap, h->stream));
+  HIP_TRY(hipMemsetAsync(d_removed, 0, sizeof(unsigned long long), h->stream));
+  // rays are cast from the ALREADY PLACED points (identity here), so that the de-duplication and the rays see the same coordinates
+  dense_carve_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)placed.pts, first, n, mat34(nullptr), sp[0], sp[1], sp[2], d.voxel,
+                                                                neighborhood_radius, max_raytracing_length, truncation_distance, d.dev, mark);
+  dense_erase_marked_kernel<<<grid_for(d.cap), kBlock, 0, h->stream>>>(d.dev, d.cap, mark, d_removed);
+  HIP_TRY(hipGetLastError());
+  unsigned long long removed = 0;
+  rc = read_back(h, {{&removed, d_removed, sizeof(removed)}});
+  if (rc) return rc;
+  if (n_removed) *n_removed = (size_t)removed;
+  return O3DS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3550,23 +3583,10 @@ int o3ds_select_by_index(o3ds_handle h, o3ds_cloud in, const uint32_t* keep_idx,
   box_copy(o, *c);  // a subset
   if (m) {
     uint32_t* d_idx = nullptr;
-    const size_t psz = p4_size(c->precision);
     TMP_ALLOC(d_idx, sizeof(uint32_t) * m);
     HIP_TRY(hipMemcpyAsync(d_idx, keep_idx, sizeof(uint32_t) * m, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(dev_alloc(h, (void**)&o.pts, psz * m));
-    if (c->nrm) HIP_TRY(dev_alloc(h, (void**)&o.nrm, psz * m));
-    if (c->precision == O3DS_PRECISION_F64)
-      gather_kernel<P4d><<<grid_for(m), kBlock, 0, h->stream>>>((const P4d*)c->pts, (const P4d*)c->nrm, d_idx, m, (P4d*)o.pts, (P4d*)o.nrm);
-    else
-      gather_kernel<P4f><<<grid_for(m), kBlock, 0, h->stream>>>((const P4f*)c->pts, (const P4f*)c->nrm, d_idx, m, (P4f*)o.pts, (P4f*)o.nrm);
-    if (c->col) {
-      HIP_TRY(dev_alloc(h, (void**)&o.col, psz * m));
-      if (c->precision == O3DS_PRECISION_F64)
-        gather_kernel<P4d><<<grid_for(m), kBlock, 0, h->stream>>>((const P4d*)c->col, nullptr, d_idx, m, (P4d*)o.col, nullptr);
-      else
-        gather_kernel<P4f><<<grid_for(m), kBlock, 0, h->stream>>>((const P4f*)c->col, nullptr, d_idx, m, (P4f*)o.col, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
+    const int rc = DISPATCH(c->precision, gather_cloud, h, *c, d_idx, m, o);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));  // keep_idx may be released by the caller
   }
   o_guard.release();
@@ -3763,8 +3783,7 @@ int voxelize_within_volume_impl(o3ds_handle h, o3ds_cloud map, double voxel_size
   if (voxel_size <= 0.0 || m->n == 0) return O3DS_OK;  // helpers.cpp:119-123 / Submap.cpp:139: unchanged
   CloudRec o;
   const CropDev cd = to_dev(crop);
-  int rc = m->precision == O3DS_PRECISION_F64 ? voxel_reduce_t<P4d>(h, *m, 1, voxel_size, cd, o, false, merge_np, merge_nv)
-                                              : voxel_reduce_t<P4f>(h, *m, 1, voxel_size, cd, o, false, merge_np, merge_nv);
+  int rc = DISPATCH(m->precision, voxel_reduce_t, h, *m, 1, voxel_size, cd, o, false, merge_np, merge_nv);
   if (rc) {
     free_cloud(h, o);
     return rc;
@@ -3912,21 +3931,9 @@ int pm_enter_t(o3ds_handle h, CloudRec& c, double voxel, double max_corr_hint, s
   d.spts = c.spts;
   d.snrm = c.snrm;
   d.pool_cap = (int)pool;
-  // counters: the handle's block of zeros (build_grid_t's: counted up, scanned, counted back down to zero by the scatter)
-  if (h->cells_cap < table + 1) {
-    if (h->d_cells) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_cells);
-      h->d_cells = nullptr;
-      h->cells_cap = 0;
-    }
-    const size_t want = table + 1 + table / 4;
-    if (hipMalloc((void**)&h->d_cells, sizeof(int) * want) != hipSuccess) return fail(h, O3DS_ERR_OOM, "persistent map: cell counters allocation failed");
-    h->cells_cap = want;
-    h->cells_clean = false;
-  }
-  if (!h->cells_clean) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
-  h->cells_clean = false;
+  int rc = cell_counters(h, table);  // build_grid_t's: counted up, scanned, counted back down to zero by the scatter
+  if (rc) return rc;
+  if (!h->d_cells) return fail(h, O3DS_ERR_OOM, "persistent map: cell counters allocation failed");
   HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * kPmCounters, h->stream));
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(d.counters + kPmN), (int)n, 1, h->stream));
   int* cell_id = nullptr;
@@ -3936,7 +3943,7 @@ int pm_enter_t(o3ds_handle h, CloudRec& c, double voxel, double max_corr_hint, s
   pm_enter_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(d, ni);
   pm_cell_count_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(d, ni, h->d_cells, cell_id);
   pm_row_slack_kernel<<<grid_for(pm->rows * 64), kBlock, 0, h->stream>>>(h->d_cells, (int)pm->rows, g.nx, d.row_cap, d.row_flag);
-  int rc = exclusive_scan_int(h, h->d_cells, cs, table + 1);
+  rc = exclusive_scan_int(h, h->d_cells, cs, table + 1);
   if (rc) return rc;
   pm_row_finish_kernel<<<grid_for(pm->rows), kBlock, 0, h->stream>>>(h->d_cells, cs, (int)pm->rows, g.nx, d.counters + kPmPoolTop);
   pm_scatter_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(d, ni, cell_id, h->d_cells);
@@ -3995,37 +4002,10 @@ int pm_insert_t(o3ds_handle h, CloudRec& c, const CloudRec& scan, const double T
   const P4* scan_col = c.col ? (const P4*)scan.col : nullptr;  // (an uncoloured map ignores a scan's colours, as operator+= does)
   const int t_now = pm->t + 1;
   // scratch: the voxel table of VoxelDownSample, the chained scan's tiles
-  size_t tcap = 1024;
-  while (tcap < 2 * ms) tcap <<= 1;
-  if (h->voxtab_cap < tcap) {
-    if (h->d_voxtab) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_voxtab);
-      h->d_voxtab = nullptr;
-      h->voxtab_cap = 0;
-    }
-    if (hipMalloc((void**)&h->d_voxtab, kVoxSlotBytes * tcap + 16) != hipSuccess) return fail(h, O3DS_ERR_OOM, "map_insert_scan: voxel table allocation failed");
-    h->voxtab_cap = tcap;
-    h->voxtab_clean = false;
-  }
-  tcap = h->voxtab_cap;
-  unsigned char* tab = h->d_voxtab;
-  VoxTable t{(VoxSlot*)tab, (unsigned int*)(tab + kVoxSlotBytes * tcap), (unsigned int)(tcap - 1)};
-  if (!h->voxtab_clean) HIP_TRY(hipMemsetAsync(tab, 0xff, kVoxSlotBytes * tcap + 16, h->stream));
-  h->voxtab_clean = false;
-  const size_t n_tiles = (ms + kVoxTile - 1) / kVoxTile;
-  if (h->tiles_cap < n_tiles) {
-    if (h->d_tiles) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_tiles);
-      h->d_tiles = nullptr;
-      h->tiles_cap = 0;
-    }
-    const size_t want = std::max<size_t>(n_tiles + n_tiles / 4, 1024);
-    if (hipMalloc((void**)&h->d_tiles, sizeof(unsigned long long) * want) != hipSuccess) return fail(h, O3DS_ERR_OOM, "map_insert_scan: scan state allocation failed");
-    HIP_TRY(hipMemsetAsync(h->d_tiles, 0, sizeof(unsigned long long) * want, h->stream));
-    h->tiles_cap = want;
-  }
+  VoxTable t{};
+  size_t n_tiles = 0;
+  const int rs = vox_scratch(h, ms, "map_insert_scan", &t, &n_tiles);
+  if (rs) return rs;
   P4 *placed = nullptr, *placed_nrm = nullptr;
   int *lead_slot = nullptr, *run_next = nullptr, *run_len = nullptr, *order = nullptr, *d_groups = nullptr;
   uint32_t* starts = nullptr;
@@ -4041,9 +4021,7 @@ int pm_insert_t(o3ds_handle h, CloudRec& c, const CloudRec& scan, const double T
   TMP_ALLOC(piece, sizeof(int2) * ms);
   TMP_ALLOC(group_key, sizeof(unsigned long long) * ms);
   TMP_ALLOC(d_groups, sizeof(int) * 16);
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int cc = 0; cc < 4; ++cc) M.m[r * 4 + cc] = T[cc * 4 + r];
+  const Mat34 M = mat34(T);
   if (++h->scan_gen == 0) h->scan_gen = 1;
   const CountRef n_scan = count_ref(h, scan);
   const CountPub groups_pub{d_groups, nullptr, 0};
@@ -4094,13 +4072,12 @@ int pm_exit_t(o3ds_handle h, CloudRec& c) {
   HIP_TRY(hipMemsetAsync(d_np, 0, sizeof(unsigned long long), h->stream));
   pm_view_key_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(pm->dev, (int)n, pm->t, hi, lo, v0, d_np);
   // order by (hi, lo): two stable sorts, least significant key first
-  size_t tb = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, lo, k1, v0, v1, n, 0, 64, h->stream));
-  void* tmp = nullptr;
-  TMP_ALLOC(tmp, tb ? tb : 16);
-  HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, lo, k1, v0, v1, n, 0, 64, h->stream));
+  SortTemp temp;  // (one temporary serves both sorts)
+  rc = sort_pairs(h, lo, k1, v0, v1, n, 64, &temp);
+  if (rc) return rc;
   pm_gather_u64_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(hi, v1, n, lo);  // lo := hi in the order of the first sort
-  HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, lo, k1, v1, v0, n, 0, 64, h->stream));
+  rc = sort_pairs(h, lo, k1, v1, v0, n, 64, &temp);
+  if (rc) return rc;
   unsigned long long n_pass = 0;
   rc = read_back(h, {{&n_pass, d_np, sizeof(n_pass)}});
   if (rc) return rc;
@@ -4117,15 +4094,7 @@ int pm_exit_t(o3ds_handle h, CloudRec& c) {
     HIP_TRY(hipGetLastError());
   }
   pm_release(h, c);
-  free_index(h, c);
-  free_points(h, c);
-  if (c.nrm) dev_free(h, c.nrm);
-  if (c.col) dev_free(h, c.col);
-  c.pts = np;
-  c.nrm = nn;
-  c.col = nc;
-  c.n = live;
-  c.cap = live > 0 ? room : 0;
+  replace_arrays(h, c, np, nn, nc, live, live > 0 ? room : 0);
   c.vox_first = (long long)n_pass;
   c.vox_count = live - (size_t)n_pass;
   return O3DS_OK;
@@ -4137,7 +4106,7 @@ namespace {
 int pm_exit(o3ds_handle h, CloudRec& c) {
   if (!c.pm) return O3DS_OK;
   ArenaScope arena_scope(h);
-  return c.precision == O3DS_PRECISION_F64 ? pm_exit_t<P4d>(h, c) : pm_exit_t<P4f>(h, c);
+  return DISPATCH(c.precision, pm_exit_t, h, c);
 }
 }  // namespace
 
@@ -4206,17 +4175,14 @@ int o3ds_dense_map_insert(o3ds_handle h, o3ds_dense_map id, o3ds_cloud cloud, co
   auto it = h->dense_maps.find(id);
   CloudRec* c = find_cloud(h, cloud);
   if (it == h->dense_maps.end() || !c) return fail(h, O3DS_ERR_INVALID_ARG, "dense_map_insert: unknown id");
-  return c->precision == O3DS_PRECISION_F64 ? dense_insert_t<P4d>(h, it->second, *c, T) : dense_insert_t<P4f>(h, it->second, *c, T);
+  return DISPATCH(c->precision, dense_insert_t, h, it->second, *c, T);
 }
 
 extern "C++" {
 namespace {
 template <typename P4>
 int export_rows_t(o3ds_handle h, const CloudRec& c, const double T[16], double voxel, int world, double* d_rows, long long* d_counts) {
-  Mat34 M{};
-  if (T)
-    for (int r = 0; r < 3; ++r)
-      for (int col = 0; col < 4; ++col) M.m[r * 4 + col] = T[col * 4 + r];
+  const Mat34 M = mat34(T);  // (null: the kernels are told not to place the points)
   HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(long long) * (size_t)world, h->stream));
   if (c.n == 0) return O3DS_OK;
   int* owner = nullptr;
@@ -4251,15 +4217,14 @@ int o3ds_cloud_export_rows_by_owner(o3ds_handle h, o3ds_cloud cloud, const doubl
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "export_rows_by_owner: unknown cloud id");
   if (!(voxel_size > 0.0) || world < 1 || world > 64 || !d_counts || (c->n && !d_rows))
     return fail(h, O3DS_ERR_INVALID_ARG, "export_rows_by_owner: voxel_size > 0, 1 <= world <= 64, non-null buffers");
-  return c->precision == O3DS_PRECISION_F64 ? export_rows_t<P4d>(h, *c, T, voxel_size, world, d_rows, d_counts)
-                                            : export_rows_t<P4f>(h, *c, T, voxel_size, world, d_rows, d_counts);
+  return DISPATCH(c->precision, export_rows_t, h, *c, T, voxel_size, world, d_rows, d_counts);
 }
 
 int o3ds_cloud_import_rows(o3ds_handle h, const double* d_rows, size_t n, int has_normals, o3ds_cloud* out) {
   CHECK_HANDLE(h);
   if (!out || (n && !d_rows)) return fail(h, O3DS_ERR_INVALID_ARG, "import_rows: null argument");
   CloudRec c;
-  const int rc = h->precision == O3DS_PRECISION_F64 ? import_rows_t<P4d>(h, d_rows, n, has_normals, c) : import_rows_t<P4f>(h, d_rows, n, has_normals, c);
+  const int rc = DISPATCH(h->precision, import_rows_t, h, d_rows, n, has_normals, c);
   if (rc) {
     free_cloud(h, c);
     return rc;
@@ -4282,7 +4247,7 @@ int o3ds_dense_map_to_cloud(o3ds_handle h, o3ds_dense_map id, o3ds_cloud* out) {
   auto it = h->dense_maps.find(id);
   if (it == h->dense_maps.end() || !out) return fail(h, O3DS_ERR_INVALID_ARG, "dense_map_to_cloud: bad argument");
   CloudRec o;
-  const int rc = h->precision == O3DS_PRECISION_F64 ? dense_to_cloud_t<P4d>(h, it->second, o) : dense_to_cloud_t<P4f>(h, it->second, o);
+  const int rc = DISPATCH(h->precision, dense_to_cloud_t, h, it->second, o);
   if (rc) {
     free_cloud(h, o);
     return rc;
@@ -4297,10 +4262,7 @@ int o3ds_dense_map_transform(o3ds_handle h, o3ds_dense_map id, const double T[16
   if (it == h->dense_maps.end() || !T) return fail(h, O3DS_ERR_INVALID_ARG, "dense_map_transform: bad argument");
   DenseRec& d = it->second;
   if (d.cap == 0) return O3DS_OK;
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int col = 0; col < 4; ++col) M.m[r * 4 + col] = T[col * 4 + r];
-  dense_transform_kernel<<<grid_for(d.cap), kBlock, 0, h->stream>>>(d.dev, d.cap, M);
+  dense_transform_kernel<<<grid_for(d.cap), kBlock, 0, h->stream>>>(d.dev, d.cap, mat34(T));
   HIP_TRY(hipGetLastError());
   return O3DS_OK;
 }
@@ -4315,67 +4277,9 @@ int o3ds_dense_map_carve(o3ds_handle h, o3ds_dense_map id, o3ds_cloud scan, cons
   if (!(neighborhood_radius > 0.0))
     return fail(h, O3DS_ERR_INVALID_ARG, "dense_map_carve: neighborhood radius must be > 0 (the ray step is 2 * radius)");
   if (n_removed) *n_removed = 0;
-  DenseRec& d = it->second;
-  const size_t n = c->n;
-  if (d.cap == 0 || n == 0) return O3DS_OK;  // cloud->empty() (Submap.cpp:128)
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int col = 0; col < 4; ++col) M.m[r * 4 + col] = scan_pose ? scan_pose[col * 4 + r] : (r == col ? 1.0 : 0.0);
-  // removeDuplicatePointsWithinSameVoxels on the PLACED scan: keys of the placed points, stable sort, heads of the key segments
-  CloudRec placed;
-  int rc = c->precision == O3DS_PRECISION_F64 ? transform_t<P4d>(h, *c, scan_pose ? scan_pose : kIdentity16, placed)
-                                              : transform_t<P4f>(h, *c, scan_pose ? scan_pose : kIdentity16, placed);
-  if (rc) {
-    free_cloud(h, placed);
-    return rc;
-  }
-  unsigned long long *k0 = nullptr, *k1 = nullptr, *d_removed = nullptr;
-  uint32_t *v0 = nullptr, *v1 = nullptr;
-  int *first = nullptr, *mark = nullptr;
-  TMP_ALLOC(k0, sizeof(unsigned long long) * n);
-  TMP_ALLOC(k1, sizeof(unsigned long long) * n);
-  TMP_ALLOC(v0, sizeof(uint32_t) * n);
-  TMP_ALLOC(v1, sizeof(uint32_t) * n);
-  TMP_ALLOC(first, sizeof(int) * n);
-  TMP_ALLOC(mark, sizeof(int) * d.cap);
-  TMP_ALLOC(d_removed, sizeof(unsigned long long));
-  CropDev none{};
-  if (c->precision == O3DS_PRECISION_F64)
-    voxel_key_kernel<P4d><<<grid_for(n), kBlock, 0, h->stream>>>((const P4d*)placed.pts, n, 1, 0.0, 0.0, 0.0, d.voxel, none, k0, v0);
-  else
-    voxel_key_kernel<P4f><<<grid_for(n), kBlock, 0, h->stream>>>((const P4f*)placed.pts, n, 1, 0.0, 0.0, 0.0, d.voxel, none, k0, v0);
-  size_t temp_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-  void* temp = nullptr;
-  TMP_ALLOC(temp, temp_bytes ? temp_bytes : 16);
-  HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, k0, k1, v0, v1, n, 0, 64, h->stream));
-  first_of_voxel_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(k1, v1, n, first);
-  HIP_TRY(hipMemsetAsync(mark, 0, sizeof(int) * d.cap, h->stream));
-  HIP_TRY(hipMemsetAsync(d_removed, 0, sizeof(unsigned long long), h->stream));
-  // rays are cast from the ALREADY PLACED points (identity here), so that the de-duplication and the rays see the same coordinates
-  Mat34 I;
-  for (int r = 0; r < 3; ++r)
-    for (int col = 0; col < 4; ++col) I.m[r * 4 + col] = r == col ? 1.0 : 0.0;
-  const double* sp = sensor_position;
-  if (c->precision == O3DS_PRECISION_F64)
-    dense_carve_kernel<P4d><<<grid_for(n), kBlock, 0, h->stream>>>((const P4d*)placed.pts, first, n, I, sp[0], sp[1], sp[2], d.voxel,
-                                                                  neighborhood_radius, max_raytracing_length, truncation_distance, d.dev, mark);
-  else
-    dense_carve_kernel<P4f><<<grid_for(n), kBlock, 0, h->stream>>>((const P4f*)placed.pts, first, n, I, sp[0], sp[1], sp[2], d.voxel,
-                                                                  neighborhood_radius, max_raytracing_length, truncation_distance, d.dev, mark);
-  dense_erase_marked_kernel<<<grid_for(d.cap), kBlock, 0, h->stream>>>(d.dev, d.cap, mark, d_removed);
-  HIP_TRY(hipGetLastError());
-  unsigned long long removed = 0;
-  {
-    const int rb = read_back(h, {{&removed, d_removed, sizeof(removed)}});
-    if (rb) {
-      free_cloud(h, placed);
-      return rb;
-    }
-  }
-  free_cloud(h, placed);
-  if (n_removed) *n_removed = (size_t)removed;
-  return O3DS_OK;
+  if (it->second.cap == 0 || c->n == 0) return O3DS_OK;  // cloud->empty() (Submap.cpp:128)
+  return DISPATCH(c->precision, dense_carve_t, h, it->second, *c, scan_pose, sensor_position, neighborhood_radius, max_raytracing_length, truncation_distance,
+                  n_removed);
 }
 
 int o3ds_dense_map_count_occupied(o3ds_handle h, o3ds_dense_map id, o3ds_cloud cloud, const double T[16], size_t* n_hits) {
@@ -4387,9 +4291,7 @@ int o3ds_dense_map_count_occupied(o3ds_handle h, o3ds_dense_map id, o3ds_cloud c
   *n_hits = 0;
   DenseRec& d = it->second;
   if (d.cap == 0 || c->n == 0) return O3DS_OK;
-  Mat34 M;
-  for (int r = 0; r < 3; ++r)
-    for (int col = 0; col < 4; ++col) M.m[r * 4 + col] = T ? T[col * 4 + r] : (r == col ? 1.0 : 0.0);
+  const Mat34 M = mat34(T);
   unsigned long long* d_hits = nullptr;
   TMP_ALLOC(d_hits, sizeof(unsigned long long));
   HIP_TRY(hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), h->stream));
@@ -4419,11 +4321,8 @@ int o3ds_overlap_indices(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, co
   if (min_points_per_voxel < 1) return fail(h, O3DS_ERR_INVALID_ARG, "minNumPointsPerVoxel must be >= 1");  // assert_ge, helpers.cpp:310
   if (s->n && t->n && s->precision != t->precision) return fail(h, O3DS_ERR_INVALID_ARG, "overlap_indices: precision mismatch");
   static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "index type");
-  return s->precision == O3DS_PRECISION_F64
-             ? overlap_t<P4d>(h, *s, *t, source_to_target, voxel_size, min_points_per_voxel, (unsigned long long*)idx_source, n_idx_source,
-                              (unsigned long long*)idx_target, n_idx_target)
-             : overlap_t<P4f>(h, *s, *t, source_to_target, voxel_size, min_points_per_voxel, (unsigned long long*)idx_source, n_idx_source,
-                              (unsigned long long*)idx_target, n_idx_target);
+  return DISPATCH(s->precision, overlap_t, h, *s, *t, source_to_target, voxel_size, min_points_per_voxel, (unsigned long long*)idx_source, n_idx_source,
+                  (unsigned long long*)idx_target, n_idx_target);
 }
 
 int o3ds_map_carve(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, const double map_to_range_sensor[16], const o3ds_crop* map_builder_crop,
@@ -4446,9 +4345,7 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
       PMapRec* pm = pmc->pm;
       const PmDev d = pm->dev;
       const double* T = map_to_range_sensor;
-      Mat34 M;
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) M.m[r * 4 + c] = T[c * 4 + r];
+      const Mat34 M = mat34(T);
       const CropDev cd = to_dev(map_builder_crop);
       unsigned int* block_bits = nullptr;
       TMP_ALLOC(block_bits, sizeof(unsigned int) << (kCarveBitsLog2 - 5));
@@ -4487,8 +4384,7 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
   CloudRec gone;
   CloudGuard gone_guard(h, gone);
   gone.precision = m->precision;
-  const int rc = m->precision == O3DS_PRECISION_F64 ? carve_t<P4d>(h, *m, *s, map_to_range_sensor, cd, *params, &removed, removed_out ? &gone : nullptr)
-                                                    : carve_t<P4f>(h, *m, *s, map_to_range_sensor, cd, *params, &removed, removed_out ? &gone : nullptr);
+  const int rc = DISPATCH(m->precision, carve_t, h, *m, *s, map_to_range_sensor, cd, *params, &removed, removed_out ? &gone : nullptr);
   if (n_removed) *n_removed = removed;
   if (rc) return rc;
   if (removed_out) {
@@ -4572,9 +4468,7 @@ int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const d
     CloudRec joined;
     placed.n = s->n;
     box_union(joined, *m, placed);
-    Mat34 M;
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 4; ++c) M.m[r * 4 + c] = T[c * 4 + r];
+    const Mat34 M = mat34(T);
     if (m->precision == O3DS_PRECISION_F64)
       transform_kernel<P4d><<<grid_for(s->n), kBlock, 0, h->stream>>>((const P4d*)s->pts, (const P4d*)s->nrm, s->n, M, T[3], T[7], T[11], T[15], (P4d*)m->pts,
                                                                       (P4d*)m->nrm, m->n);

@@ -11,17 +11,9 @@ constexpr size_t kBatchMaxWorkgroups = O3DS_BATCH_MAX_WORKGROUPS;
 
 template <typename P4>
 void launch_batch_accumulate_t(o3ds_handle h, const IcpBatchArgs& ba, int nblocks, bool crop, bool gicp) {
-  if (gicp) {
-    if (crop)
-      icp_batch_accumulate_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(ba);
-    else
-      icp_batch_accumulate_kernel<P4, false, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(ba);
-  } else {
-    if (crop)
-      icp_batch_accumulate_kernel<P4, true, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(ba);
-    else
-      icp_batch_accumulate_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(ba);
-  }
+  with_crop_and_estimator(crop, gicp, [&](auto crop_c, auto gicp_c) {
+    icp_batch_accumulate_kernel<P4, decltype(crop_c)::value, kIcpBlock, 4, decltype(gicp_c)::value><<<nblocks, kIcpBlock, 0, h->stream>>>(ba);
+  });
 }
 
 void launch_batch_accumulate(o3ds_handle h, int precision, const IcpBatchArgs& ba, int nblocks, bool crop, bool gicp) {

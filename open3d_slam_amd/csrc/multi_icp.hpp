@@ -8,18 +8,9 @@ namespace {
 
 template <typename P4>
 void launch_multi_accumulate_t(o3ds_handle h, const IcpMultiArgs& ma, int nblocks) {
-  const bool crop = h->session_crop;
-  if (h->session_method == O3DS_ICP_GENERALIZED) {
-    if (crop)
-      icp_multi_accumulate_kernel<P4, true, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
-    else
-      icp_multi_accumulate_kernel<P4, false, kIcpBlock, 4, true><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
-  } else {
-    if (crop)
-      icp_multi_accumulate_kernel<P4, true, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
-    else
-      icp_multi_accumulate_kernel<P4, false, kIcpBlock, 4, false><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
-  }
+  with_crop_and_estimator(h->session_crop, h->session_method == O3DS_ICP_GENERALIZED, [&](auto crop, auto gicp) {
+    icp_multi_accumulate_kernel<P4, decltype(crop)::value, kIcpBlock, 4, decltype(gicp)::value><<<nblocks, kIcpBlock, 0, h->stream>>>(ma);
+  });
 }
 
 void launch_multi_accumulate(o3ds_handle h, const IcpMultiArgs& ma, int nblocks) {

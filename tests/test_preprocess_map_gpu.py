@@ -1439,6 +1439,86 @@ def test_persistent_map_is_bitwise_the_array_form(prec, case):
     assert got[-1][2] > 5000
 
 
+@pytest.fixture(scope="module")
+def scratch_clouds():
+    """seeded samples of the synthetic scene (a 60 m x 60 m x 10 m hall), with normals, by size"""
+    scene = syn.make_scene()
+    return {n: syn.sample_map(scene, n, seed=100 + k) for k, n in enumerate((400, 3_000, 40_000, 1_100_000))}
+
+
+def _scratch_history(be, clouds, sizes, reverse):
+    """every operation that uses a scratch block the handle owns and grows (the voxel table, the chained scan's tiles, the per-cell
+    counters), on one handle; `reverse`: the inputs of each kind in descending instead of ascending size.  Returns what each
+    (operation, input) left, as bytes."""
+    out = {}
+    ids = {n: be.upload(*clouds[n]) for n in sizes}
+
+    def look(key, cid):
+        p, n = be.download(cid)
+        out[key] = (p.tobytes(), n.tobytes())
+        be.free(cid)
+
+    def insert(m, k, hint):  # (the insertions of a map keep their order on both handles: a map is what its history made it)
+        T = (np.eye(4), syn.make_pose([1.5, 0.4, 0.0], [0.0, 0.0, 4.0]), syn.make_pose([3.0, 0.8, 0.0], [0.0, 0.0, 8.0]))[k]
+        crop = backend.make_crop(backend.CROP_MIN_MAX_RADIUS, center=T[:3, 3], rmin=0.0, rmax=12.0)
+        be.map_insert_scan(m, ids[(40_000, 3_000, 40_000)[k]], T, 0.2, crop, max_corr_hint=hint)
+        assert be.is_persistent_map(m) == (k >= 1)  # the second insertion enters the persistent form
+
+    # the voxel table (1 024, 8 192, 131 072 slots: the next power of two >= 2 n; 2 m voxels: 2 499 of the 40 000 points) and the tiles
+    # (1 100 000 points: 1 075 tiles, beyond the 1 024 of the first allocation); between them three insertions into one map, whose
+    # persistent form shares both blocks and, entering, counts into the cell counters (hint 4 m: cells of 1 m, 7e4 of them)
+    vol = backend.make_crop(backend.CROP_MAX_RADIUS, rmax=20.0)
+    m = be.upload(np.zeros((0, 3)))
+    for k, n in enumerate(sizes[::-1] if reverse else sizes):
+        look(("voxel_down_sample", n), be.voxel_down_sample(ids[n], 2.0))
+        look(("crop_voxel_down_sample", n), be.crop_voxel_down_sample(ids[n], vol, 2.0))
+        if k < 3:
+            insert(m, k, 4.0)
+    look(("map",), m)
+    # the cell counters: an index with cells of 2 m (4 500), then of 0.5 m (2.9e5: the block grows); registrations against each until it
+    # has its replica (the fourth), whose counter table (nx (ny + 2) (nz + 2)) is larger than the index's
+    T0 = syn.make_pose([0.05, -0.03, 0.02], [0.2, -0.1, 0.3])
+    for cell in ((0.5, 2.0) if reverse else (2.0, 0.5)):
+        be.build_index(ids[40_000], 1.0, cell_size=cell)
+        for k in range(6):
+            r = be.icp_point_to_plane_dev(ids[3_000], ids[40_000], 1.0, init=T0, max_iter=10, rel_fitness=0.0, rel_rmse=0.0)
+            assert r["n_corr"] > 1000
+            out[("register", cell, k)] = (r["transformation"].tobytes(), r["n_corr"])
+            if be.index_replica(ids[40_000]) > 0:
+                break
+        assert be.index_replica(ids[40_000]) > 0
+    # ... and their third user, the row table of a map entering the persistent form (hint 1 m: cells of 0.2 m, 8.6e6 of them)
+    m = be.upload(np.zeros((0, 3)))
+    insert(m, 0, 1.0)
+    insert(m, 1, 1.0)
+    look(("fresh map",), m)
+    return out
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_shared_scratch_blocks_do_not_remember_their_history(prec, scratch_clouds):
+    """The voxel table, the tile records and the cell counters belong to the handle, are shared by VoxelDownSample, the persistent map,
+    the index build, the replica build and the row table, grow on demand and are left clean by their users instead of being cleared.
+    Two handles run the same operations on the same clouds, one with the inputs of each kind in ascending size (every block grows
+    step by step, every user meets what a smaller one left), one in descending size (every block is allocated once at its largest):
+    the same kernels on the same data, so every result -- points and normals, the 16 pose doubles and n_corr -- is the same bytes.
+    What is not reversed: the insertions into a map (a map is its history) and the order of the kinds.  The 1 100 000-point cloud, the
+    smallest that outgrows the tile array's first allocation, runs with f32 storage only."""
+    p = backend.PRECISION_F64 if prec == "f64" else backend.PRECISION_F32
+    sizes = (400, 3_000, 40_000) + ((1_100_000,) if prec == "f32" else ())
+    got = []
+    for reverse in (False, True):
+        be = backend.Backend(0, p)
+        try:
+            got.append(_scratch_history(be, scratch_clouds, sizes, reverse))
+        finally:
+            be.close()
+    assert got[0].keys() == got[1].keys() and len(got[0]) >= 2 * len(sizes) + 2 + 8
+    for key in got[0]:
+        assert got[0][key] == got[1][key], key
+    assert len(got[0][("map",)][0]) > 24 * 40_000  # (most points lie outside the 12 m volumes and pass through unmerged)
+
+
 def test_normals_with_exact_ties_duplicates_and_tiny_clouds(backend_f64, oracle):
     """The neighbour order (d2, original index) decides everything where distances tie EXACTLY: a regular lattice (every point has
     whole shells of equidistant neighbours, so the max_nn-th place is always tied), duplicated points (d2 = 0 several times), and
