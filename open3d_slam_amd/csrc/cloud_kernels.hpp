@@ -308,6 +308,26 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const P4* __restrict__ p
 struct Mat34 {
   double m[12];  // row-major 3x4
 };
+struct Vec3d {
+  double x, y, z;
+};
+// The three placements of o3d_slam::transform (helpers.cpp:273-305), in double and in the reference's order of operations; the callers
+// cast to their storage type.  (placed_point, of the owner kernels, keeps its own copy of the rows: through place_point both kernels
+// come out with other register counts.)  T * (p, 1), the affine rows only:
+__device__ __forceinline__ Vec3d place_point(const Mat34& M, double x, double y, double z) {
+  return {M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
+          M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11]};
+}
+// ... divided by the fourth row's w, as the reference does for a cloud (helpers.cpp:289-290: xyz / new_point(3))
+__device__ __forceinline__ Vec3d place_point_homogeneous(const Mat34& M, double w0, double w1, double w2, double w3, double x, double y, double z) {
+  const double w = w0 * x + w1 * y + w2 * z + w3;
+  return {(M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3]) / w, (M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7]) / w,
+          (M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11]) / w};
+}
+// T * (n, 0): normals rotate, nothing is added (helpers.cpp:294-296)
+__device__ __forceinline__ Vec3d rotate_normal(const Mat34& M, double a, double b, double c) {
+  return {M.m[0] * a + M.m[1] * b + M.m[2] * c, M.m[4] * a + M.m[5] * b + M.m[6] * c, M.m[8] * a + M.m[9] * b + M.m[10] * c};
+}
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void transform_kernel(const P4* __restrict__ pts, const P4* __restrict__ nrm, size_t n, Mat34 M,
                                                             double w0, double w1, double w2, double w3, P4* __restrict__ out_pts,
@@ -315,21 +335,16 @@ __global__ __launch_bounds__(kBlock) void transform_kernel(const P4* __restrict_
   using R = typename Scalar<P4>::type;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     const P4 p = pts[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const double w = w0 * x + w1 * y + w2 * z + w3;  // helpers.cpp:289-290: xyz / new_point(3)
+    const Vec3d t = place_point_homogeneous(M, w0, w1, w2, w3, (double)p.x, (double)p.y, (double)p.z);
     P4 o;
-    o.x = (R)((M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3]) / w);
-    o.y = (R)((M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7]) / w);
-    o.z = (R)((M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11]) / w);
+    o.x = (R)t.x, o.y = (R)t.y, o.z = (R)t.z;
     o.i = (typename Scalar<P4>::index)(out_off + i);
     out_pts[out_off + i] = o;
     if (nrm) {
       const P4 q = nrm[i];
-      const double a = (double)q.x, b = (double)q.y, c = (double)q.z;
+      const Vec3d r = rotate_normal(M, (double)q.x, (double)q.y, (double)q.z);
       P4 on;
-      on.x = (R)(M.m[0] * a + M.m[1] * b + M.m[2] * c);  // helpers.cpp:294-296: T * (n, 0)
-      on.y = (R)(M.m[4] * a + M.m[5] * b + M.m[6] * c);
-      on.z = (R)(M.m[8] * a + M.m[9] * b + M.m[10] * c);
+      on.x = (R)r.x, on.y = (R)r.y, on.z = (R)r.z;
       on.i = 0;
       out_nrm[out_off + i] = on;
     }
@@ -446,6 +461,28 @@ __host__ __device__ __forceinline__ unsigned long long pack_key(long long kx, lo
   const unsigned long long bz = (unsigned long long)(kz + (1ll << 20)) & 0x1FFFFFull;
   return (bz << 42) | (by << 21) | bx;
 }
+// The voxel of a point, in the four roundings this backend bins points with.  They disagree on points that lie on a voxel face
+// (k * 0.1 * (1 / 0.1) and k * 0.1 / 0.1 fall on different sides of k) and beyond the range of an int, so none stands in for another.
+// [O3D] VoxelDownSample (call site helpers.cpp:107-113): floor((p - voxel_min_bound) / v) -- a division, anchored at the data's own corner
+__device__ __forceinline__ unsigned long long key_from_origin(double x, double y, double z, double ox, double oy, double oz, double v) {
+  return pack_key((long long)floor((x - ox) / v), (long long)floor((y - oy) / v), (long long)floor((z - oz) / v));
+}
+// voxelizeWithinCroppingVolume (helpers.cpp:153) and the sorted map merge: floor(p * (1 / v)) -- a product with the rounded reciprocal,
+// anchored at the world's origin, widened straight to 64 bits (no pass through an int, unlike key_world_int below)
+__device__ __forceinline__ unsigned long long key_world(double x, double y, double z, double inv) {
+  return pack_key((long long)floor(x * inv), (long long)floor(y * inv), (long long)floor(z * inv));
+}
+// getVoxelIdx(p, inverse size) (VoxelHashMap.hpp:47-50) as the dense map and the carving's VoxelMap call it: the same product, but the
+// floor passes through an int, as the Eigen::Vector3i there makes it
+__device__ __forceinline__ long long voxel_index_int(double x, double inv) { return (long long)(int)floor(x * inv); }
+__device__ __forceinline__ unsigned long long key_world_int(double x, double y, double z, double inv) {
+  return pack_key(voxel_index_int(x, inv), voxel_index_int(y, inv), voxel_index_int(z, inv));
+}
+// getVoxelIdx(p, size) (VoxelHashMap.hpp:52-55) as getVoxelsWithinPointNeighborhood calls it (VoxelHashMap.cpp:13-44): floor(p / v)
+// through an int -- a DIVISION by the voxel size where the two above multiply
+__device__ __forceinline__ unsigned long long key_by_division(double x, double y, double z, double v) {
+  return pack_key((long long)(int)floor(x / v), (long long)(int)floor(y / v), (long long)(int)floor(z / v));
+}
 
 // mode 0: data-anchored ([O3D] VoxelDownSample: floor((p - origin)/v));  mode 1: world-anchored (floor(p * (1/v)))
 // (Packing the voxel coordinates relative to a known box -- the cloud's bounding box, or the box around a bounded cropping volume --
@@ -464,9 +501,9 @@ __global__ __launch_bounds__(kBlock) void voxel_key_kernel(const P4* __restrict_
     if ((mode == 1 || filter) && !crop_contains(crop, x, y, z)) {
       k = kPassBit | (unsigned long long)i;
     } else if (mode == 0) {
-      k = pack_key((long long)floor((x - ox) / v), (long long)floor((y - oy) / v), (long long)floor((z - oz) / v));
+      k = key_from_origin(x, y, z, ox, oy, oz, v);
     } else {
-      k = pack_key((long long)floor(x * inv), (long long)floor(y * inv), (long long)floor(z * inv));
+      k = key_world(x, y, z, inv);
     }
     keys[i] = k;
     vals[i] = (uint32_t)i;
@@ -495,14 +532,14 @@ __global__ __launch_bounds__(kBlock) void merge_class_kernel(const P4* __restric
     }
     const P4 p = pts[i];
     const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const unsigned long long vk = pack_key((long long)floor(x * inv), (long long)floor(y * inv), (long long)floor(z * inv));
+    const unsigned long long vk = key_world(x, y, z, inv);
     const bool inside = crop_contains(crop, x, y, z);
     const bool in_v = i >= np && i < np + nv;
     keys[i] = inside ? vk : (kPassBit | (unsigned long long)i);
     cls[i] = inside ? (in_v ? kCntV : 0ull) : kCntPass;
     if (in_v && i > np) {  // the voxel block must still be in key order (a mean that rounding put on the far side of a face breaks it)
       const P4 q = pts[i - 1];
-      const unsigned long long pk = pack_key((long long)floor((double)q.x * inv), (long long)floor((double)q.y * inv), (long long)floor((double)q.z * inv));
+      const unsigned long long pk = key_world((double)q.x, (double)q.y, (double)q.z, inv);
       if (vk < pk) atomicOr(unsorted, 1);
     }
   }
@@ -801,6 +838,33 @@ __global__ __launch_bounds__(kBlock) void segment_last_kernel(const P4* __restri
 // (key -> segment) and one thread per ray marches and probes; marking a point is an idempotent store, no atomics.
 constexpr unsigned long long kEmptyKey = ~0ull;
 
+// Every voxel table of this backend is open addressing with linear steps on the packed key.  `key_at(i)` is the address of slot i's key:
+// the tables differ in their records (bare key arrays, VoxSlot, PmHash), not in how they are probed.
+__device__ __forceinline__ unsigned int table_hash(unsigned long long k) { return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32); }
+// the slot of key k, claimed for it if no slot holds it yet.  (carve_table_insert_kernel keeps its own copy: it stores its value inside
+// the loop, and with the store after a call it comes out with other register counts.)
+template <typename KeyAt>
+__device__ __forceinline__ unsigned int table_claim(KeyAt key_at, unsigned int mask, unsigned long long k) {
+  unsigned int slot = table_hash(k) & mask;
+  while (true) {
+    const unsigned long long prev = atomicCAS(key_at(slot), kEmptyKey, k);
+    if (prev == kEmptyKey || prev == k) return slot;
+    slot = (slot + 1) & mask;
+  }
+}
+// ... or ~0u when the key is not in the table (read-only probe).  (carve_rays_kernel, dense_probe_kernel and dense_mark keep their own
+// copies: they act on the hit inside the loop; asking again whether there was one costs each of their kernels four scalar registers.)
+template <typename KeyAt>
+__device__ __forceinline__ unsigned int table_find(KeyAt key_at, unsigned int mask, unsigned long long k) {
+  unsigned int slot = table_hash(k) & mask;
+  while (true) {
+    const unsigned long long cur = *key_at(slot);
+    if (cur == k) return slot;
+    if (cur == kEmptyKey) return ~0u;
+    slot = (slot + 1) & mask;
+  }
+}
+
 // ---- VoxelDownSample without a sort, in three launches ------------------------------------------------------------------------------------
 // [O3D] VoxelDownSample walks the points once and keeps an unordered_map voxel -> AccumulatedPoint, so a voxel's sum runs over its points
 // in cloud order and (here, as in the oracle) the voxels come out in order of first appearance.  Three kernels, no sort, no size read-back:
@@ -830,6 +894,27 @@ struct VoxTable {
   unsigned int mask;
 };
 constexpr size_t kVoxSlotBytes = sizeof(VoxSlot);
+// One step of the insertion, for a whole wavefront at once (the runs are found by lane): point i carries key k, kEmptyKey for "no
+// entry".  The first lane of every run of equal keys claims the voxel's slot, lowers its smallest point index and pushes the run
+// {first index, length} onto its run list; lead_slot[i] = that slot for a run's first point, -1 for every other point below n.
+__device__ __forceinline__ void vox_run_insert(VoxTable t, unsigned long long k, size_t i, size_t n, int lane, int* __restrict__ lead_slot,
+                                               int* __restrict__ run_next, int* __restrict__ run_len) {
+  const unsigned long long kp = __shfl_up(k, 1, 64);
+  const bool lead = k != kEmptyKey && (lane == 0 || kp != k);
+  const unsigned long long ends = __ballot(lane == 0 || kp != k);  // a run also ends where entries without a key begin
+  int slot = -1;
+  if (lead) {
+    const unsigned long long above = lane == 63 ? 0ull : (ends >> (lane + 1));
+    const int len = above ? (int)__builtin_ctzll(above) + 1 : 64 - lane;
+    const unsigned int sl = table_claim([&](unsigned int j) { return &t.s[j].key; }, t.mask, k);
+    atomicMin(&t.s[sl].first, (unsigned int)i);
+    atomicAdd(&t.s[sl].nrun, 1u);
+    run_next[i] = atomicExch(&t.s[sl].head, (int)i);
+    run_len[i] = len;
+    slot = (int)sl;
+  }
+  if (i < n) lead_slot[i] = slot;
+}
 
 // scan_local_kernel (icp_kernels.hpp) with its input computed on the fly
 template <typename T, typename Load>
@@ -987,28 +1072,9 @@ __global__ __launch_bounds__(kBlock) void vox_insert_kernel(const P4* __restrict
       const P4 p = pts[i];
       const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
       if (!filter || crop_contains(crop, x, y, z))
-        k = pack_key((long long)floor((x - ox) / v), (long long)floor((y - oy) / v), (long long)floor((z - oz) / v));
+        k = key_from_origin(x, y, z, ox, oy, oz, v);
     }
-    const unsigned long long kp = __shfl_up(k, 1, 64);
-    const bool lead = k != kEmptyKey && (lane == 0 || kp != k);
-    const unsigned long long ends = __ballot(lane == 0 || kp != k);  // a run also ends where entries without a key begin
-    int slot = -1;
-    if (lead) {
-      const unsigned long long above = lane == 63 ? 0ull : (ends >> (lane + 1));
-      const int len = above ? (int)__builtin_ctzll(above) + 1 : 64 - lane;
-      unsigned int sl = (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32) & t.mask;
-      while (true) {
-        const unsigned long long prev = atomicCAS(&t.s[sl].key, kEmptyKey, k);
-        if (prev == kEmptyKey || prev == k) break;
-        sl = (sl + 1) & t.mask;
-      }
-      atomicMin(&t.s[sl].first, (unsigned int)i);
-      atomicAdd(&t.s[sl].nrun, 1u);
-      run_next[i] = atomicExch(&t.s[sl].head, (int)i);
-      run_len[i] = len;
-      slot = (int)sl;
-    }
-    if (i < n) lead_slot[i] = slot;
+    vox_run_insert(t, k, i, n, lane, lead_slot, run_next, run_len);
   }
 }
 
@@ -1257,6 +1323,57 @@ __device__ __forceinline__ unsigned int carve_block_bit(unsigned long long key) 
   return (unsigned int)(((key & kCarveBlockMask) * 0x9E3779B97F4A7C15ull) >> (64 - kCarveBitsLog2));
 }
 
+// The ray of one scan point (helpers.cpp:245-251, and 347-377 for the dense map): unit vector from the sensor to the placed point and the
+// length the samples cover.  No ray (valid = false) for a point at the sensor itself, where the reference divides by zero.
+// (carve_rays_kernel keeps its own copy of this and of carve_walk: with either its register counts change.)
+struct CarveRay {
+  double ux, uy, uz, lim;
+  bool valid;
+};
+__device__ __forceinline__ CarveRay carve_ray(double px, double py, double pz, double sx, double sy, double sz, double step, double trunc,
+                                              double max_len) {
+  const double dx = px - sx, dy = py - sy, dz = pz - sz;
+  const double length = sqrt(dx * dx + dy * dy + dz * dz);
+  return {dx / length, dy / length, dz / length, fmax(step, fmin(length - trunc, max_len)), length > 0.0};
+}
+// The samples of a ray, one every `voxel` metres from the sensor: on_hit(key) for every sample whose block of voxels may hold something,
+// kBatch block look-ups at a time (why: see the walk in carve_rays_kernel); what on_hit does is idempotent, the order does not matter.
+template <typename OnHit>
+__device__ __forceinline__ void carve_walk(const CarveRay& ray, double sx, double sy, double sz, double voxel,
+                                           const unsigned int* __restrict__ block_bits, OnHit on_hit) {
+  constexpr int kBatch = 8;
+  const double inv = 1.0 / voxel;
+  double dist = 0.0;
+  while (dist < ray.lim) {
+    unsigned long long ks[kBatch];
+    unsigned int bits[kBatch], words[kBatch];
+    int m = 0;
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u)
+      if (dist < ray.lim) {
+        ks[u] = key_world_int(dist * ray.ux + sx, dist * ray.uy + sy, dist * ray.uz + sz, inv);
+        bits[u] = carve_block_bit(ks[u]);
+        dist += voxel;
+        m = u + 1;
+      }
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u)
+      if (u < m) words[u] = block_bits[bits[u] >> 5];
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) {
+      if (u >= m) break;
+      if (!((words[u] >> (bits[u] & 31u)) & 1u)) continue;  // nothing of the map in this block of voxels
+      on_hit(ks[u]);
+    }
+  }
+}
+// whether the ray removes a map point with this normal: |ray . unit normal| > min_dot (helpers.cpp:257-258)
+__device__ __forceinline__ bool carve_removes(const CarveRay& ray, double a, double b, double c, double min_dot) {
+  const double nl = sqrt(a * a + b * b + c * c);
+  const double dot = nl > 0.0 ? (ray.ux * a + ray.uy * b + ray.uz * c) / nl : 0.0;  // Eigen normalized(): the zero vector stays zero
+  return fabs(dot) > min_dot;
+}
+
 // keys of the map points inside the wide cropping volume, everything else gets the pass-through bit (never probed)
 __global__ __launch_bounds__(kBlock) void carve_table_insert_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ seg_start,
                                                                     size_t n_seg, unsigned long long* __restrict__ tkey, int* __restrict__ tseg,
@@ -1266,7 +1383,7 @@ __global__ __launch_bounds__(kBlock) void carve_table_insert_kernel(const unsign
     if (k & kPassBit) continue;  // segments of points outside the volume
     const unsigned int bit = carve_block_bit(k);
     atomicOr(&block_bits[bit >> 5], 1u << (bit & 31u));
-    unsigned int slot = (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+    unsigned int slot = table_hash(k) & mask;
     while (true) {
       const unsigned long long prev = atomicCAS(&tkey[slot], kEmptyKey, k);
       if (prev == kEmptyKey || prev == k) {
@@ -1290,10 +1407,8 @@ __global__ __launch_bounds__(kBlock) void carve_rays_kernel(const P4* __restrict
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_scan; i += (size_t)gridDim.x * kBlock) {
     const P4 q = scan[i];
     // o3d_slam::transform (helpers.cpp:273-305) of the raw scan into the map frame, then the ray from the sensor position
-    const double x = (double)q.x, y = (double)q.y, z = (double)q.z;
-    const double px = M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], py = M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
-                 pz = M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11];
-    const double dx = px - sx, dy = py - sy, dz = pz - sz;
+    const Vec3d p = place_point(M, (double)q.x, (double)q.y, (double)q.z);
+    const double dx = p.x - sx, dy = p.y - sy, dz = p.z - sz;
     const double length = sqrt(dx * dx + dy * dy + dz * dz);
     if (!(length > 0.0)) continue;
     const double ux = dx / length, uy = dy / length, uz = dz / length;
@@ -1310,8 +1425,7 @@ __global__ __launch_bounds__(kBlock) void carve_rays_kernel(const P4* __restrict
 #pragma unroll
       for (int u = 0; u < kBatch; ++u)
         if (dist < lim) {
-          const double cx = dist * ux + sx, cy = dist * uy + sy, cz = dist * uz + sz;
-          ks[u] = pack_key((long long)(int)floor(cx * inv), (long long)(int)floor(cy * inv), (long long)(int)floor(cz * inv));
+          ks[u] = key_world_int(dist * ux + sx, dist * uy + sy, dist * uz + sz, inv);
           bits[u] = carve_block_bit(ks[u]);
           dist += voxel;
           m = u + 1;
@@ -1324,7 +1438,7 @@ __global__ __launch_bounds__(kBlock) void carve_rays_kernel(const P4* __restrict
         if (u >= m) break;
         if (!((words[u] >> (bits[u] & 31u)) & 1u)) continue;  // nothing of the table in this block of voxels
         const unsigned long long k = ks[u];
-        unsigned int slot = (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+        unsigned int slot = table_hash(k) & mask;
         int seg = -1;
         while (true) {
           const unsigned long long t = tkey[slot];
@@ -1342,10 +1456,7 @@ __global__ __launch_bounds__(kBlock) void carve_rays_kernel(const P4* __restrict
           bool rem = true;
           if (map_nrm) {
             const P4 nn = map_nrm[id];
-            const double a = (double)nn.x, bb = (double)nn.y, c = (double)nn.z;
-            const double nl = sqrt(a * a + bb * bb + c * c);
-            const double dot = nl > 0.0 ? (ux * a + uy * bb + uz * c) / nl : 0.0;  // Eigen normalized(): the zero vector stays zero
-            rem = fabs(dot) > min_dot;
+            rem = carve_removes(CarveRay{ux, uy, uz, lim, true}, (double)nn.x, (double)nn.y, (double)nn.z, min_dot);
           }
           if (rem) flags[id] = 0;  // flags are "keep" flags: 1 = stays in the map
         }
@@ -1414,16 +1525,8 @@ struct DenseDev {
   unsigned int mask;         // cap - 1
 };
 
-__device__ __forceinline__ unsigned int dense_slot_of(unsigned long long k, unsigned int mask) {
-  return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-}
 __device__ __forceinline__ unsigned int dense_find_or_insert(const DenseDev& d, unsigned long long k) {
-  unsigned int slot = dense_slot_of(k, d.mask);
-  while (true) {
-    const unsigned long long prev = atomicCAS(&d.keys[slot], kEmptyKey, k);
-    if (prev == kEmptyKey || prev == k) return slot;
-    slot = (slot + 1) & d.mask;
-  }
+  return table_claim([&](unsigned int j) { return &d.keys[j]; }, d.mask, k);
 }
 
 // VoxelizedPointCloud::insert (Voxel.cpp:66-90) of o3d_slam::transform(T, cloud) (Submap.cpp:81-84)
@@ -1432,22 +1535,18 @@ __global__ __launch_bounds__(kBlock) void dense_insert_kernel(const P4* __restri
                                                               size_t n, Mat34 M, double inv, DenseDev d) {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     const P4 p = pts[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const double px = M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], py = M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
-                 pz = M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11];
-    const unsigned long long k = pack_key((long long)(int)floor(px * inv), (long long)(int)floor(py * inv), (long long)(int)floor(pz * inv));
-    const unsigned int slot = dense_find_or_insert(d, k);
+    const Vec3d w = place_point(M, (double)p.x, (double)p.y, (double)p.z);
+    const unsigned int slot = dense_find_or_insert(d, key_world_int(w.x, w.y, w.z, inv));
     atomicAdd(&d.cnt[slot], 1);
-    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot], (unsigned long long)llrint(px / kDensePosQ));
-    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot + 1], (unsigned long long)llrint(py / kDensePosQ));
-    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot + 2], (unsigned long long)llrint(pz / kDensePosQ));
+    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot], (unsigned long long)llrint(w.x / kDensePosQ));
+    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot + 1], (unsigned long long)llrint(w.y / kDensePosQ));
+    atomicAdd((unsigned long long*)&d.sp[3 * (size_t)slot + 2], (unsigned long long)llrint(w.z / kDensePosQ));
     if (nrm) {
       const P4 q = nrm[i];
-      const double a = (double)q.x, b = (double)q.y, c = (double)q.z;
-      const double nx = M.m[0] * a + M.m[1] * b + M.m[2] * c, ny = M.m[4] * a + M.m[5] * b + M.m[6] * c, nz = M.m[8] * a + M.m[9] * b + M.m[10] * c;
-      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot], (unsigned long long)llrint(nx / kDenseNrmQ));
-      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot + 1], (unsigned long long)llrint(ny / kDenseNrmQ));
-      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot + 2], (unsigned long long)llrint(nz / kDenseNrmQ));
+      const Vec3d r = rotate_normal(M, (double)q.x, (double)q.y, (double)q.z);
+      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot], (unsigned long long)llrint(r.x / kDenseNrmQ));
+      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot + 1], (unsigned long long)llrint(r.y / kDenseNrmQ));
+      atomicAdd((unsigned long long*)&d.sn[3 * (size_t)slot + 2], (unsigned long long)llrint(r.z / kDenseNrmQ));
     }
     if (col) {  // colours are not rotated (o3d_slam::transform leaves colors_ alone)
       const P4 c = col[i];
@@ -1503,8 +1602,7 @@ __global__ __launch_bounds__(kBlock) void owner_count_kernel(const P4* __restric
       typename Scalar<P4>::type q[3];
       placed_point<P4>(pts[i], M, place != 0, q);
       if (isfinite((double)q[0]) && isfinite((double)q[1]) && isfinite((double)q[2])) {
-        const long long kx = (long long)(int)floor((double)q[0] * inv), ky = (long long)(int)floor((double)q[1] * inv),
-                        kz = (long long)(int)floor((double)q[2] * inv);
+        const long long kx = voxel_index_int((double)q[0], inv), ky = voxel_index_int((double)q[1], inv), kz = voxel_index_int((double)q[2], inv);
         const unsigned long long hsh = (unsigned long long)(kx + 17191ll * ky + 17191ll * 17191ll * kz) & 0xffffffffull;
         o = (int)(hsh % (unsigned long long)world);
       }
@@ -1565,8 +1663,8 @@ __global__ __launch_bounds__(kBlock) void owner_scatter_kernel(const P4* __restr
       const P4 v = nrm[i];
       a = (double)v.x, b = (double)v.y, c = (double)v.z;
       if (place) {  // normals rotate with the cloud (o3d_slam::transform, helpers.cpp:273-305)
-        const double x = a, y = b, z = c;
-        a = M.m[0] * x + M.m[1] * y + M.m[2] * z, b = M.m[4] * x + M.m[5] * y + M.m[6] * z, c = M.m[8] * x + M.m[9] * y + M.m[10] * z;
+        const Vec3d r = rotate_normal(M, a, b, c);
+        a = r.x, b = r.y, c = r.z;
       }
     }
     r[3] = a, r[4] = b, r[5] = c;
@@ -1598,11 +1696,9 @@ __global__ __launch_bounds__(kBlock) void dense_probe_kernel(const P4* __restric
   unsigned int mine = 0;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     const P4 p = pts[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const double px = M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], py = M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
-                 pz = M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11];
-    const unsigned long long k = pack_key((long long)(int)floor(px * inv), (long long)(int)floor(py * inv), (long long)(int)floor(pz * inv));
-    unsigned int slot = dense_slot_of(k, d.mask);
+    const Vec3d w = place_point(M, (double)p.x, (double)p.y, (double)p.z);
+    const unsigned long long k = key_world_int(w.x, w.y, w.z, inv);
+    unsigned int slot = table_hash(k) & d.mask;
     while (true) {
       const unsigned long long t = d.keys[slot];
       if (t == k) {
@@ -1621,7 +1717,7 @@ __global__ __launch_bounds__(kBlock) void dense_probe_kernel(const P4* __restric
 // (helpers.cpp:347-377) + getVoxelsWithinPointNeighborhood (VoxelHashMap.cpp:13-44, keys by DIVISION floor(p / v) as written there).
 // One thread per kept scan point; marking a slot is an idempotent store.
 __device__ __forceinline__ void dense_mark(const DenseDev& d, unsigned long long k, int* __restrict__ mark) {
-  unsigned int slot = dense_slot_of(k, d.mask);
+  unsigned int slot = table_hash(k) & d.mask;
   while (true) {
     const unsigned long long t = d.keys[slot];
     if (t == k) {
@@ -1632,9 +1728,6 @@ __device__ __forceinline__ void dense_mark(const DenseDev& d, unsigned long long
     slot = (slot + 1) & d.mask;
   }
 }
-__device__ __forceinline__ unsigned long long key_by_division(double x, double y, double z, double v) {
-  return pack_key((long long)(int)floor(x / v), (long long)(int)floor(y / v), (long long)(int)floor(z / v));
-}
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void dense_carve_kernel(const P4* __restrict__ scan, const int* __restrict__ first, size_t n, Mat34 M,
                                                              double sx, double sy, double sz, double v, double radius, double max_len,
@@ -1643,16 +1736,11 @@ __global__ __launch_bounds__(kBlock) void dense_carve_kernel(const P4* __restric
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     if (!first[i]) continue;
     const P4 q = scan[i];
-    const double x = (double)q.x, y = (double)q.y, z = (double)q.z;
-    const double px = M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], py = M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
-                 pz = M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11];
-    const double dx0 = px - sx, dy0 = py - sy, dz0 = pz - sz;
-    const double length = sqrt(dx0 * dx0 + dy0 * dy0 + dz0 * dz0);
-    if (!(length > 0.0)) continue;
-    const double ux = dx0 / length, uy = dy0 / length, uz = dz0 / length;
-    const double lim = fmax(step, fmin(length - trunc, max_len));
-    for (double dist = 0.0; dist < lim; dist += step) {
-      const double cx = dist * ux + sx, cy = dist * uy + sy, cz = dist * uz + sz;
+    const Vec3d p = place_point(M, (double)q.x, (double)q.y, (double)q.z);
+    const CarveRay ray = carve_ray(p.x, p.y, p.z, sx, sy, sz, step, trunc, max_len);
+    if (!ray.valid) continue;
+    for (double dist = 0.0; dist < ray.lim; dist += step) {
+      const double cx = dist * ray.ux + sx, cy = dist * ray.uy + sy, cz = dist * ray.uz + sz;
       const unsigned long long ck = key_by_division(cx, cy, cz, v);
       bool center_added = false;
       for (double ax = -radius; ax <= radius; ax += v)
@@ -1763,13 +1851,11 @@ __global__ __launch_bounds__(kBlock) void dense_transform_kernel(DenseDev d, siz
   for (size_t s = (size_t)blockIdx.x * kBlock + threadIdx.x; s < cap; s += (size_t)gridDim.x * kBlock) {
     if (d.keys[s] == kEmptyKey || d.cnt[s] <= 0) continue;
     const double x = (double)d.sp[3 * s] * kDensePosQ, y = (double)d.sp[3 * s + 1] * kDensePosQ, z = (double)d.sp[3 * s + 2] * kDensePosQ;
-    d.sp[3 * s] = llrint((M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3]) / kDensePosQ);
-    d.sp[3 * s + 1] = llrint((M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7]) / kDensePosQ);
-    d.sp[3 * s + 2] = llrint((M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11]) / kDensePosQ);
+    const Vec3d p = place_point(M, x, y, z);
+    d.sp[3 * s] = llrint(p.x / kDensePosQ), d.sp[3 * s + 1] = llrint(p.y / kDensePosQ), d.sp[3 * s + 2] = llrint(p.z / kDensePosQ);
     const double a = (double)d.sn[3 * s] * kDenseNrmQ, b = (double)d.sn[3 * s + 1] * kDenseNrmQ, c = (double)d.sn[3 * s + 2] * kDenseNrmQ;
-    d.sn[3 * s] = llrint((M.m[0] * a + M.m[1] * b + M.m[2] * c + M.m[3]) / kDenseNrmQ);
-    d.sn[3 * s + 1] = llrint((M.m[4] * a + M.m[5] * b + M.m[6] * c + M.m[7]) / kDenseNrmQ);
-    d.sn[3 * s + 2] = llrint((M.m[8] * a + M.m[9] * b + M.m[10] * c + M.m[11]) / kDenseNrmQ);
+    const Vec3d q = place_point(M, a, b, c);  // (place_point, not rotate_normal: that is the quirk)
+    d.sn[3 * s] = llrint(q.x / kDenseNrmQ), d.sn[3 * s + 1] = llrint(q.y / kDenseNrmQ), d.sn[3 * s + 2] = llrint(q.z / kDenseNrmQ);
   }
 }
 

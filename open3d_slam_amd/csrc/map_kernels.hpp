@@ -122,28 +122,16 @@ enum PmCounter {
 
 template <typename P4>
 __device__ __forceinline__ unsigned long long pm_key(const P4& p, double inv) {
-  return pack_key((long long)floor((double)p.x * inv), (long long)floor((double)p.y * inv), (long long)floor((double)p.z * inv));
+  return key_world((double)p.x, (double)p.y, (double)p.z, inv);
 }
-__device__ __forceinline__ unsigned int pm_hash(unsigned long long k) { return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> 32); }
 
 // hash entry of key k (inserted if absent)
 __device__ __forceinline__ unsigned int pm_entry(const PmDev& m, unsigned long long k) {
-  unsigned int e = pm_hash(k) & m.hmask;
-  while (true) {
-    const unsigned long long prev = atomicCAS(&m.h[e].key, kEmptyKey, k);
-    if (prev == kEmptyKey || prev == k) return e;
-    e = (e + 1) & m.hmask;
-  }
+  return table_claim([&](unsigned int e) { return &m.h[e].key; }, m.hmask, k);
 }
 // ... or ~0u when the key is not in the table (read-only probe)
 __device__ __forceinline__ unsigned int pm_find(const PmDev& m, unsigned long long k) {
-  unsigned int e = pm_hash(k) & m.hmask;
-  while (true) {
-    const unsigned long long cur = m.h[e].key;
-    if (cur == k) return e;
-    if (cur == kEmptyKey) return ~0u;
-    e = (e + 1) & m.hmask;
-  }
+  return table_find([&](unsigned int e) { return &m.h[e].key; }, m.hmask, k);
 }
 
 // index cell of a voxel key: (row, x) with the clamping build_grid_t's cell_of has
@@ -456,8 +444,8 @@ __global__ __launch_bounds__(kBlock) void pm_scatter_kernel(PmDev m, int n, cons
 }
 
 // ---- an insertion -----------------------------------------------------------------------------------------------------------------------
-// (1) place the scan (o3d_slam::transform: the arithmetic of transform_kernel), round to storage, and group the placed points that lie inside
-// the volume by voxel: vox_insert_kernel's run lists on the WORLD-anchored key.  Points outside the volume go on a list.
+// (1) place the scan (o3d_slam::transform), round to storage, and group the placed points that lie inside the volume by voxel: run
+// lists (vox_run_insert) on the WORLD-anchored key.  Points outside the volume go on a list.
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_place_kernel(const P4* __restrict__ spts, const P4* __restrict__ snrm, CountRef n_in, Mat34 M, double w0,
                                                           double w1, double w2, double w3, CropDev crop, PmDev m, VoxTable t, P4* __restrict__ placed,
@@ -472,21 +460,16 @@ __global__ __launch_bounds__(kBlock) void pm_place_kernel(const P4* __restrict__
     unsigned long long k = kEmptyKey;
     if (i < n) {
       const P4 p = spts[i];
-      const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-      const double w = w0 * x + w1 * y + w2 * z + w3;
+      const Vec3d w = place_point_homogeneous(M, w0, w1, w2, w3, (double)p.x, (double)p.y, (double)p.z);
       P4 o;
-      o.x = (R)((M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3]) / w);
-      o.y = (R)((M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7]) / w);
-      o.z = (R)((M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11]) / w);
+      o.x = (R)w.x, o.y = (R)w.y, o.z = (R)w.z;
       o.i = (typename Scalar<P4>::index)i;
       placed[i] = o;
       if (snrm) {
         const P4 q = snrm[i];
-        const double a = (double)q.x, b = (double)q.y, c = (double)q.z;
+        const Vec3d r = rotate_normal(M, (double)q.x, (double)q.y, (double)q.z);
         P4 on;
-        on.x = (R)(M.m[0] * a + M.m[1] * b + M.m[2] * c);
-        on.y = (R)(M.m[4] * a + M.m[5] * b + M.m[6] * c);
-        on.z = (R)(M.m[8] * a + M.m[9] * b + M.m[10] * c);
+        on.x = (R)r.x, on.y = (R)r.y, on.z = (R)r.z;
         on.i = 0;
         placed_nrm[i] = on;
       }
@@ -495,26 +478,7 @@ __global__ __launch_bounds__(kBlock) void pm_place_kernel(const P4* __restrict__
       else
         pm_push(m.outside_pts, m.counters + kPmOutside, m.list_cap, (int)i, m.counters + kPmError);
     }
-    const unsigned long long kp = __shfl_up(k, 1, 64);
-    const bool lead = k != kEmptyKey && (lane == 0 || kp != k);
-    const unsigned long long ends = __ballot(lane == 0 || kp != k);
-    int slot = -1;
-    if (lead) {
-      const unsigned long long above = lane == 63 ? 0ull : (ends >> (lane + 1));
-      const int len = above ? (int)__builtin_ctzll(above) + 1 : 64 - lane;
-      unsigned int sl = pm_hash(k) & t.mask;
-      while (true) {
-        const unsigned long long prev = atomicCAS(&t.s[sl].key, kEmptyKey, k);
-        if (prev == kEmptyKey || prev == k) break;
-        sl = (sl + 1) & t.mask;
-      }
-      atomicMin(&t.s[sl].first, (unsigned int)i);
-      atomicAdd(&t.s[sl].nrun, 1u);
-      run_next[i] = atomicExch(&t.s[sl].head, (int)i);
-      run_len[i] = len;
-      slot = (int)sl;
-    }
-    if (i < n) lead_slot[i] = slot;
+    vox_run_insert(t, k, i, n, lane, lead_slot, run_next, run_len);
   }
 }
 
@@ -652,7 +616,7 @@ __global__ __launch_bounds__(kBlock) void pm_group_kernel(PmDev m, CountRef g_in
       t.s[s] = e0;
     }
     // (the first probe of the voxel hash goes out now, beside the walks over the runs: two chains of dependent loads, side by side)
-    const unsigned int e0 = pm_hash(key) & m.hmask;
+    const unsigned int e0 = table_hash(key) & m.hmask;
     const PmHash h0 = have ? m.h[e0] : PmHash{kEmptyKey, -1, 0u};
     const unsigned long long hk0 = h0.key;
     const int hh0 = h0.head;
@@ -1435,7 +1399,7 @@ __global__ __launch_bounds__(64) void pm_turn_kernel(PmDev m, CountPub pub, Crop
 // ---- Submap::carve (Submap.cpp:109-125 -> getIdxsOfCarvedPoints, helpers.cpp:235-271) on the persistent form -----------------------------
 // The reference bins the map points inside the cropping volume by voxel and lets every scan ray probe that table; here the table exists
 // already -- the voxel hash, when the carving voxel is the map's voxel (the shipped configuration: 0.1 m both).  Same rays, same samples
-// (carve_rays_kernel's arithmetic), same test per point (inside the volume; |ray . unit normal| > min_dot or no normals); a point that
+// (carve_ray, carve_walk), same test per point (inside the volume; carve_removes, or no normals); a point that
 // goes is marked, listed once, and killed by pm_carve_apply_kernel: dead flag, its index entry replaced by the far sentinel.  It stays
 // in its chain (many rays reach one voxel at the same time: no unlinking here), chain walks skip the dead, the next fold drops them.
 // The survivors keep their order by construction: the order is a function of the slots' histories (pm_view_key), not of an array.
@@ -1451,69 +1415,38 @@ template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_carve_rays_kernel(PmDev m, const P4* __restrict__ scan, size_t n_scan, Mat34 M /* map <- sensor */, double sx,
                                                                double sy, double sz, double max_len, double trunc, double min_dot, CropDev crop,
                                                                const unsigned int* __restrict__ block_bits) {
-  const double voxel = m.voxel, inv = 1.0 / voxel;
+  const double voxel = m.voxel;
   const bool has_nrm = m.nrm != nullptr;
-  {  // one ray per thread (no loop over rays: the pose and the scan's address are dead after these lines, which is what keeps the kernel's
-     // scalar registers within the file)
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_scan) return;
-    const P4 q = scan[i];
-    const double x = (double)q.x, y = (double)q.y, z = (double)q.z;
-    const double px = M.m[0] * x + M.m[1] * y + M.m[2] * z + M.m[3], py = M.m[4] * x + M.m[5] * y + M.m[6] * z + M.m[7],
-                 pz = M.m[8] * x + M.m[9] * y + M.m[10] * z + M.m[11];
-    const double dx = px - sx, dy = py - sy, dz = pz - sz;
-    const double length = sqrt(dx * dx + dy * dy + dz * dz);
-    if (!(length > 0.0)) return;
-    const double ux = dx / length, uy = dy / length, uz = dz / length;
-    const double lim = fmax(voxel, fmin(length - trunc, max_len));
-    constexpr int kBatch = 8;
-    double dist = 0.0;
-    while (dist < lim) {
-      unsigned long long ks[kBatch];
-      unsigned int bits[kBatch], words[kBatch];
-      int nb = 0;
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u)
-        if (dist < lim) {
-          const double cx = dist * ux + sx, cy = dist * uy + sy, cz = dist * uz + sz;
-          ks[u] = pack_key((long long)(int)floor(cx * inv), (long long)(int)floor(cy * inv), (long long)(int)floor(cz * inv));
-          bits[u] = carve_block_bit(ks[u]);
-          dist += voxel;
-          nb = u + 1;
-        }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u)
-        if (u < nb) words[u] = block_bits[bits[u] >> 5];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        if (u >= nb) break;
-        if (!((words[u] >> (bits[u] & 31u)) & 1u)) continue;  // nothing of the map in this block of voxels
-        const unsigned int e = pm_find(m, ks[u]);
-        if (e == ~0u) continue;
-        for (int s = m.h[e].head; s != -1; s = m.slot[s].hnext) {
-          const unsigned int fl = m.slot[s].flags;
-          if (fl & (kPmDead | kPmCarved)) continue;
-          const P4 p = ((const P4*)m.pts)[s];
-          if (!crop_contains(crop, (double)p.x, (double)p.y, (double)p.z)) continue;  // (the reference's table holds the points inside the volume)
-          bool rem = true;
-          if (has_nrm) {
-            const P4 nn = ((const P4*)m.nrm)[s];
-            const double a = (double)nn.x, bb = (double)nn.y, c = (double)nn.z;
-            const double nl = sqrt(a * a + bb * bb + c * c);
-            const double dot = nl > 0.0 ? (ux * a + uy * bb + uz * c) / nl : 0.0;  // Eigen normalized(): the zero vector stays zero
-            rem = fabs(dot) > min_dot;
-          }
-          if (rem && !(atomicOr(&m.slot[s].flags, kPmCarved) & kPmCarved)) {
-            const int k = atomicAdd(m.counters + kPmCarvedCnt, 1);  // (one ticket per removal: a carve removes a few hundred points)
-            if (k < m.list_cap)
-              m.new_slots[k] = s;
-            else
-              atomicOr(m.counters + kPmError, 1);
-          }
-        }
+  // one ray per thread (no loop over rays: the pose and the scan's address are dead after these lines, which is what keeps the kernel's
+  // scalar registers within the file)
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_scan) return;
+  const P4 q = scan[i];
+  const Vec3d w = place_point(M, (double)q.x, (double)q.y, (double)q.z);
+  const CarveRay ray = carve_ray(w.x, w.y, w.z, sx, sy, sz, voxel, trunc, max_len);
+  if (!ray.valid) return;
+  carve_walk(ray, sx, sy, sz, voxel, block_bits, [&](unsigned long long key) {
+    const unsigned int e = pm_find(m, key);
+    if (e == ~0u) return;
+    for (int s = m.h[e].head; s != -1; s = m.slot[s].hnext) {
+      const unsigned int fl = m.slot[s].flags;
+      if (fl & (kPmDead | kPmCarved)) continue;
+      const P4 p = ((const P4*)m.pts)[s];
+      if (!crop_contains(crop, (double)p.x, (double)p.y, (double)p.z)) continue;  // (the reference's table holds the points inside the volume)
+      bool rem = true;
+      if (has_nrm) {
+        const P4 nn = ((const P4*)m.nrm)[s];
+        rem = carve_removes(ray, (double)nn.x, (double)nn.y, (double)nn.z, min_dot);
+      }
+      if (rem && !(atomicOr(&m.slot[s].flags, kPmCarved) & kPmCarved)) {
+        const int k = atomicAdd(m.counters + kPmCarvedCnt, 1);  // (one ticket per removal: a carve removes a few hundred points)
+        if (k < m.list_cap)
+          m.new_slots[k] = s;
+        else
+          atomicOr(m.counters + kPmError, 1);
       }
     }
-  }
+  });
 }
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_carve_apply_kernel(PmDev m, CountPub pub, double* __restrict__ host_vals) {

@@ -1439,6 +1439,173 @@ def test_persistent_map_is_bitwise_the_array_form(prec, case):
     assert got[-1][2] > 5000
 
 
+def _face_points(prec, seed):
+    """500 points ON voxel faces, with unit normals: 250 lattice points k * 0.1 (k integer in [-12, 12] per axis), computed in double and
+    rounded to the storage type, and the same points shifted by half a 0.1 voxel.  The world-anchored keys have the lattice points on
+    their faces, the data-anchored key of VoxelDownSample (origin = min bound - voxel / 2) the shifted ones."""
+    rng = np.random.default_rng(seed)
+    lat = rng.integers(-12, 13, size=(250, 3)) * 0.1
+    pts = np.vstack([lat, lat + 0.05])
+    nrm = rng.normal(size=pts.shape)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    if prec == "f32":
+        pts, nrm = pts.astype(np.float32).astype(np.float64), nrm.astype(np.float32).astype(np.float64)
+    return pts, nrm
+
+
+_FACE_CARVE = dict(max_length=20.0, truncation=0.1, min_dot=0.5)
+
+
+def _face_carve_scan(prec):
+    """rays from the origin (the sensor of an identity pose) to face points: along the axes their samples lie on faces too"""
+    b, _ = _face_points(prec, 2)
+    return b[np.linalg.norm(b, axis=1) > 0.0][:150]
+
+
+def _face_map_sequence(be, prec, voxel, look):
+    """two insertions of face points into an empty map at the identity pose (no rounding in the placement), then a carve with the
+    map's voxel.  look: download the map between the insertions and the carve -- that folds a map in its persistent form into the
+    array, so the carve works on the array; without it a persistent map is carved where it is."""
+    crop = backend.make_crop(backend.CROP_MIN_MAX_RADIUS, rmin=0.0, rmax=1.5)
+    m = be.upload(np.zeros((0, 3)))
+    for seed in (1, 2):
+        s = be.upload(*_face_points(prec, seed))
+        be.map_insert_scan(m, s, np.eye(4), voxel, crop, max_corr_hint=1.0)
+        be.free(s)
+    out = {}
+    if look:
+        out["inserted"] = be.download(m)
+    raw = be.upload(_face_carve_scan(prec))
+    out["removed"] = be.map_carve(m, raw, np.eye(4), crop, voxel=voxel, **_FACE_CARVE)
+    out["carved"] = be.download(m)
+    be.free(raw)
+    be.free(m)
+    return out
+
+
+def _face_map_sequences(be, prec):
+    return {(voxel, look): _face_map_sequence(be, prec, voxel, look) for voxel in (0.1, 0.25) for look in (True, False)}
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_points_on_voxel_faces_fall_where_the_oracle_puts_them(backend_f64, backend_f32, oracle, prec):
+    """The voxel of a point is rounded in four ways (cloud_kernels.hpp key_from_origin, key_world, key_world_int, key_by_division), each
+    after another line of the reference, and they disagree only on points that lie on voxel faces -- which the scans of the other tests
+    almost never hit.  Here every point lies on a face of one of the grids, and every operation that bins points is held to the oracle:
+    bit for bit in f64 storage (identity poses: the placement rounds nothing), with the neighbouring f32 tests' comparisons in f32."""
+    import pickle
+    import subprocess
+    import sys
+
+    from scipy.spatial import cKDTree
+
+    be = backend_f64 if prec == "f64" else backend_f32
+    f64 = prec == "f64"
+    a, an = _face_points(prec, 1)
+    b, bn = _face_points(prec, 2)
+    # the input tells the roundings apart: the oracle's VoxelDownSample and its dense map bin these points differently, and (binary64
+    # lattice values only: rounded to f32 they sit 1e-9 off the faces) multiplying by 1 / v and dividing by v disagree on some
+    assert len(oracle.voxel_down_sample(a, 0.1)) != len(oracle.dense_fuse(a, None, 0.1)[0])
+    if f64:
+        assert np.any(np.floor(a * (1.0 / 0.1)) != np.floor(a / 0.1))
+    ca, cb = be.upload(a, an), be.upload(b, bn)
+    crop_kw = dict(center=(0.03, -0.02, 0.01), rmax=1.3)
+    keep = oracle.crop_indices(a, oracle.make_crop(oracle.CROP_MAX_RADIUS, **crop_kw))
+    assert 0 < len(keep) < len(a)
+
+    def same_cloud(cid, ref, rn):
+        got, gn = be.download(cid)
+        if f64:
+            np.testing.assert_array_equal(got, ref)
+            np.testing.assert_array_equal(gn, rn)
+        else:  # (test_voxel_down_sample_with_normals_and_f32)
+            j = _match(got, ref, 5e-6)
+            np.testing.assert_allclose(gn[j], rn, atol=1e-6)
+        be.free(cid)
+
+    # the array form of the map sequences: the A/B library in a child process (the switch is read once per process)
+    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preprocess_map_gpu as t; from open3d_slam_amd import backend; "
+            "be = backend.Backend(0, %d, ab=True); sys.stdout.buffer.write(pickle.dumps(t._face_map_sequences(be, %r)))"
+            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)),
+               backend.PRECISION_F64 if f64 else backend.PRECISION_F32, prec))
+    array_form = pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True,
+                                             env=dict(os.environ, O3DS_NO_PERSISTENT_MAP="1")).stdout)
+    persistent = _face_map_sequences(be, prec)
+    ocrop = oracle.make_crop(oracle.CROP_MIN_MAX_RADIUS, rmin=0.0, rmax=1.5)
+    raw = _face_carve_scan(prec)
+
+    for voxel in (0.1, 0.25):
+        same_cloud(be.voxel_down_sample(ca, voxel), *oracle.voxel_down_sample(a, voxel, an))
+        same_cloud(be.crop_voxel_down_sample(ca, backend.make_crop(backend.CROP_MAX_RADIUS, **crop_kw), voxel),
+                   *oracle.voxel_down_sample(a[keep], voxel, an[keep]))
+
+        # map_insert_scan twice, map_carve: the three routes agree byte for byte ...
+        looked, unlooked, arr = persistent[(voxel, True)], persistent[(voxel, False)], array_form[(voxel, True)]
+        for other in (unlooked, arr, array_form[(voxel, False)]):
+            assert other["removed"] == looked["removed"]
+            for name in ("carved", "inserted") if "inserted" in other else ("carved",):
+                for x, y in zip(other[name], looked[name]):
+                    assert x.tobytes() == y.tobytes()
+        # ... and with the oracle (test_voxelize_within_volume_matches_oracle, test_map_carve_matches_oracle)
+        ref_p, ref_n, _ = oracle.voxelize_within_volume(a, an, voxel, ocrop)
+        ref_p, ref_n, npass = oracle.voxelize_within_volume(np.vstack([ref_p, b]), np.vstack([ref_n, bn]), voxel, ocrop)
+        mp, mn = looked["inserted"]
+        assert len(mp) == len(ref_p) and 0 < npass < len(ref_p)
+        if f64:
+            np.testing.assert_array_equal(mp[:npass], ref_p[:npass])
+            j = _match(mp[npass:], ref_p[npass:], 0.0)
+            np.testing.assert_array_equal(mp[npass:][j], ref_p[npass:])
+            np.testing.assert_allclose(mn[npass:][j], ref_n[npass:], atol=1e-9)  # (test_map_insert_scan_sequence_matches_oracle)
+        else:
+            j = _match(mp, ref_p, 5e-6)
+            np.testing.assert_allclose(mn[j], ref_n, atol=1e-6)
+        gone = oracle.carve_flags(raw, np.zeros(3), mp, mn, oracle.crop_indices(mp, ocrop), voxel=voxel, **_FACE_CARVE)
+        assert 0 < int(gone.sum()) < len(mp)
+        if f64:
+            assert looked["removed"] == int(gone.sum())
+            np.testing.assert_array_equal(looked["carved"][0], mp[~gone])
+            np.testing.assert_array_equal(looked["carved"][1], mn[~gone])
+        else:  # (test_map_carve_matches_oracle's f32 bound)
+            assert abs(looked["removed"] - int(gone.sum())) <= 0.01 * gone.sum() + 5
+            assert len(looked["carved"][0]) == len(mp) - looked["removed"]
+
+        # dense map: insert, count, carve (test_dense_voxel_map_matches_oracle, test_dense_map_carve_matches_oracle)
+        dm = be.dense_map_create(voxel)
+        be.dense_map_insert(dm, ca)
+        rp, _, _ = oracle.dense_fuse(a, None, voxel)
+        key_of = lambda pts: np.array([oracle.lib().orc_voxel_key(np.ascontiguousarray(q).ctypes.data_as(oracle._dp), voxel) for q in pts], np.int64)
+        occupied = set(key_of(a).tolist())
+        assert sorted(key_of(rp).tolist()) == sorted(occupied)  # (the oracle's means are fit to stand for their voxels in dense_carve)
+        assert be.dense_map_size(dm) == len(rp)
+        assert be.dense_map_count_occupied(dm, cb) == sum(k in occupied for k in key_of(b).tolist())
+        before_id = be.dense_map_to_cloud(dm)
+        before = be.download(before_id)[0]
+        # fixed-point sums: 1 nm per inserted point; f32 storage of the means: half a spacing of 1.2e-7 per axis at these magnitudes
+        d, j = cKDTree(rp).query(before)
+        assert np.array_equal(np.sort(j), np.arange(len(rp))) and d.max() < (1e-8 if f64 else 1e-6)
+        ref = oracle.dense_carve(raw, np.zeros(3), rp, voxel)[j]
+        s = be.upload(raw)
+        removed = be.dense_map_carve(dm, s, np.zeros(3))
+        assert removed == int(ref.sum()) and 0 < removed < len(before)
+        after_id = be.dense_map_to_cloud(dm)
+        np.testing.assert_array_equal(be.download(after_id)[0], before[~ref])
+        for cid in (before_id, after_id, s):
+            be.free(cid)
+        be.dense_map_free(dm)
+
+        # overlap_indices at the identity (test_overlap_indices_match_oracle)
+        g_s, g_t = be.overlap_indices(ca, cb, np.eye(4), voxel, 1)
+        r_s, r_t = oracle.overlap_indices(a, b, np.eye(4), voxel, 1)
+        assert 0 < len(r_s) < len(a)
+        if f64:
+            np.testing.assert_array_equal(g_s, r_s)
+            np.testing.assert_array_equal(g_t, r_t)
+        else:
+            assert len(np.setxor1d(g_s, r_s)) <= 0.002 * len(r_s) + 5
+    be.free(ca)
+    be.free(cb)
+
+
 @pytest.fixture(scope="module")
 def scratch_clouds():
     """seeded samples of the synthetic scene (a 60 m x 60 m x 10 m hall), with normals, by size"""
