@@ -495,8 +495,11 @@ __device__ __forceinline__ bool row_extent(float b2, float rowd2, float ux, int*
   const float w2 = b2 - rowd2;
   if (!(w2 >= 0.0f)) return false;
   const float w = sqrtf(w2) + 1e-4f;
-  *xa = (int)floorf(fmaxf(ux - w, -64.0f));
-  *xb = (int)floorf(fminf(ux + w, 64.0f));
+  // clamped only so that the int conversion is safe, at a bound no grid reaches (an axis has at most 2^27 cells): the search radius in
+  // cells is unbounded (an index built with an explicit cell keeps it for any r), and every caller clamps to its own block, to the grid
+  // and to K itself.  |own cell| <= 1e9 (locate), so own cell + offset still fits an int
+  *xa = (int)floorf(fmaxf(ux - w, -1.0e9f));
+  *xb = (int)floorf(fminf(ux + w, 1.0e9f));
   return true;
 }
 

@@ -1,0 +1,527 @@
+"""The ICP neighbour search per query against brute force (needs an MI355X).
+
+Every registration entry point rests on one device routine, the exact 1-NN within radius of icp_kernels.hpp (nn_search_group,
+nn_search_wave_far, consider, scan_strided, the cached starting bound, the neighbourhood-major replica, the crop predicate, the candidate
+sets of the fused kernel).  Here its per-query observable -- o3ds_icp_nn_keys: float bits of d2, rank, position, or "none" -- and the
+step record of the same session state are held against tests/icp_search_restatement.py, whose agreement with the oracle
+tests/test_icp_search_restatement_cpu.py proves without a GPU.  Row search and replica, f32 and f64 storage.
+
+Bounds (derived, not measured; every test prints the largest observed ratio before it asserts):
+  * exact cases (coordinates small integers times a power of two, pose the identity or an exact translation): every operation is exact
+    in both storages, the float bits of d2 are equal.
+  * f32 storage, seeded clouds: |d2_dev - d2_ref| <= 8 * 2^-24 * d2_ref.  dist2 is fmaf(dz, dz, fmaf(dy, dy, dx * dx)): the three
+    differences are each within 2^-24 relative of the exact ones (one rounding; exact when the operands are within a factor of two), so
+    each SQUARE is within (1 + 2^-24)^2 - 1 < 2.0001 * 2^-24; the product dx * dx and the two fused steps add one rounding each, and as
+    all terms are non-negative a relative error of the terms is a relative error of the sum: 2 + 3 = 5 units of 2^-24 to first order,
+    under 8 with every higher-order term.  The reference forms d2 in f64 from the same stored coordinates (error 2^-52, nothing).
+  * f64 storage: float(d2_ref) within one float ulp of the key's float -- the device's d2 differs from the reference's by a few f64 ulps
+    (its own three products and two sums, and the f64 rounding of p = T s, whose multiply-adds the compiler may fuse), so the double-to-
+    float cast is the only rounding that can differ, and only by landing on the other side of a rounding boundary.
+  * records: |term_dev - term_ref| <= 1e-12 * sum |addends| per term: an addend carries at most about eight f64 roundings (1e-15), the
+    workgroup sums add n * 2^-53, the sums across workgroups are exact by design; three orders of margin.  In f32 storage terms [27]
+    and [29] take the d2 bound above instead.
+The key cannot show WHICH of several equidistant points won; the record can (duplicated target points carry different normals), and it
+pins the position -> point -> normal gather with it."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import icp_search_restatement as rs  # noqa: E402
+
+from open3d_slam_amd import backend  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -0x0123456789ABCDEF
+PREC = {rs.F32: backend.PRECISION_F32, rs.F64: backend.PRECISION_F64}
+PATHS = ("rows", "replica")
+REC_TOL = 1e-12
+GAP_MIN, NEAR_R_MIN = 1e-5, 1e-6  # the premises of tests/test_icp_search_restatement_cpu.py, asserted here where the pose comes from the device
+
+
+@pytest.fixture(autouse=True)
+def _eager_replica(monkeypatch):
+    monkeypatch.setenv("O3DS_NN_REPLICA_AFTER", "1")
+    monkeypatch.delenv("O3DS_DEBUG_ACC", raising=False)
+
+
+@pytest.fixture(scope="module")
+def ab():
+    """one handle of the A/B library per storage (the switches O3DS_NN_REPLICA, O3DS_NN_REPLICA_AFTER, O3DS_DEBUG_ACC exist only there)"""
+    bes = {s: backend.Backend(0, p, ab=True) for s, p in PREC.items()}
+    yield bes
+    for be in bes.values():
+        be.close()
+
+
+@pytest.fixture(scope="module")
+def shipped():
+    bes = {s: backend.Backend(0, p) for s, p in PREC.items()}
+    yield bes
+    for be in bes.values():
+        be.close()
+
+
+def _path(monkeypatch, path):
+    monkeypatch.setenv("O3DS_NN_REPLICA", "1" if path == "replica" else "0")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    return {c.name: c for c in rs.all_cases()}[name]
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(name, storage):
+    c = _case(name)
+    return rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
+
+
+class Session:
+    """source and target of one case on a handle, its index built with the case's cell"""
+
+    def __init__(self, be, src, tgt, nrm, r, cell, target_id=None):
+        self.be, self.r, self.n = be, r, len(src)
+        self.s = be.upload(src)
+        self.t = be.upload(tgt, nrm) if target_id is None else target_id  # (a target the caller has built keeps the index it has)
+        if target_id is None:
+            be.build_index(self.t, r, cell)
+
+    def begin(self, T, path=None, crop=None, method=backend.ICP_POINT_TO_PLANE, max_iter=10):
+        self.be.icp_begin(self.s, self.t, self.r, init=T, max_iter=max_iter, rel_fitness=0.0, rel_rmse=0.0, target_crop=crop, method=method)
+        if path == "replica":
+            assert self.be.index_replica(self.t) > 0, "the target has no replica: this run would take the row search"
+
+    def keys(self, first=0, count=None, rank=0):
+        import torch
+
+        count = self.n - first if count is None else count
+        k = torch.full((max(self.n, 1),), SENTINEL, dtype=torch.int64, device="cuda:0")
+        torch.cuda.synchronize()
+        self.be.icp_nn_keys(first, count, rank, k.data_ptr())
+        self.be.synchronize()
+        return k
+
+    def record(self, first=0, count=None, keys=None, rank=0):
+        import torch
+
+        count = self.n - first if count is None else count
+        rec = torch.full((32,), 7.0, dtype=torch.float64, device="cuda:0")
+        torch.cuda.synchronize()
+        if keys is None:
+            self.be.icp_accumulate(first, count, rec.data_ptr())
+        else:
+            self.be.icp_accumulate_keys(first, count, rank, keys.data_ptr(), rec.data_ptr())
+        self.be.synchronize()
+        return rec
+
+    def close(self):
+        self.be.free(self.s)
+        self.be.free(self.t)
+
+
+def _check_keys(keys, m, storage, exact, rank, n_tgt, first, count, what):
+    """the keys of queries [first, first + count) against the brute-force matches m (of ALL queries); returns the largest d2 deviation
+    as a fraction of its bound"""
+    k = keys.cpu().numpy()[:len(m.idx)]
+    outside = np.ones(len(k), dtype=bool)
+    outside[first:first + count] = False
+    assert (k[outside] == SENTINEL).all(), f"{what}: keys outside the range were written"
+    sel = slice(first, first + count)
+    none, d2, rk, pos = rs.decode_keys(k[sel])
+    want_none = m.idx[sel] < 0
+    bad = np.flatnonzero(none != want_none)
+    assert bad.size == 0, f"{what}: {bad.size} of {count} queries differ in match / no match, first {first + bad[:8]}, reference d {np.sqrt(m.best[sel][bad[:8]])}"
+    hit = ~none
+    assert (rk[hit] == rank).all(), f"{what}: rank not echoed"
+    if n_tgt is not None:
+        assert (pos[hit] < n_tgt).all(), f"{what}: position beyond the target"
+    ref = m.d2[sel][hit]
+    dev = d2[hit].astype(np.float64)
+    if exact:
+        np.testing.assert_array_equal(d2[hit].view(np.uint32), ref.astype(np.float32).view(np.uint32), err_msg=f"{what}: float bits of d2")
+        return 0.0
+    if not hit.any():
+        return 0.0
+    if storage == rs.F32:
+        ratio = np.abs(dev - ref) / (rs.D2_F32_REL * ref)
+    else:
+        ratio = np.abs(dev - ref.astype(np.float32).astype(np.float64)) / rs.ulp32(ref)
+    worst = float(ratio.max())
+    print(f"SEARCH {what}: d2 deviation / bound {worst:.3f}")
+    assert worst <= 1.0, f"{what}: d2 off by {worst:.3f} x its bound at query {first + np.flatnonzero(hit)[ratio.argmax()]}"
+    return worst
+
+
+def _check_record(rec, m, tgt, nrm, storage, method, first, count, what):
+    got = rec.cpu().numpy()
+    idx = np.full_like(m.idx, -1)
+    idx[first:first + count] = m.idx[first:first + count]
+    ref, scale = rs.record(m.p, tgt, nrm, idx, storage, method)
+    tol = np.full(32, REC_TOL)
+    if storage == rs.F32:
+        tol[[27, 29]] = rs.D2_F32_REL
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(scale > 0, np.abs(got - ref) / (tol * scale), np.where(got == ref, 0.0, np.inf))
+    worst = float(ratio.max())
+    print(f"SEARCH {what}: record deviation / bound {worst:.3e} (term {int(ratio.argmax())}), {int(ref[28])} matches of {count}")
+    assert got[28] == ref[28], f"{what}: {got[28]} correspondences, brute force {ref[28]}"
+    assert worst <= 1.0, f"{what}: record term {int(ratio.argmax())} off by {worst:.3e} x its bound: {got[ratio.argmax()]} vs {ref[ratio.argmax()]}"
+    return worst
+
+
+def _premises(m, r, what):
+    hit = m.idx >= 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = m.gap[hit] / m.d2[hit]
+    assert rel.size == 0 or rel.min() >= GAP_MIN, f"{what}: premise: relative gap {rel.min():.3e}"
+    fin = np.isfinite(m.best)
+    near = np.abs(np.sqrt(m.best[fin]) - r) / r
+    assert near.size == 0 or near.min() >= NEAR_R_MIN, f"{what}: premise: |d - r| / r = {near.min():.3e}"
+
+
+def _run_case(ab, monkeypatch, name, storage, first=0, count=None, rank=3):
+    c = _case(name)
+    m = _ref(name, storage)
+    count = len(c.src) - first if count is None else count
+    ses = Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
+    try:
+        for path in PATHS:
+            what = f"{name} {storage} {path} [{first},{first + count})"
+            _path(monkeypatch, path)
+            for method in (backend.ICP_POINT_TO_PLANE, backend.ICP_POINT_TO_POINT):
+                ses.begin(c.T, path, method=method)
+                keys = ses.keys(first, count, rank)
+                rec = ses.record(first, count)
+                _check_keys(keys, m, storage, c.exact, rank, len(c.tgt), first, count, what)
+                _check_record(rec, m, c.tgt, c.nrm, storage, method, first, count, f"{what} method {method}")
+    finally:
+        ses.close()
+
+
+def _ids(cases):
+    return [c.name for c in cases]
+
+
+# ---- a. lattice: exact ties, points on cell faces, one ulp to either side of a face, workgroup and wavefront boundaries
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("n", rs.LATTICE_COUNTS)
+def test_lattice_exact_bits_and_tie_rule(ab, monkeypatch, storage, n):
+    _run_case(ab, monkeypatch, f"lattice-{n}", storage)
+
+
+@pytest.mark.parametrize("storage", rs.STORAGES)
+def test_lattice_sub_range(ab, monkeypatch, storage):
+    _run_case(ab, monkeypatch, "lattice-300", storage, first=rs.LATTICE_SUBRANGE[0], count=rs.LATTICE_SUBRANGE[1])
+
+
+# ---- b. the radius itself: strict
+@pytest.mark.parametrize("name", _ids(rs.radius_cases()))
+def test_radius_is_strict(ab, monkeypatch, name):
+    for storage in _case(name).storages:
+        _run_case(ab, monkeypatch, name, storage)
+
+
+# ---- c. stage boundaries
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("cell", rs.STAGE_CELLS)
+@pytest.mark.parametrize("void", rs.STAGE_VOIDS)
+def test_stage_boundaries(ab, monkeypatch, void, cell, storage):
+    _run_case(ab, monkeypatch, f"void{void}-cell{cell}-r1.0", storage)
+
+
+@pytest.mark.parametrize("storage", rs.STORAGES)
+def test_matches_and_misses_in_one_workgroup(ab, monkeypatch, storage):
+    _run_case(ab, monkeypatch, "void0.9-cell0.25-r0.5", storage)
+
+
+# ---- d. outside the grid, far away, non-finite rows
+@pytest.mark.parametrize("storage", rs.STORAGES)
+def test_queries_outside_the_grid(ab, monkeypatch, storage):
+    _run_case(ab, monkeypatch, "outside", storage)
+
+
+# ---- e. thin and tiny
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("name", _ids(rs.tiny_cases()))
+def test_thin_and_tiny_targets(ab, monkeypatch, name, storage):
+    _run_case(ab, monkeypatch, name, storage)
+
+
+# ---- f. a radius beyond 64 cells
+@pytest.mark.parametrize("storage", rs.STORAGES)
+def test_radius_beyond_64_cells(ab, monkeypatch, storage):
+    """An index built explicitly with cell c is never rebuilt for another radius, so r / c is unbounded (a map indexed for scan matching,
+    then used for a loop-closure refinement at ten times the radius).  Before row_extent stopped cutting rows at +-64 cells the query 70
+    cells from its neighbour reported "no match" (f32 and f64, rows and replica alike)."""
+    _run_case(ab, monkeypatch, "far-radius", storage)
+
+
+# ---- h. large coordinates
+@pytest.mark.parametrize("name", _ids(rs.large_cases()))
+def test_large_coordinates(ab, monkeypatch, name):
+    for storage in _case(name).storages:
+        _run_case(ab, monkeypatch, name, storage)
+
+
+# ---- g. crops
+@functools.lru_cache(maxsize=None)
+def _crop_ref(k, storage):
+    from oracle import pyoracle
+
+    src, tgt, nrm = rs.void_cloud(rs.CROP_VOID)
+    keep = pyoracle.crop_indices(rs.to_storage(tgt, storage), pyoracle.make_crop(**rs.CROPS[k]))
+    return rs.nearest_within(src, tgt, np.eye(4), 1.0, storage, keep=keep)
+
+
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("k", range(len(rs.CROPS)))
+def test_crops(ab, monkeypatch, k, storage):
+    src, tgt, nrm = rs.void_cloud(rs.CROP_VOID)
+    m = _crop_ref(k, storage)
+    crop = backend.make_crop(**rs.CROPS[k])
+    ses = Session(ab[storage], src, tgt, nrm, 1.0, 0.25)
+    try:
+        for path in PATHS:
+            what = f"crop{k} {storage} {path}"
+            _path(monkeypatch, path)
+            ses.begin(np.eye(4), path, crop=crop)
+            keys = ses.keys(rank=1)
+            rec = ses.record()
+            _check_keys(keys, m, storage, False, 1, len(tgt), 0, len(src), what)
+            _check_record(rec, m, tgt, nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(src), what)
+            if k == 0:  # [O3D] GetInformationMatrixFromPointClouds with the crop that excludes every query's nearest points
+                got = ses.be.information_matrix_dev(ses.s, ses.t, 1.0, np.eye(4), target_crop=crop)
+                ref = rs.information(tgt, m.idx, storage)
+                assert got[3, 3] == ref[3, 3] == (m.idx >= 0).sum()
+                if storage == rs.F64:  # the tolerances of test_icp_gpu.py::test_information_matrix_matches_oracle
+                    np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-7)
+                else:
+                    np.testing.assert_allclose(got, ref, rtol=0, atol=2e-5 * np.abs(ref).max())
+    finally:
+        ses.close()
+
+
+# ---- i. later passes: the cached bound, which may be stale
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("method", [backend.ICP_POINT_TO_POINT, backend.ICP_POINT_TO_PLANE])
+@pytest.mark.parametrize("void", [0.0, 0.6])
+def test_later_passes(ab, monkeypatch, void, method, storage):
+    """k rounds of nn_keys / accumulate_keys / update, then the keys of round k; icp_finish returns the pose those keys were computed under
+    (sessions replay bit for bit), so the brute force uses exactly that matrix.  Point-to-plane runs on random unit normals: its updates
+    jump, which is what a stale bound needs."""
+    import torch
+
+    src, tgt, nrm = rs.void_cloud(void)
+    n = len(src)
+    ses = Session(ab[storage], src, tgt, nrm, 1.0, 0.25)
+    try:
+        for path in PATHS:
+            _path(monkeypatch, path)
+            for k in range(4):
+                what = f"later void{void} method {method} {storage} {path} round {k}"
+                ses.begin(rs.LATER_INIT, path, method=method)
+                for _ in range(k):
+                    keys = ses.keys()
+                    rec = ses.record(keys=keys)
+                    ses.be.icp_update(rec.data_ptr(), n)
+                keys = ses.keys()
+                rec_keys = ses.record(keys=keys)
+                rec_foreign = ses.record(keys=keys, rank=1)
+                rec_plain = ses.record()
+                assert torch.equal(keys, ses.keys()), what  # the search of a state is repeatable (now from the bound its first run cached)
+                T = ses.be.icp_finish()["transformation"]
+                assert (T != rs.LATER_INIT).any() == (k > 0), what
+                m = rs.nearest_within(src, tgt, T, 1.0, storage)
+                _premises(m, 1.0, what)
+                _check_keys(keys, m, storage, False, 0, len(tgt), 0, n, what)
+                _check_record(rec_plain, m, tgt, nrm, storage, method, 0, n, what)
+                a, b = rec_keys.cpu().numpy(), rec_plain.cpu().numpy()
+                same = np.ones(32, dtype=bool)
+                same[[27, 29]] = False  # (these may carry the float-rounded d2 of the key)
+                np.testing.assert_array_equal(a[same], b[same], err_msg=what)
+                np.testing.assert_allclose(a[~same], b[~same], rtol=2.0 ** -23, atol=0, err_msg=what)
+                assert not rec_foreign.cpu().numpy().any(), f"{what}: a record accumulated under a foreign rank is all zero"
+    finally:
+        ses.close()
+
+
+# ---- j. two shards on one GPU
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("name", ["lattice-300", "void0.6-cell0.25-r1.0"])
+def test_two_shards(ab, monkeypatch, name, storage):
+    """the element-wise minimum of the two shards' keys is the brute force over the union (a tie goes to the lower rank), the sum of the two
+    accumulate_keys records is the union's record"""
+    import torch
+
+    c, m = _case(name), _ref(name, storage)
+    h = len(c.tgt) // 2
+    other = backend.Backend(0, PREC[storage], ab=True)
+    parts = []
+    try:
+        parts += [Session(ab[storage], c.src, c.tgt[:h], c.nrm[:h], c.r, c.cell), Session(other, c.src, c.tgt[h:], c.nrm[h:], c.r, c.cell)]
+        for path in PATHS:
+            what = f"shards {name} {storage} {path}"
+            _path(monkeypatch, path)
+            ks = []
+            for rank, ses in enumerate(parts):
+                ses.begin(c.T, path)
+                ks.append(ses.keys(rank=rank))
+            merged = torch.minimum(ks[0], ks[1])
+            torch.cuda.synchronize()
+            none, d2, rk, pos = rs.decode_keys(merged.cpu().numpy())
+            np.testing.assert_array_equal(none, m.idx < 0, err_msg=what)
+            np.testing.assert_array_equal(rk[~none], (m.idx[~none] >= h).astype(np.int64), err_msg=f"{what}: which shard holds the winner")
+            for rank in (0, 1):
+                mine = ~none & (rk == rank)
+                assert (pos[mine] < (h if rank == 0 else len(c.tgt) - h)).all()
+            # d2 as in the single-shard test: the merged keys against the union's matches (rank is checked above)
+            dev = d2[~none]
+            ref = m.d2[~none]
+            if c.exact:
+                np.testing.assert_array_equal(dev.view(np.uint32), ref.astype(np.float32).view(np.uint32), err_msg=what)
+            elif storage == rs.F32:
+                assert (np.abs(dev.astype(np.float64) - ref) <= rs.D2_F32_REL * ref).all(), what
+            else:
+                assert (np.abs(dev.astype(np.float64) - ref.astype(np.float32).astype(np.float64)) <= rs.ulp32(ref)).all(), what
+            total = np.zeros(32)
+            for rank, ses in enumerate(parts):
+                total += ses.record(keys=merged, rank=rank).cpu().numpy()
+            ref_rec, scale = rs.record(m.p, c.tgt, c.nrm, m.idx, storage)
+            tol = np.full(32, REC_TOL)
+            if storage == rs.F32:
+                tol[[27, 29]] = rs.D2_F32_REL
+            assert total[28] == ref_rec[28]
+            assert (np.abs(total - ref_rec) <= tol * scale).all(), f"{what}: {np.abs(total - ref_rec) / np.maximum(tol * scale, 1e-300)}"
+            print(f"SEARCH {what}: {int(ref_rec[28])} matches of {len(c.src)}, {int((rk[~none] == 1).sum())} in shard 1")
+    finally:
+        for ses in parts:
+            ses.close()
+        other.close()
+
+
+# ---- k. a persistent-map target
+@pytest.mark.parametrize("storage", rs.STORAGES)
+def test_persistent_map_target(ab, storage):
+    """two map_insert_scan calls with max_corr_hint leave the map in its persistent form (row-paged index, no replica); the keys and the record
+    are taken against it as it is, the map is downloaded (which folds it) only afterwards, and the brute force runs against the
+    downloaded points"""
+    be = ab[storage]
+    src, tgt, _ = rs.void_cloud(0.3)
+    crop = backend.make_crop(backend.CROP_MAX_RADIUS, center=tuple(rs.VOID_CENTRE), rmax=2.5)
+    mp = be.upload(np.zeros((0, 3)))
+    scans = [be.upload(tgt[:10_000]), be.upload(tgt[10_000:])]
+    ses = Session(be, src, None, None, 1.0, None, target_id=mp)
+    try:
+        for sc in scans:
+            be.map_insert_scan(mp, sc, np.eye(4), 0.1, crop, max_corr_hint=1.0)
+        assert be.is_persistent_map(mp)
+        ses.begin(np.eye(4), method=backend.ICP_POINT_TO_POINT)
+        keys = ses.keys(rank=2)
+        rec = ses.record()
+        assert be.is_persistent_map(mp), "taking keys folded the map"
+        pts, _ = be.download(mp)
+        m = rs.nearest_within(src, pts, np.eye(4), 1.0, storage)
+        what = f"persistent map {storage}"
+        _premises(m, 1.0, what)
+        assert 15_000 < len(pts) <= len(tgt)
+        _check_keys(keys, m, storage, False, 2, None, 0, len(src), what)  # (positions are slots of the row-paged index, not array positions)
+        _check_record(rec, m, pts, None, storage, backend.ICP_POINT_TO_POINT, 0, len(src), what)
+    finally:
+        for c in scans:
+            be.free(c)
+        ses.close()
+
+
+# ---- l. the fused kernel (the shipped library: candidate sets on, lanes re-dealt)
+def _fused_inputs():
+    out = []
+    for v in rs.STAGE_VOIDS:
+        for cell in rs.STAGE_CELLS:
+            out.append((f"void{v}-cell{cell}", v, cell, 1.0, None, np.eye(4), backend.ICP_POINT_TO_PLANE))
+    out.append(("void0.9-r0.5", 0.9, 0.25, 0.5, None, np.eye(4), backend.ICP_POINT_TO_PLANE))
+    for k in range(len(rs.CROPS)):
+        out.append((f"crop{k}", rs.CROP_VOID, 0.25, 1.0, k, np.eye(4), backend.ICP_POINT_TO_PLANE))
+    for v in (0.0, 0.6):
+        for method in (backend.ICP_POINT_TO_POINT, backend.ICP_POINT_TO_PLANE):
+            out.append((f"later-void{v}-method{method}", v, 0.25, 1.0, None, rs.LATER_INIT, method))
+    return out
+
+
+FUSED = _fused_inputs()
+
+
+@pytest.mark.parametrize("storage", rs.STORAGES)
+@pytest.mark.parametrize("inp", FUSED, ids=[f[0] for f in FUSED])
+def test_fused_kernel_counts_and_rmse(shipped, inp, storage):
+    """o3ds_icp_register_dev, o3ds_icp_register_multi and o3ds_icp_register_batch (lists of one) with max_iteration 0..3 and fixed
+    criteria: n_corr is the brute-force count at the returned pose, inlier_rmse is sqrt(sum d2 / n) within the d2 bound"""
+    from oracle import pyoracle
+
+    name, void, cell, r, crop_k, T0, method = inp
+    be = shipped[storage]
+    src, tgt, nrm = rs.void_cloud(void, query_radius=None if r == 1.0 else rs.VOID_QUERY_RADIUS_MIXED)  # (the queries of stage_case)
+    crop = keep = None
+    if crop_k is not None:
+        crop = backend.make_crop(**rs.CROPS[crop_k])
+        keep = pyoracle.crop_indices(rs.to_storage(tgt, storage), pyoracle.make_crop(**rs.CROPS[crop_k]))
+    bound = rs.D2_F32_REL if storage == rs.F32 else 2.0 ** -23
+    s, t = be.upload(src), be.upload(tgt, nrm)
+    try:
+        be.build_index(t, r, cell)
+        seen = {}
+        for k in range(4):
+            params = be._params(r, k, 0.0, 0.0, method)
+            runs = {"dev": be.icp_register_dev(s, t, r, init=T0, max_iter=k, rel_fitness=0.0, rel_rmse=0.0, target_crop=crop, method=method),
+                    "multi": be.icp_register_multi(s, [t], form=be.MULTI_UNION, crop=crop, init=T0, params=params)}
+            res, status = be.icp_register_batch([(s, t, crop, T0)], params)
+            assert status == [0]
+            runs["batch"] = res[0]
+            for form, got in runs.items():
+                what = f"fused {name} {storage} {form} max_iter {k}"
+                key = got["transformation"].tobytes()
+                if key not in seen:
+                    m = rs.nearest_within(src, tgt, got["transformation"], r, storage, keep=keep)
+                    _premises(m, r, what)
+                    seen[key] = rs.record(m.p, tgt, nrm, m.idx, storage, method)[0]
+                ref = seen[key]
+                assert got["n_corr"] == ref[28], f"{what}: n_corr {got['n_corr']}, brute force {int(ref[28])}"
+                mean = ref[29] / max(ref[28], 1.0)
+                dev = abs(got["inlier_rmse"] ** 2 - mean) / (bound * mean) if mean > 0 else abs(got["inlier_rmse"])
+                print(f"SEARCH {what}: n_corr {got['n_corr']} of {len(src)}, rmse^2 deviation / bound {dev:.3e}")
+                assert dev <= 1.0, f"{what}: inlier_rmse {got['inlier_rmse']} vs {np.sqrt(mean)}"
+    finally:
+        be.free(s)
+        be.free(t)
+
+
+# ---- m. negative control: the inputs reach the far stage
+def test_negative_control_stage_three_skipped(ab, monkeypatch):
+    """O3DS_DEBUG_ACC=16 (A/B library) skips stage 3.  The comparison of the stage cases must then report mismatches on the void-0.9 cloud
+    and none on the void-0 cloud: the inputs reach the far stage, and the comparison notices a search that stops early.  The count per
+    case is a lower bound of the queries stage 3 serves (an unproven stage-2 result is often the right one already)."""
+    _path(monkeypatch, "rows")
+    counts = {}
+    for void in rs.STAGE_VOIDS:
+        for cell in (0.25, 0.1):
+            name = f"void{void}-cell{cell}-r1.0"
+            c, m = _case(name), _ref(name, rs.F32)
+            ses = Session(ab[rs.F32], c.src, c.tgt, c.nrm, c.r, c.cell)
+            try:
+                monkeypatch.setenv("O3DS_DEBUG_ACC", "16")
+                ses.begin(c.T)
+                none, d2, _, _ = rs.decode_keys(ses.keys().cpu().numpy())
+                monkeypatch.delenv("O3DS_DEBUG_ACC")
+            finally:
+                ses.close()
+            wrong = none != (m.idx < 0)
+            both = ~none & (m.idx >= 0)
+            wrong[both] = np.abs(d2[both].astype(np.float64) - m.d2[both]) > rs.D2_F32_REL * m.d2[both]
+            counts[name] = int(wrong.sum())
+            print(f"SEARCH control {name}: {counts[name]} of {len(c.src)} queries wrong without stage 3")
+    assert counts["void0.9-cell0.25-r1.0"] > 0 and counts["void0.9-cell0.1-r1.0"] > 0
+    assert counts["void0.0-cell0.25-r1.0"] == 0
