@@ -1627,25 +1627,30 @@ __device__ __forceinline__ void solve6_wave(const double* rec, double* x_out, in
 // Each step checks that the pivot it was handed is the STRICT maximum of the remaining diagonal (then Eigen's first-maximum rule picks
 // it too); if any step fails the result is discarded and the caller runs the searching solve.  Returns whether the order held.
 __device__ __forceinline__ bool solve6_wave_ordered(const double* rec, double* x_out, int lane, unsigned order) {
+  // One wavefront alone on its SIMD issues an instruction every four cycles whatever it is, so this path costs its instruction COUNT
+  // (profiles/serial_step.txt).  Hence: no divergent loads (lanes >= 6 carry a copy of position 5's row, which nothing reads), and the
+  // record's packed upper triangle is addressed by a nibble table -- element (r, c), r <= c, sits at r (11 - r) / 2 + c.
+  // All 64 lanes load, so the indices must be in bounds for ANY order word: only solve6_wave writes IcpStateDev::pad, with fields 0..5
+  // (indices <= 20); a field of 6 or 7 would still read inside the kRec = 32 doubles of the record (table nibble <= 15, plus c <= 7).
   const int pt = (int)((order >> (3 * min(lane, 5))) & 7u);
-  double a[6], b = 0.0;
+  double a[6], b;
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     const int pj = (int)((order >> (3 * j)) & 7u);
     const int r = min(pt, pj), c = max(pt, pj);
-    a[j] = lane < 6 ? rec[r * 6 - (r * (r - 1)) / 2 + (c - r)] : (j == 0 ? 1.0 : 0.0);
+    a[j] = rec[(int)((0xFEC950u >> (4 * r)) & 15u) + c];
   }
-  if (lane < 6) b = -rec[21 + pt];
-  bool bad = false;
+  b = -rec[21 + pt];
+  // worse[k], bit k: the diagonal entry of position k was at least as large as a pivot handed in before it.  One comparison per
+  // (step, later position) straight on the register that holds that entry, instead of first selecting every lane's own diagonal
+  unsigned long long worse[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
   double rd[6];
 #pragma unroll
   for (int s = 0; s < 6; ++s) {
-    double diag = a[0];
-#pragma unroll
-    for (int k = 1; k < 6; ++k) diag = lane == k ? a[k] : diag;
     const double d = O3DS_BCAST(a[s], s);
     const double bs = O3DS_BCAST(b, s);
-    bad |= lane > s && lane < 6 && fabs(diag) >= fabs(d);
+#pragma unroll
+    for (int k = s + 1; k < 6; ++k) worse[k] |= __ballot(fabs(a[k]) >= fabs(d));
     rd[s] = fabs(d) > 2.2250738585072014e-308 ? 1.0 / d : 0.0;
     const double l = d != 0.0 ? a[s] * (1.0 / d) : a[s];
     const bool below = lane > s && lane < 6;
@@ -1656,7 +1661,10 @@ __device__ __forceinline__ bool solve6_wave_ordered(const double* rec, double* x
     }
     if (below) b = fma(-l, bs, b);
   }
-  if (__ballot(bad) != 0ull) return false;
+  unsigned long long bad = 0ull;
+#pragma unroll
+  for (int k = 1; k < 6; ++k) bad |= worse[k] & (1ull << k);
+  if (bad != 0ull) return false;
   double xs[6];
   double mine = 0.0;
 #pragma unroll
@@ -1785,12 +1793,13 @@ __device__ inline void umeyama_from_record(const double* rec, double Ucm[16]) {
 // [O3D] RegistrationICP loop body after the correspondence pass: convergence test, solve, T <- U*T.
 // Called by every thread of one workgroup (>= 128 threads) with the record in LDS.  This tail is on the critical path of
 // every ICP iteration, so its two dependent chains run on two wavefronts (= two SIMDs) at once and meet at ONE workgroup
-// barrier: wavefront 0 solves (lane-parallel), takes the three sincos in three lanes (broadcast with v_readlane) and forms
-// U*T speculatively; wavefront 1 computes fitness / rmse and the convergence test and decides whether the update is
-// applied.  (Measured inside icp_fused_kernel: 4.7 us for the one-thread-plus-barriers form this replaces.)
+// barrier: wavefront 0 solves (lane-parallel), takes the three sincos in three lanes (broadcast with v_readlane), builds U with
+// one entry per lane and forms U*T speculatively from the lanes' registers; wavefront 1 computes fitness / rmse and the convergence
+// test and decides whether the update is applied.  (Measured inside icp_fused_kernel: 4.7 us for the one-thread-plus-barriers form
+// this replaces.)
 __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev* st, unsigned long long n_src_total, int max_iter,
                                                double rel_fitness, double rel_rmse, double* s_x /* [8] */, double* s_sc /* [8]: scratch of the solve (pivot order) */,
-                                               double* s_U /* [16] */, double* s_T /* [16] */, int* s_go,
+                                               double* s_U /* [16] */, int* s_go,
                                                unsigned long long* tr = nullptr /* 8 timestamps, development aid */,
                                                int method = O3DS_ICP_POINT_TO_PLANE,
                                                float* s_margin = nullptr /* [2]: |R - I|_F and |t| of the update (candidate-set margin) */,
@@ -1805,9 +1814,11 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
   const double count = s_rec[kRecCount];
   double tnew = 0.0;
   if (wv == 0 && !fold_only) {
-    if (lane < 16) s_T[lane] = st->T[lane];
-    if (lane < 8) s_x[lane] = 0.0;
-    lds_wave_sync();
+    // lane 4 c + r forms entry (r, c) of U * T: its column of T is fetched now and has long arrived when the solve is through
+    double tc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tc[k] = st->T[(lane & 12) + k];
+    double u = 0.0;  // lane l < 16: U[l], column-major
     if (method == O3DS_ICP_POINT_TO_POINT) {  // closed form: U straight from the record, no 6-vector (uniform branch)
       if (lane == 0) {
         double Ucm[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -1816,7 +1827,11 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
         for (int k = 0; k < 16; ++k) s_U[k] = Ucm[k];
       }
       lds_wave_sync();
+      u = s_U[lane & 15];
     } else {
+    // (no wavefront sync between this zeroing and the solve's own stores to s_x: both are LDS stores of this one wavefront, which
+    // complete in program order, and the compiler keeps two stores that may alias in order.  The zeroing must stay in front of the solve.)
+    if (lane < 8) s_x[lane] = 0.0;
     if (count > 0.0) {  // empty correspondence set => identity update (x = 0)
       // the pivot order of the previous iteration's solve travels in the state (bit 31: valid; 3 bits per position)
       const unsigned order = (unsigned)st->pad;
@@ -1833,8 +1848,8 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
           st->pad = (int)o;
         }
       }
-      lds_wave_sync();
     }
+    lds_wave_sync();
     O3DS_TSTAMP(2);
     double sn = 0.0, cs = 1.0;
     const double ang = s_x[lane < 6 ? lane : 0];
@@ -1843,32 +1858,37 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
     const double ca = O3DS_BCAST(cs, 0), cb = O3DS_BCAST(cs, 1), cg = O3DS_BCAST(cs, 2);
     const double tx = O3DS_BCAST(ang, 3), ty = O3DS_BCAST(ang, 4), tz = O3DS_BCAST(ang, 5);
     O3DS_TSTAMP(3);
-    if (lane < 16) {  // [O3D] TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0), t = x[3:6]; column-major
-      double v;
-      switch (lane) {
-        case 0: v = cg * cb; break;
-        case 1: v = sg * cb; break;
-        case 2: v = -sb; break;
-        case 4: v = cg * sb * sa - sg * ca; break;
-        case 5: v = sg * sb * sa + cg * ca; break;
-        case 6: v = cb * sa; break;
-        case 8: v = cg * sb * ca + sg * sa; break;
-        case 9: v = sg * sb * ca - cg * sa; break;
-        case 10: v = cb * ca; break;
-        case 12: v = tx; break;
-        case 13: v = ty; break;
-        case 14: v = tz; break;
-        case 15: v = 1.0; break;
-        default: v = 0.0; break;
-      }
-      s_U[lane] = v;
+    // [O3D] TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0), t = x[3:6]; column-major.  The operands are wave-uniform, so every
+    // lane evaluates all nine rotation entries -- each product and the one sum or difference of an entry in the order the reference
+    // writes them, (a b) c +- d e -- and then keeps its own: eighteen operations in one instruction stream, where a switch over the
+    // lane ran thirteen arms one after the other, each under its own EXEC mask.
+    {
+      const double cgsb = cg * sb, sgsb = sg * sb;
+      const double u0 = cg * cb, u1 = sg * cb, u2 = -sb;
+      const double u4 = cgsb * sa - sg * ca, u5 = sgsb * sa + cg * ca, u6 = cb * sa;
+      const double u8 = cgsb * ca + sg * sa, u9 = sgsb * ca - cg * sa, u10 = cb * ca;
+      u = lane == 0 ? u0 : u;
+      u = lane == 1 ? u1 : u;
+      u = lane == 2 ? u2 : u;
+      u = lane == 4 ? u4 : u;
+      u = lane == 5 ? u5 : u;
+      u = lane == 6 ? u6 : u;
+      u = lane == 8 ? u8 : u;
+      u = lane == 9 ? u9 : u;
+      u = lane == 10 ? u10 : u;
+      u = lane == 12 ? tx : u;
+      u = lane == 13 ? ty : u;
+      u = lane == 14 ? tz : u;
+      u = lane == 15 ? 1.0 : u;
     }
-    lds_wave_sync();
+    if (lane < 16) s_U[lane] = u;  // (in passing, for the margin below: nothing of this wavefront reads it)
     }
-    if (lane < 16) {  // U * T
-      const int c = lane >> 2, r = lane & 3;
+    // U * T with U taken from the lanes that hold it: no trip through LDS, no wait between U and the product
 #pragma unroll
-      for (int k = 0; k < 4; ++k) tnew = fma(s_U[k * 4 + r], s_T[c * 4 + k], tnew);
+    for (int k = 0; k < 4; ++k) {
+      const int from = (k * 4 + (lane & 3)) << 2;
+      const double uk = __hiloint2double(__builtin_amdgcn_ds_bpermute(from, __double2hiint(u)), __builtin_amdgcn_ds_bpermute(from, __double2loint(u)));
+      tnew = fma(uk, tc[k], tnew);
     }
   } else if (wv == 1) {
     const double fitness = count > 0.0 ? count / (double)n_src_total : 0.0;
@@ -1921,14 +1941,14 @@ __global__ __launch_bounds__(kUpdBlock) void icp_reduce_update_kernel(const doub
   }
   __shared__ double s_part[2 * (kUpdBlock / 32) * kRec];
   __shared__ double s_out[kRec];
-  __shared__ double s_x[8], s_sc[8], s_U[16], s_T[16];
+  __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ int s_go;
   reduce_partials(partials, nrows, qt.q, s_part, s_out);
   if (debug_mode == 2) {  // timing experiment: reduction only
     if (threadIdx.x == 0) { state->pass += 1; state->iterations += 1; state->fitness = s_out[28]; if (state->iterations > max_iter) state->done = 1; }
     return;
   }
-  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, s_T, &s_go, nullptr, method);
+  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
 }
 
 // sharded path: the record was all-reduced by the caller
@@ -1936,11 +1956,11 @@ __global__ __launch_bounds__(128) void icp_update_kernel(const double* __restric
                                                         int max_iter, double rel_fitness, double rel_rmse, int method) {
   if (state->done) return;
   __shared__ double s_out[kRec];
-  __shared__ double s_x[8], s_sc[8], s_U[16], s_T[16];
+  __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ int s_go;
   if (threadIdx.x < kRec) s_out[threadIdx.x] = record[threadIdx.x];
   __syncthreads();
-  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, s_T, &s_go, nullptr, method);
+  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2017,7 +2037,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   __shared__ double s_red[kParts][kRec];
   __shared__ int2 s_seg[kQPB * kSegMax];
   __shared__ double s_out[kRec];
-  __shared__ double s_x[8], s_sc[8], s_U[16], s_T[16];
+  __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ IcpStateDev s_st;
   __shared__ int s_set[kQPB * (1 + kSetCap)];
   __shared__ float s_margin[2];
@@ -2089,7 +2109,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   }
   O3DS_STAMP(1);
   if (!first) {
-    icp_step_block(s_out, &s_st, n_src_total, fa.max_iter, fa.rel_fitness, fa.rel_rmse, s_x, s_sc, s_U, s_T, &s_go,
+    icp_step_block(s_out, &s_st, n_src_total, fa.max_iter, fa.rel_fitness, fa.rel_rmse, s_x, s_sc, s_U, &s_go,
                    fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 8 : nullptr, fa.pass.method, s_margin,
                    /* fold_only: the last launch of a registration that ran out of iterations */ s_st.iterations >= fa.max_iter);
     lds_barrier();

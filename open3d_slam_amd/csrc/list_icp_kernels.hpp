@@ -165,10 +165,10 @@ __device__ __forceinline__ void list_reduce_update(const double* __restrict__ pa
                                                    unsigned long long den, int max_iter, double rel_fitness, double rel_rmse, int method) {
   __shared__ double s_part[2 * (kUpdBlock / 32) * kRec];
   __shared__ double s_out[kRec];
-  __shared__ double s_x[8], s_sc[8], s_U[16], s_T[16];
+  __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ int s_go;
   reduce_partials(partials, nrows, q_hi, s_part, s_out);
-  icp_step_block(s_out, state, den, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, s_T, &s_go, nullptr, method);
+  icp_step_block(s_out, state, den, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
 }
 
 }  // namespace o3ds
