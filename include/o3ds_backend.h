@@ -224,6 +224,12 @@ int o3ds_icp_overlap_next(o3ds_handle h, o3ds_overlap_fn fn, void* arg);
 /* RegistrationIcpGeneralized::registerClouds (CloudRegistration.cpp:16-21) = [O3D] RegistrationGeneralizedICP with a
  * default TransformationEstimationForGeneralizedICP (epsilon 1e-3): per-point covariances C = Rx diag(eps,1,1) Rx^T built from
  * the clouds' (unit) normals, residual (Ct + R Cs R^T)^-1/2 (p - q), same loop / solve / convergence test as point-to-plane.
+ * The device evaluates the closed form C = I - k n n^T (k = 1 - eps), with n := e1 where the stored normal has x < -0.99
+ * ([O3D] GetRotationFromE1ToX's special case) or is the zero vector (for which the same function returns the identity: the
+ * voxel merges of the pipeline store one where the merged normals cancel); both are decided on the stored normal, the
+ * source's before it is rotated by the pose.  Out of scope: NaN normals, and non-unit normals other than zero -- the model is
+ * stated for unit normals, and no producer in the pipeline makes others (both voxel merges renormalise, the estimator
+ * normalises).
  * open3d_slam always calls estimateNormalsOrCovariancesIfNeeded first (CloudRegistration.cpp:22-30); a cloud that still has no
  * normals (null pointer / device cloud without normals) gets [O3D] InitializePointCloudForGeneralizedICP's treatment:
  * EstimateNormals(KDTreeSearchParamKNN(20)) on a copy, the caller's cloud is left as it was. */

@@ -839,7 +839,9 @@ __device__ __forceinline__ double to_sgpr(double v) {
 // in s_red[0][0..31]... more precisely returns it in `row_val` of threads 0..31.
 // [O3D] GeneralizedICP (reference call site CloudRegistration.cpp:16-21), closed form for covariances built
 // from unit normals: C = Rx diag(eps,1,1) Rx^T = I - k n n^T (k = 1 - eps; n := e1 when n.x < -0.99, GetRotationFromE1ToX's
-// special case), so M = Ct + R Cs R^T = 2I - k (a a^T + b b^T).  With A = [-[p]x | I] and W = M^-1/2 the three residual rows
+// special case, and when n is the zero vector, for which the same function returns the identity as well: c = 0, v = 0 -- a voxel merge
+// whose normals cancel stores one; write_record applies both rules to the STORED normal, the source's before it is rotated), so
+// M = Ct + R Cs R^T = 2I - k (a a^T + b b^T).  With A = [-[p]x | I] and W = M^-1/2 the three residual rows
 // W d and Jacobian rows W A contribute  J^T J = A^T M^-1 A  and  J^T r = A^T M^-1 d : only M^-1 is needed (3x3 cofactors).
 // Writes the 21 + 6 + 3 record values of ONE correspondence.
 __device__ __forceinline__ void gicp_record(double px, double py, double pz, double dx, double dy, double dz, const double a[3],
@@ -1038,11 +1040,12 @@ __device__ __forceinline__ void write_record(const IcpPassArgs& a, double* rec, 
   if (kGicp) {
     const P4 ns = ((const P4*)a.snrm)[a.first + i];
     double sa[3] = {(double)ns.x, (double)ns.y, (double)ns.z};
-    if (sa[0] < -0.99) sa[0] = 1.0, sa[1] = 0.0, sa[2] = 0.0;  // GetRotationFromE1ToX special case (decided on the stored normal)
+    // GetRotationFromE1ToX returns the identity for x < -0.99 and for the zero vector: n := e1 (decided on the stored normal)
+    if (sa[0] < -0.99 || (sa[0] == 0.0 && sa[1] == 0.0 && sa[2] == 0.0)) sa[0] = 1.0, sa[1] = 0.0, sa[2] = 0.0;
     const double av[3] = {t00 * sa[0] + t01 * sa[1] + t02 * sa[2], t10 * sa[0] + t11 * sa[1] + t12 * sa[2],
                           t20 * sa[0] + t21 * sa[1] + t22 * sa[2]};  // covariance rotates with the cloud
     double bv[3] = {nx, ny, nz};
-    if (bv[0] < -0.99) bv[0] = 1.0, bv[1] = 0.0, bv[2] = 0.0;
+    if (bv[0] < -0.99 || (bv[0] == 0.0 && bv[1] == 0.0 && bv[2] == 0.0)) bv[0] = 1.0, bv[1] = 0.0, bv[2] = 0.0;
     gicp_record(px, py, pz, dx, dy, dz, av, bv, a.gicp_k, rec);
   } else {
     rec[0] = py * nz - pz * ny;  // J = [p x n ; n]

@@ -25,7 +25,9 @@ import numpy as np
 NO_KEY = 0x7FFFFFFFFFFFFFFF
 F32, F64 = "f32", "f64"
 STORAGES = (F32, F64)
-METHOD_POINT_TO_PLANE, METHOD_POINT_TO_POINT = 0, 2  # o3ds_icp_method
+METHOD_POINT_TO_PLANE, METHOD_GENERALIZED, METHOD_POINT_TO_POINT = 0, 1, 2  # o3ds_icp_method
+GICP_EPSILON = 1e-3  # [O3D] TransformationEstimationForGeneralizedICP's default, and the handle's
+LD = np.longdouble   # 64-bit mantissa on x86-64: the extended precision of the generalized record
 
 
 def to_storage(a, storage) -> np.ndarray:
@@ -91,11 +93,13 @@ def nearest_within(src, tgt, T, r, storage, keep=None, chunk=64) -> Matches:
     return Matches(idx, np.where(idx >= 0, best, np.inf), gap, best, p, q)
 
 
-def record(p, tgt, nrm, idx, storage, method=METHOD_POINT_TO_PLANE):
+def record(p, tgt, nrm, idx, storage, method=METHOD_POINT_TO_PLANE, src_nrm=None, T=None, eps=GICP_EPSILON):
     """(record[32], scale[32]): the step record of o3ds_backend.h over the matches idx (-1 = none) of the transformed, unrounded source
     points p, and per term the sum of |addends|.  Point-to-plane: [0..20] upper triangle of JtJ row-major, [21..26] Jtr, [27] sum r^2,
     [28] count, [29] sum d^2, J = [p x n ; n], r = (p - t) . n.  Point-to-point: [0..8] sum t_a p_b row-major, [9..11] sum p,
-    [12..14] sum t, [28], [29]."""
+    [12..14] sum t, [28], [29].  Generalized (needs src_nrm and the pose T): record_gicp, whose scale is its own."""
+    if method == METHOD_GENERALIZED:
+        return record_gicp(p, tgt, nrm, src_nrm, idx, T, eps, storage)
     t_all = to_storage(np.asarray(tgt, dtype=np.float64).reshape(-1, 3), storage)
     m = np.flatnonzero(np.asarray(idx) >= 0)
     P = np.asarray(p, dtype=np.float64)[m]
@@ -136,8 +140,131 @@ def record(p, tgt, nrm, idx, storage, method=METHOD_POINT_TO_PLANE):
     return rec, scale
 
 
+# ---- the generalized estimator ([O3D] TransformationEstimationForGeneralizedICP), per matched pair, in extended precision
+FORM_O3D, FORM_CLOSED = "o3d", "closed"
+
+
+def _skew(v):
+    """[v]x of n vectors: (n, 3) -> (n, 3, 3)"""
+    K = np.zeros((len(v), 3, 3), dtype=v.dtype)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -v[:, 2], v[:, 1], v[:, 2], -v[:, 0], -v[:, 1], v[:, 0]
+    return K
+
+
+def rotation_from_e1(x):
+    """[O3D] GetRotationFromE1ToX of n stored vectors (n, 3): v = e1 x X, c = e1 . X; the identity if c < -0.99 (decided on the value as
+    it is stored), else I + [v]x + [v]x^2 / (1 + c).  The zero vector has c = 0 and v = 0: the identity, by the formula."""
+    x = np.asarray(x, dtype=LD)
+    v = np.zeros_like(x)
+    v[:, 1], v[:, 2] = -x[:, 2], x[:, 1]
+    K = _skew(v)
+    special = x[:, 0] < -0.99
+    f = LD(1) / np.where(special, LD(1), LD(1) + x[:, 0])
+    Rx = np.eye(3, dtype=LD) + K + np.matmul(K, K) * f[:, None, None]
+    Rx[special] = np.eye(3, dtype=LD)
+    return Rx
+
+
+def covariance_from_normals(x, eps):
+    """[O3D] the covariance the generalized estimator gives a point with (stored) normal x: Rx diag(eps, 1, 1) Rx^T, (n, 3, 3)"""
+    Rx = rotation_from_e1(x)
+    return np.matmul(Rx * np.array([LD(eps), LD(1), LD(1)]), np.transpose(Rx, (0, 2, 1)))
+
+
+def _inverse3(M):
+    """inverses of n symmetric 3x3 matrices in extended precision: adjugate over determinant, then one Newton step B + B (I - M B)"""
+    c = np.empty_like(M)
+    for i in range(3):
+        for j in range(3):
+            a, b = [k for k in range(3) if k != i], [k for k in range(3) if k != j]
+            c[:, j, i] = (-1) ** (i + j) * (M[:, a[0], b[0]] * M[:, a[1], b[1]] - M[:, a[0], b[1]] * M[:, a[1], b[0]])
+    det = M[:, 0, 0] * c[:, 0, 0] + M[:, 0, 1] * c[:, 1, 0] + M[:, 0, 2] * c[:, 2, 0]
+    B = c / det[:, None, None]
+    return B + np.matmul(B, np.eye(3, dtype=LD) - np.matmul(M, B))
+
+
+def gicp_pairs(tgt_nrm, src_nrm, idx, T, eps, storage, form=FORM_O3D, zero_is_e1=True):
+    """(m, B, w) of the matched pairs i -> idx[i] (m: their query indices): B = M^-1 (n, 3, 3) in extended precision and w = |B|_2 =
+    1 / lambda_min(M).
+      FORM_O3D     M = C(nt) + R C(ns) R^T with the covariances of covariance_from_normals, from the UNROTATED stored normals; R is the
+                   3x3 block of the pose as it is.
+      FORM_CLOSED  what the device documents (icp_kernels.hpp above gicp_record) for unit normals: M = 2I - k (a a^T + b b^T), k = 1 - eps
+                   in f64, b = nt and a = R ns, where a stored normal with x < -0.99 -- and, with zero_is_e1, the zero vector -- counts as e1
+                   (on the source side before the rotation)."""
+    idx = np.asarray(idx)
+    m = np.flatnonzero(idx >= 0)
+    nt = to_storage(np.asarray(tgt_nrm, dtype=np.float64).reshape(-1, 3), storage)[idx[m]].astype(LD)
+    ns = to_storage(np.asarray(src_nrm, dtype=np.float64).reshape(-1, 3), storage)[m].astype(LD)
+    R = np.asarray(T, dtype=np.float64)[:3, :3].astype(LD)
+    if form == FORM_O3D:
+        M = covariance_from_normals(nt, eps) + np.matmul(np.matmul(R, covariance_from_normals(ns, eps)), R.T)
+    else:
+        def as_e1(x):
+            x = x.copy()
+            fire = x[:, 0] < -0.99
+            if zero_is_e1:
+                fire |= (x == 0).all(axis=1)
+            x[fire] = np.array([1, 0, 0], dtype=LD)
+            return x
+        a, b = np.matmul(as_e1(ns), R.T), as_e1(nt)
+        k = LD(1.0 - float(eps))
+        M = 2 * np.eye(3, dtype=LD) - k * (a[:, :, None] * a[:, None, :] + b[:, :, None] * b[:, None, :])
+    if len(m) == 0:
+        return m, M, np.zeros(0)
+    return m, _inverse3(M), 1.0 / np.linalg.eigvalsh(M.astype(np.float64))[:, 0]
+
+
+def gicp_defect(tgt_nrm, src_nrm, idx, T, eps, storage, zero_is_e1=True) -> float:
+    """the largest |B_closed - B_o3d| (entry-wise) over |B|_2 of a pair: how far the closed form stands from Open3D's own form on these
+    stored normals (unit only to the storage's rounding) -- a term of the record built from one form differs from the other's by at most
+    this times its scale.  One reference against the other; no device in it."""
+    _, Bo, w = gicp_pairs(tgt_nrm, src_nrm, idx, T, eps, storage, FORM_O3D)
+    _, Bc, _ = gicp_pairs(tgt_nrm, src_nrm, idx, T, eps, storage, FORM_CLOSED, zero_is_e1)
+    if len(w) == 0:
+        return 0.0
+    return float((np.abs(Bc - Bo).max(axis=(1, 2)).astype(np.float64) / w).max())
+
+
+def record_gicp(p, tgt, tgt_nrm, src_nrm, idx, T, eps, storage, form=FORM_O3D, zero_is_e1=True):
+    """(record[32], scale[32]) of the generalized estimator over the matches idx of the transformed, unrounded source points p: per pair
+    B = M^-1 (gicp_pairs), A = [-[p]x | I], d = p - q with q the stored target point; [0..20] upper triangle of sum A^T B A row-major,
+    [21..26] sum A^T B d, [27] sum d^T B d, [28] count, [29] sum |d|^2.  The addends are formed in extended precision, rounded to f64 once
+    and summed exactly.  Scale: with w = |B|_2, alpha_a = |column a of A|_1 (1 for a >= 3) and delta = |d|_1 of the pair,
+    scale[(a, b)] = sum w alpha_a alpha_b, scale[21 + a] = sum w alpha_a delta, scale[27] = sum w delta^2 -- the device's inverse is
+    accurate relative to |B|, not entry by entry, so the sum of |addends| would be too tight where B is 0.5 beside entries of 500."""
+    m, B, w = gicp_pairs(tgt_nrm, src_nrm, idx, T, eps, storage, form, zero_is_e1)
+    t_all = to_storage(np.asarray(tgt, dtype=np.float64).reshape(-1, 3), storage)
+    P = np.asarray(p, dtype=np.float64)[m].astype(LD)
+    D = P - t_all[np.asarray(idx)[m]].astype(LD)
+    A = np.zeros((len(m), 3, 6), dtype=LD)
+    A[:, :, :3] = -_skew(P)
+    A[:, :, 3:] = np.eye(3, dtype=LD)
+    BA = np.matmul(B, A)
+    H = np.matmul(np.transpose(A, (0, 2, 1)), BA)                      # A^T B A
+    g = np.matmul(np.transpose(BA, (0, 2, 1)), D[:, :, None])[:, :, 0]  # A^T B d  (B symmetric)
+    e = (D[:, None, :] @ np.matmul(B, D[:, :, None]))[:, 0, 0]          # d^T B d
+    alpha = np.abs(A).sum(axis=1).astype(np.float64)
+    delta = np.abs(D).sum(axis=1).astype(np.float64)
+    terms, scales = [None] * 32, [None] * 32
+    k = 0
+    for a in range(6):
+        for b in range(a, 6):
+            terms[k], scales[k] = H[:, a, b], w * alpha[:, a] * alpha[:, b]
+            k += 1
+    for a in range(6):
+        terms[21 + a], scales[21 + a] = g[:, a], w * alpha[:, a] * delta
+    terms[27], scales[27] = e, w * delta * delta
+    terms[28] = scales[28] = np.ones(len(m))
+    terms[29] = scales[29] = (D * D).sum(axis=1)
+    rec, scale = np.zeros(32), np.zeros(32)
+    for k in range(30):
+        rec[k] = math.fsum(np.asarray(terms[k]).astype(np.float64).tolist())
+        scale[k] = math.fsum(np.abs(np.asarray(scales[k]).astype(np.float64)).tolist())
+    return rec, scale
+
+
 def jtj_from_record(rec):
-    """(JtJ 6x6, Jtr 6, sum r^2) of a point-to-plane record"""
+    """(JtJ 6x6, Jtr 6, sum r^2) of a point-to-plane (or generalized) record"""
     A = np.zeros((6, 6))
     k = 0
     for a in range(6):
@@ -380,6 +507,155 @@ def large_cases():
 
 # i. later passes: an init that is off by (0.4, -0.3, 0.1) m and 3 degrees
 LATER_INIT = rigid((1.5, -2.0, 1.7), (0.4, -0.3, 0.1))  # |rotation| ~ 3 degrees
+
+
+# j. the generalized estimator: per-point source normals (generators of their own: the arrays above do not depend on them), poses, epsilons
+# and the edge values of the normals
+SOURCE_NORMAL_SEED = 4  # (chosen so that the later passes' poses keep the gap premise: test_premises_of_the_generalized_later_passes)
+
+
+def lattice_source_normals(n_src):
+    return unit_normals(np.random.default_rng([SOURCE_NORMAL_SEED, 0]), 300)[:n_src]
+
+
+def void_source_normals(void_radius, n_src=300):
+    return unit_normals(np.random.default_rng([SOURCE_NORMAL_SEED, 1 + int(round(10 * void_radius))]), n_src)
+
+
+def about(centre, T):
+    """the rigid motion T carried out about `centre` instead of the origin (its translation added afterwards)"""
+    out = np.array(T, dtype=np.float64)
+    c = np.asarray(centre, dtype=np.float64)
+    out[:3, 3] = c - out[:3, :3] @ c + out[:3, 3]
+    return out
+
+
+YAW170 = about(VOID_CENTRE, rigid((0.0, 0.0, 170.0), (0.03, -0.02, 0.04)))  # a 170 degree yaw about the void's centre plus a few centimetres
+GICP_EPSILONS = (1.0, 1e-3, 1e-6)
+X99 = -0.99
+EDGE_X = (("x=-1", -1.0), ("x=-0.99", X99), ("x=-0.99-ulp", float(np.nextafter(X99, -1.0))), ("x=-0.99+ulp", float(np.nextafter(X99, 0.0))),
+          ("x=f32(-0.99)", float(np.float32(X99))), ("x=+1", 1.0), ("zero", None))
+EDGE_GROUP = 12       # matched pairs per group, at least
+EDGE_DUPLICATES = 10
+
+
+class GicpCase(NamedTuple):
+    name: str
+    src: np.ndarray
+    src_nrm: np.ndarray
+    tgt: np.ndarray
+    nrm: np.ndarray
+    r: float
+    cell: float
+    T: np.ndarray
+    eps: float = GICP_EPSILON
+    storages: tuple = STORAGES
+    groups: tuple = ()     # (name, first query, count): contiguous query ranges with one kind of normal each (gicp_edge_case)
+    n_plain: int = 0       # gicp_edge_case: the targets before the duplicates were appended
+
+
+def _with_x(rng, x, n):
+    """n vectors with first component x (exactly) and the rest on the circle that makes them unit"""
+    if x is None:
+        return np.zeros((n, 3))
+    phi = rng.uniform(0.0, 2.0 * math.pi, size=n)
+    s = math.sqrt(max(1.0 - x * x, 0.0))
+    return np.stack([np.full(n, x), s * np.cos(phi), s * np.sin(phi)], axis=1)
+
+
+def gicp_edge_case() -> GicpCase:
+    """The void-0 cloud under YAW170, its normals overwritten in disjoint groups of at least EDGE_GROUP matched pairs.  Target side: the
+    seven EDGE_X values on the matched target point (every query that matches such a point belongs to that group and keeps a random source
+    normal).  Source side, on queries whose match keeps its random normal nt: the same seven values, ns = R^T nt (a = b), ns = -R^T nt,
+    ns orthogonal to R^T nt, R ns = -e1 with a stored x > 0 (the special case must not fire after the rotation), stored ns = -e1 with
+    (R ns).x > 0 (it must fire).  The queries are re-ordered so that every group is one contiguous range (`groups`); the rest stay
+    random.  Ten matched target points outside the target-side groups are appended once more with other normals: the copy has the larger
+    index and must lose."""
+    src, tgt, nrm = void_cloud(0.0)
+    rng = np.random.default_rng([SOURCE_NORMAL_SEED, 99])
+    T, R = YAW170, YAW170[:3, :3]
+    m = nearest_within(src, tgt, T, 1.0, F64)
+    assert (m.idx >= 0).all()
+    nrm = nrm.copy()
+    free = np.ones(len(src), dtype=bool)   # queries not yet in a group
+    order, groups = [], []
+
+    def close_group(name, members):
+        groups.append((name, len(order), len(members)))
+        order.extend(int(i) for i in members)
+        free[members] = False
+
+    for name, x in EDGE_X:   # target side: whole targets, until the group holds EDGE_GROUP pairs
+        members = []
+        for i in np.flatnonzero(free):
+            if len(members) >= EDGE_GROUP:
+                break
+            if not free[i]:
+                continue
+            same = np.flatnonzero(m.idx == m.idx[i])
+            nrm[m.idx[i]] = _with_x(rng, x, 1)[0]
+            members.extend(same.tolist())
+            free[same] = False
+        close_group("tgt " + name, np.array(members))
+    touched = np.unique(m.idx[~free])
+    src_nrm = void_source_normals(0.0).copy()
+    rest = np.flatnonzero(free)
+    k = 0
+
+    def take():
+        nonlocal k
+        out = rest[k:k + EDGE_GROUP]
+        k += EDGE_GROUP
+        return out
+
+    for name, x in EDGE_X:
+        members = take()
+        src_nrm[members] = _with_x(rng, x, len(members))
+        close_group("src " + name, members)
+    for name in ("a=b", "a=-b", "a orthogonal b"):
+        members = take()
+        back = nrm[m.idx[members]] @ R   # rows R^T nt
+        if name == "a=-b":
+            back = -back
+        elif name != "a=b":
+            o = np.cross(back, rng.normal(size=back.shape))
+            back = o / np.linalg.norm(o, axis=1, keepdims=True)
+        src_nrm[members] = back
+        close_group("src " + name, members)
+    members = take()
+    src_nrm[members] = -R[0, :]                    # R^T (-e1): rotates onto -e1
+    close_group("src rotates to -e1", members)
+    members = take()
+    src_nrm[members] = np.array([-1.0, 0.0, 0.0])  # R (-e1) has x = cos 10 deg
+    close_group("src -e1 rotates away", members)
+    order.extend(int(i) for i in rest[k:])
+    order = np.array(order)
+    assert len(order) == len(src) and len(np.unique(order)) == len(src)
+    dup = np.setdiff1d(np.unique(m.idx), touched)[:EDGE_DUPLICATES]
+    assert len(dup) == EDGE_DUPLICATES
+    tgt2 = np.concatenate([tgt, tgt[dup]])
+    nrm2 = np.concatenate([nrm, unit_normals(rng, EDGE_DUPLICATES)])
+    return GicpCase("gicp-edge", src[order], src_nrm[order], tgt2, nrm2, 1.0, 0.25, T, groups=tuple(groups), n_plain=len(tgt))
+
+
+def gicp_cases():
+    """every input of the generalized-record tests that is a plain case (the crop, the later passes and the shards build theirs)"""
+    out = []
+    for n in LATTICE_COUNTS:
+        c = lattice_case(n)
+        out.append(GicpCase(c.name, c.src, lattice_source_normals(n), c.tgt, c.nrm, c.r, c.cell, c.T))
+    for c, v in ((stage_case(0.0, 0.25), 0.0), (stage_case(0.9, 0.25), 0.9), (stage_case(0.9, 0.25, r=0.5), 0.9)):
+        out.append(GicpCase(c.name, c.src, void_source_normals(v), c.tgt, c.nrm, c.r, c.cell, c.T))
+    c = stage_case(0.0, 0.25)
+    for name, T in (("later-init", LATER_INIT), ("yaw170", YAW170)):
+        out.append(GicpCase(f"void0.0-pose-{name}", c.src, void_source_normals(0.0), c.tgt, c.nrm, c.r, c.cell, T))
+    for eps in GICP_EPSILONS:
+        if eps != GICP_EPSILON:
+            out.append(GicpCase(f"void0.0-eps{eps:g}", c.src, void_source_normals(0.0), c.tgt, c.nrm, c.r, c.cell, c.T, eps))
+    for c in large_cases():
+        out.append(GicpCase(c.name, c.src, void_source_normals(0.6), c.tgt, c.nrm, c.r, c.cell, c.T, GICP_EPSILON, c.storages))
+    out.append(gicp_edge_case())
+    return out
 
 
 def all_cases():
