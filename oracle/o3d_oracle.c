@@ -1444,91 +1444,109 @@ void orc_estimate_normals(const double* pts, size_t n, double radius, int max_nn
   orc_estimate_normals_ex(pts, n, radius, max_nn, 0, normals);
 }
 
+/* The normal of point p from its k neighbours idx[0..k), in that order: cumulants summed in list order, covariance (the identity below
+ * three neighbours), eigenvector of the smallest eigenvalue, then (unless raw) NormalizeNormals and OrientNormalsTowardsCameraLocation(0) */
+static void normal_from_list(const double* pts, const double* p, const int32_t* idx, int k, int raw, double* out) {
+  double cov[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (k >= 3) {
+    double c[9] = {0};
+    for (int j = 0; j < k; ++j) {
+      const double* v = pts + 3 * (size_t)idx[j];
+      c[0] += v[0];
+      c[1] += v[1];
+      c[2] += v[2];
+      c[3] += v[0] * v[0];
+      c[4] += v[0] * v[1];
+      c[5] += v[0] * v[2];
+      c[6] += v[1] * v[1];
+      c[7] += v[1] * v[2];
+      c[8] += v[2] * v[2];
+    }
+    for (int j = 0; j < 9; ++j) c[j] /= (double)k;
+    cov[0] = c[3] - c[0] * c[0];
+    cov[4] = c[6] - c[1] * c[1];
+    cov[8] = c[8] - c[2] * c[2];
+    cov[1] = cov[3] = c[4] - c[0] * c[1];
+    cov[2] = cov[6] = c[5] - c[0] * c[2];
+    cov[5] = cov[7] = c[7] - c[1] * c[2];
+  }
+  double nv[3];
+  orc_fast_eigen3x3_min_evec(cov, nv);
+  double nn = sqrt(dot3(nv, nv));
+  if (nn == 0.0) {
+    nv[0] = 0;
+    nv[1] = 0;
+    nv[2] = 1;
+    nn = 1.0;
+  }
+  if (raw) {
+    out[0] = nv[0];
+    out[1] = nv[1];
+    out[2] = nv[2];
+    return;
+  }
+  /* NormalizeNormals */
+  nv[0] /= nn;
+  nv[1] /= nn;
+  nv[2] /= nn;
+  if (isnan(nv[0])) {
+    nv[0] = 0;
+    nv[1] = 0;
+    nv[2] = 1;
+  }
+  /* OrientNormalsTowardsCameraLocation(camera = 0): reference = -p */
+  double ref[3] = {-p[0], -p[1], -p[2]};
+  if (dot3(nv, nv) == 0.0) {
+    double rn = sqrt(dot3(ref, ref));
+    if (rn == 0.0) {
+      nv[0] = 0;
+      nv[1] = 0;
+      nv[2] = 1;
+    } else {
+      nv[0] = ref[0] / rn;
+      nv[1] = ref[1] / rn;
+      nv[2] = ref[2] / rn;
+    }
+  } else if (dot3(nv, ref) < 0.0) {
+    nv[0] = -nv[0];
+    nv[1] = -nv[1];
+    nv[2] = -nv[2];
+  }
+  out[0] = nv[0];
+  out[1] = nv[1];
+  out[2] = nv[2];
+}
+
+/* The part of orc_estimate_normals_ex after the search, for neighbour lists given from outside (a search restated elsewhere: tests):
+ * point i has the cnt[i] neighbours idx[i * stride .. i * stride + cnt[i]), in the order the cumulants are to be summed in */
+void orc_normals_from_neighbours(const double* pts, size_t n, const int32_t* idx, const int32_t* cnt, size_t stride, int raw, double* out) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < (long)n; ++i)
+    normal_from_list(pts, pts + 3 * (size_t)i, idx + (size_t)i * stride, cnt[i], raw, out + 3 * (size_t)i);
+}
+
 /* radius <= 0: KDTreeSearchParamKNN(max_nn) instead of the hybrid search.  raw != 0: [O3D] EstimateNormals alone (ComputeNormal's vector,
  * (0,0,1) when it is zero) without NormalizeNormals / OrientNormalsTowardsCameraLocation -- what
  * InitializePointCloudForGeneralizedICP does to a cloud that has no normals (KNN(20)), call site src/CloudRegistration.cpp:16-21 */
 void orc_estimate_normals_ex(const double* pts, size_t n, double radius, int max_nn, int raw, double* normals) {
   orc_kdtree* t = orc_kdtree_build(pts, n);
+  const size_t stride = (size_t)(max_nn > 0 ? max_nn : 1);
+  int32_t* idx = (int32_t*)malloc(sizeof(int32_t) * stride * (n ? n : 1));
+  int32_t* cnt = (int32_t*)malloc(sizeof(int32_t) * (n ? n : 1));
 #pragma omp parallel
   {
-    int32_t* idx = (int32_t*)malloc(sizeof(int32_t) * (size_t)(max_nn > 0 ? max_nn : 1));
-    double* d2 = (double*)malloc(sizeof(double) * (size_t)(max_nn > 0 ? max_nn : 1));
+    double* d2 = (double*)malloc(sizeof(double) * stride);
 #pragma omp for schedule(static)
     for (long i = 0; i < (long)n; ++i) {
       const double* p = pts + 3 * (size_t)i;
-      int k = radius > 0.0 ? orc_kdtree_search_hybrid(t, p, radius, max_nn, idx, d2) : orc_kdtree_search_knn(t, p, max_nn, idx, d2);
-      double cov[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      if (k >= 3) {
-        double c[9] = {0};
-        for (int j = 0; j < k; ++j) {
-          const double* v = pts + 3 * (size_t)idx[j];
-          c[0] += v[0];
-          c[1] += v[1];
-          c[2] += v[2];
-          c[3] += v[0] * v[0];
-          c[4] += v[0] * v[1];
-          c[5] += v[0] * v[2];
-          c[6] += v[1] * v[1];
-          c[7] += v[1] * v[2];
-          c[8] += v[2] * v[2];
-        }
-        for (int j = 0; j < 9; ++j) c[j] /= (double)k;
-        cov[0] = c[3] - c[0] * c[0];
-        cov[4] = c[6] - c[1] * c[1];
-        cov[8] = c[8] - c[2] * c[2];
-        cov[1] = cov[3] = c[4] - c[0] * c[1];
-        cov[2] = cov[6] = c[5] - c[0] * c[2];
-        cov[5] = cov[7] = c[7] - c[1] * c[2];
-      }
-      double nv[3];
-      orc_fast_eigen3x3_min_evec(cov, nv);
-      double nn = sqrt(dot3(nv, nv));
-      if (nn == 0.0) {
-        nv[0] = 0;
-        nv[1] = 0;
-        nv[2] = 1;
-        nn = 1.0;
-      }
-      if (raw) {
-        normals[3 * (size_t)i] = nv[0];
-        normals[3 * (size_t)i + 1] = nv[1];
-        normals[3 * (size_t)i + 2] = nv[2];
-        continue;
-      }
-      /* NormalizeNormals */
-      nv[0] /= nn;
-      nv[1] /= nn;
-      nv[2] /= nn;
-      if (isnan(nv[0])) {
-        nv[0] = 0;
-        nv[1] = 0;
-        nv[2] = 1;
-      }
-      /* OrientNormalsTowardsCameraLocation(camera = 0): reference = -p */
-      double ref[3] = {-p[0], -p[1], -p[2]};
-      if (dot3(nv, nv) == 0.0) {
-        double rn = sqrt(dot3(ref, ref));
-        if (rn == 0.0) {
-          nv[0] = 0;
-          nv[1] = 0;
-          nv[2] = 1;
-        } else {
-          nv[0] = ref[0] / rn;
-          nv[1] = ref[1] / rn;
-          nv[2] = ref[2] / rn;
-        }
-      } else if (dot3(nv, ref) < 0.0) {
-        nv[0] = -nv[0];
-        nv[1] = -nv[1];
-        nv[2] = -nv[2];
-      }
-      normals[3 * (size_t)i] = nv[0];
-      normals[3 * (size_t)i + 1] = nv[1];
-      normals[3 * (size_t)i + 2] = nv[2];
+      int32_t* li = idx + (size_t)i * stride;
+      cnt[i] = radius > 0.0 ? orc_kdtree_search_hybrid(t, p, radius, max_nn, li, d2) : orc_kdtree_search_knn(t, p, max_nn, li, d2);
     }
-    free(idx);
     free(d2);
   }
+  orc_normals_from_neighbours(pts, n, idx, cnt, stride, raw, normals);
+  free(idx);
+  free(cnt);
   orc_kdtree_free(t);
 }
 

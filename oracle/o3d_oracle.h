@@ -134,6 +134,9 @@ void orc_covariance_from_normal(const double nrm[3], double epsilon, double cov[
 /* A.5 EstimateNormals(Hybrid(radius,max_nn), fast) + NormalizeNormals + OrientNormalsTowardsCameraLocation(0)
  * (call site open3d_slam/src/CloudRegistration.cpp:49-56).  normals out: 3n */
 void orc_estimate_normals(const double* pts, size_t n, double radius, int max_nn, double* normals);
+/* the same after the search, from explicit ordered neighbour lists: point i has cnt[i] neighbours idx[i * stride ...]; raw != 0 stops
+ * after ComputeNormal (no normalisation, no orientation) */
+void orc_normals_from_neighbours(const double* pts, size_t n, const int32_t* idx, const int32_t* cnt, size_t stride, int raw, double* out);
 void orc_fast_eigen3x3_min_evec(const double cov[9], double out[3]);
 /* portable restatements of std::acos on [-1,1] and std::cos on [0,pi] used by it (see o3d_oracle.c) */
 double orc_acos(double x);

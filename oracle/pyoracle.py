@@ -94,6 +94,8 @@ def lib():
         L.orc_estimate_normals.argtypes = [_dp, C.c_size_t, C.c_double, C.c_int, _dp]
         L.orc_estimate_normals_ex.argtypes = [_dp, C.c_size_t, C.c_double, C.c_int, C.c_int, _dp]
         L.orc_estimate_normals_ex.restype = None
+        L.orc_normals_from_neighbours.argtypes = [_dp, C.c_size_t, _ip, _ip, C.c_size_t, C.c_int, _dp]
+        L.orc_normals_from_neighbours.restype = None
         L.orc_fast_eigen3x3_min_evec.argtypes = [_dp, _dp]
         L.orc_acos.restype = C.c_double
         L.orc_acos.argtypes = [C.c_double]
@@ -377,6 +379,17 @@ def estimate_normals_knn_raw(pts, max_nn=20):
     pts, pp = _d(pts)
     out = np.empty_like(pts)
     lib().orc_estimate_normals_ex(pp, len(pts), 0.0, max_nn, 1, out.ctypes.data_as(_dp))
+    return out
+
+
+def normals_from_neighbours(pts, idx, cnt, raw=False):
+    """the oracle's normals from explicit neighbour lists: row i of idx (n, stride) holds point i's cnt[i] neighbours in summation order"""
+    pts, pp = _d(pts)
+    idx = np.ascontiguousarray(idx, np.int32).reshape(len(pts), -1)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    assert len(cnt) == len(pts) and (len(pts) == 0 or (cnt.min() >= 0 and cnt.max() <= idx.shape[1]))
+    out = np.empty_like(pts)
+    lib().orc_normals_from_neighbours(pp, len(pts), idx.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip), idx.shape[1], int(raw), out.ctypes.data_as(_dp))
     return out
 
 

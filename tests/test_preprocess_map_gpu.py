@@ -156,7 +156,8 @@ def test_estimate_normals_f32_storage_and_repeatability(backend_f32, oracle, sca
     """f32 storage: distances are f32, so the neighbour set may differ from the f64 oracle's where two candidates tie within f32
     rounding; where the data define the direction it agrees to 1e-5.  And the result is a function of the cloud alone: it repeats
     bit for bit when the device pool has been disturbed in between (the index build's atomic scatter then orders the points of a
-    cell differently -- which is what made the round-1 kernel irreproducible)."""
+    cell differently -- which is what made the round-1 kernel irreproducible).
+    (Against the f64 oracle this can only be statistical; tests/test_normals_exact_gpu.py holds every f32-storage normal bit for bit.)"""
     import hashlib
 
     pts = oracle.voxel_down_sample(scan, 0.1)[::3]  # thinned: keeps the python eig-gap loop short
