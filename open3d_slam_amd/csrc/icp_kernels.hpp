@@ -486,21 +486,41 @@ __device__ __forceinline__ QueryCell locate(const GridDev& g, double qx, double 
   return c;
 }
 
-// distance (cell units) from the query to the slab of cells at offset d along one axis; u = position inside the own cell
-__device__ __forceinline__ float slab_dist(int d, float u) { return d == 0 ? 0.0f : (d < 0 ? u + (float)(-d - 1) : (1.0f - u) + (float)(d - 1)); }
+// distance (cell units) from the query to the slab of cells at offset d along one axis; u = position inside the own cell.  The three
+// cases (0 for the own slab, u + (-d - 1) below it, (1 - u) + (d - 1) above it) are the larger of d - u and (u - 1) - d where that is
+// positive: one conversion, two subtractions and a three-way maximum, no comparison of d
+__device__ __forceinline__ float slab_dist(int d, float u) {
+  const float fd = (float)d;
+  return fmaxf(fmaxf(fd - u, (u - 1.0f) - fd), 0.0f);
+}
 
 // x-extent [xa, xb] (cell offsets relative to the own cell) of the ball of squared radius b2 (cell units, already
-// inflated) at a row whose squared distance is rowd2; returns false if the row is out of reach
+// inflated) at a row whose squared distance is rowd2; returns false if the row is out of reach.
+// The extent only has to be a SUPERSET of the cells the ball reaches (a cell it adds holds points beyond the bound + m, which can
+// neither win nor be listed: the argument of the replica's x-only trim), so the root is the hardware's v_sqrt_f32 (error <= 1 ulp,
+// 2^-23 relative) and not the correctly rounded sqrtf, which costs about twenty instructions more per row.  With B^2 the exact squared
+// bound, D^2 <= B^2 the exact squared distance of a row in reach and W^2 = B^2 - D^2:  b2 >= B^2 (1 + 1e-4) (bound_cells2), rowd2 <=
+// D^2 (1 + 3e-7) and the subtraction rounds by at most 2^-24 b2, so  w2 >= W^2 + (1e-4 - 4e-7) B^2 >= W^2 (1 + 9.9e-5)  and
+//     hw_sqrt(w2) >= sqrt(w2) (1 - 2^-23) >= W (1 + 4.9e-5) (1 - 1.2e-7) > W
+// at any size of the bound; the additive 1e-4 cells and the rest of the relative headroom stand above the rounding of ux -+ w
+// (2^-24 w).  A denormal w2 may come back as 0: its root is below 1e-19 cells.
+// A row out of reach has w2 < 0 and a NaN for w: fmaxf / fminf return their other operand, the clamp, and only then does the value
+// become an int.  That holds under IEEE semantics only -- this file must not be built with -ffinite-math-only or -ffast-math.
 __device__ __forceinline__ bool row_extent(float b2, float rowd2, float ux, int* xa, int* xb) {
   const float w2 = b2 - rowd2;
-  if (!(w2 >= 0.0f)) return false;
-  const float w = sqrtf(w2) + 1e-4f;
+  const float w = __builtin_amdgcn_sqrtf(w2) + 1e-4f;  // (NaN for a row out of reach: the clamps below drop it, the caller drops the row)
   // clamped only so that the int conversion is safe, at a bound no grid reaches (an axis has at most 2^27 cells): the search radius in
   // cells is unbounded (an index built with an explicit cell keeps it for any r), and every caller clamps to its own block, to the grid
   // and to K itself.  |own cell| <= 1e9 (locate), so own cell + offset still fits an int
   *xa = (int)floorf(fmaxf(ux - w, -1.0e9f));
   *xb = (int)floorf(fminf(ux + w, 1.0e9f));
-  return true;
+  return w2 >= 0.0f;
+}
+
+// cell_start entry x (0 <= x <= nx) of the row that starts at rowp: the row's base is the one 64-bit address, the entry a 32-bit byte
+// offset added to it (an axis has at most 2^27 cells)
+__device__ __forceinline__ int row_entry(const int* __restrict__ rowp, int x) {
+  return *(const int*)((const char*)rowp + ((unsigned)x << 2));
 }
 
 // (d + m)^2 for a squared distance d2 and a margin m (metres); m = 0 leaves d2 as it is
@@ -519,6 +539,10 @@ __device__ __forceinline__ float bound_cells2(R d2, R m, const GridDev& g) {
   const float ic = (float)g.inv_cell;
   return widen2(d2, m) * ic * ic * (1.0f + 1e-4f) + 1e-6f;
 }
+
+// r / 3 and r / 5 of a lane's row number in the 3x3 and the 5x5 cross-section (0 <= r < 32) as a multiply and a shift
+__device__ __forceinline__ int div3_row(int r) { return (r * 11) >> 5; }
+__device__ __forceinline__ int div5_row(int r) { return (r * 13) >> 6; }
 
 // All G lanes of a group call this with the same query and the same starting bound `best` (any eligible target point, or {r^2, -1,
 // -1}); every lane returns the same winner.  m / col: the candidate-set margin and list (m = 0, col.tau2 = 0: off); *kdone = the
@@ -569,12 +593,12 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
     bool rv[kOwn];
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) {
-      const int r = gl + k * G;
-      const int y = c.iy + (r % 3) - 1, z = c.iz + (r / 3) - 1;
+      const int r = gl + k * G, rz = div3_row(r);
+      const int y = c.iy + (r - 3 * rz) - 1, z = c.iz + rz - 1;
       rv[k] = r < 9 && xlo <= xhi && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz;
-      const int row = rv[k] ? (z * g.ny + y) * g.sx : 0;
+      const int* __restrict__ rowp = cs + (rv[k] ? (z * g.ny + y) * g.sx : 0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[k][j] = rv[k] ? cs[row + min(xlo + j, xhi + 1)] : 0;
+      for (int j = 0; j < 4; ++j) v[k][j] = rv[k] ? row_entry(rowp, min(xlo + j, xhi + 1)) : 0;
     }
     // ---- stage 1: the 3x3x3 block, trimmed by the bound
     {
@@ -583,8 +607,8 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
       int cnt = 0;
 #pragma unroll
       for (int k = 0; k < kOwn; ++k) {
-        const int r = gl + k * G;
-        const float ddy = slab_dist((r % 3) - 1, c.uy), ddz = slab_dist((r / 3) - 1, c.uz);
+        const int r = gl + k * G, rz = div3_row(r);
+        const float ddy = slab_dist((r - 3 * rz) - 1, c.uy), ddz = slab_dist(rz - 1, c.uz);
         int xa, xb;
         ss[k] = ee[k] = 0;
         if (rv[k] && row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb)) {
@@ -623,33 +647,29 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
 #pragma unroll 1
     for (int r0 = 0; r0 < 25; r0 += kHalf) {
       const float b2 = bound_cells2(best.d2, m, g);
+      const int own = min(kHalf, 25 - r0);  // rows of this half
       int s2[2 * kOwn2], e2[2 * kOwn2];
 #pragma unroll
       for (int k = 0; k < kOwn2; ++k) {
-        const int rl = gl + k * G, r = r0 + rl;
-        const int dy = (r % 5) - 2, dz = (r / 5) - 2;
+        const int rl = gl + k * G, r = r0 + rl, rz = div5_row(r);
+        const int dy = (r - 5 * rz) - 2, dz = rz - 2;
         const int y = c.iy + dy, z = c.iz + dz;
-        s2[2 * k] = e2[2 * k] = s2[2 * k + 1] = e2[2 * k + 1] = 0;
-        if (rl < kHalf && r < 25 && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz) {
-          const float ddy = slab_dist(dy, c.uy), ddz = slab_dist(dz, c.uz);
-          int xa, xb;
-          if (row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb)) {
-            xa = max(max(c.ix + xa, c.ix - 2), 0);
-            xb = min(min(c.ix + xb, c.ix + 2), g.nx - 1);
-            const bool inner = abs(dy) <= 1 && abs(dz) <= 1;  // cells ix-1..ix+1 of these rows were stage 1
-            const int row = (z * g.ny + y) * g.sx;
-            const int xb1 = inner ? min(xb, c.ix - 2) : xb;
-            if (xa <= xb1) {
-              s2[2 * k] = cs[row + xa];
-              e2[2 * k] = cs[row + xb1 + 1];
-            }
-            const int xa2 = max(xa, c.ix + 2);
-            if (inner && xa2 <= xb) {
-              s2[2 * k + 1] = cs[row + xa2];
-              e2[2 * k + 1] = cs[row + xb + 1];
-            }
-          }
-        }
+        // branch-free: a row out of the grid or out of reach, and an empty half, read entry 0 of row 0 twice (start == end: no segment),
+        // so that all the loads of a lane go out back to back with nothing conditional between them
+        const float ddy = slab_dist(dy, c.uy), ddz = slab_dist(dz, c.uz);
+        int xa, xb;
+        const bool reach = row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb) && rl < own && (unsigned)y < (unsigned)g.ny &&
+                           (unsigned)z < (unsigned)g.nz;
+        xa = max(c.ix + max(xa, -2), 0);  // clamped to the block and to the grid once per row
+        xb = min(c.ix + min(xb, 2), g.nx - 1);
+        const bool inner = abs(dy) <= 1 && abs(dz) <= 1;  // cells ix-1..ix+1 of these rows were stage 1
+        const int* __restrict__ rowp = cs + (reach ? (z * g.ny + y) * g.sx : 0);
+        const int xb1 = inner ? min(xb, c.ix - 2) : xb, xa2 = max(xa, c.ix + 2);
+        const bool h0 = reach && xa <= xb1, h1 = reach && inner && xa2 <= xb;
+        s2[2 * k] = row_entry(rowp, h0 ? xa : 0);
+        e2[2 * k] = row_entry(rowp, h0 ? xb1 + 1 : 0);
+        s2[2 * k + 1] = row_entry(rowp, h1 ? xa2 : 0);
+        e2[2 * k + 1] = row_entry(rowp, h1 ? xb + 1 : 0);
       }
       int cnt = 0;
 #pragma unroll
@@ -675,53 +695,58 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
 }
 
 // Stage 3 -- queries whose nearest neighbour (if any) is farther than two cells: all 64 lanes of the wavefront serve ONE
-// query, still on the fine grid.  The half-rows of the (2K+1)^2 cross-section (K = ceil(r / cell)) that intersect the ball
-// of the current bound and were not scanned by stages 0-2 are dealt to the lanes (one cell_start pair each), compacted
-// through the wavefront's LDS list (mbcnt rank), and the lanes regroup so that every listed half-row gets
-// 64 / pow2(#rows) (>= 4) lanes striding over it.
+// query, still on the fine grid.  The rows of the (2K+1)^2 cross-section (K = ceil(r / cell)) are dealt to the lanes whole, rows
+// `lane` and `lane + 64` of every round of 128 (one round for K <= 5).  A row's geometry -- in the grid or not, its distance, the
+// x-extent of the ball of the current bound, clamped to the block and the grid, the row's base in cell_start -- is formed once; its
+// two halves (left and right of the own cell, or of the five cells stages 0-2 scanned in an inner row) differ in one clamp and one
+// cell_start pair each, all fetched in one batch.  The non-empty half-rows are compacted through the wavefront's LDS list (mbcnt
+// rank), and the lanes regroup so that every listed half-row gets 64 / pow2(#rows) (>= 4) lanes striding over it.
+//
+// Which rows a lane owns depends on the lane and on K alone, and costs no division by the run-time side 2K+1 per query: for a
+// cross-section of at most 128 rows (K <= 5) the row number rr < 128 splits as rr / side = (rr * far_side_recip(K)) >> 16, exactly
+// (the reciprocal is rounded up by less than 1, so the product overshoots rr * 65536 / side by less than 128, and the fraction of
+// rr / side stands at least 65536 / side >= 5957 below the next integer).  The reciprocal is wave-uniform and formed once per
+// workgroup and target, outside the loop that pops the far queries; a row pair packed per lane in a register of its own was tried
+// and spilt in the generalized multi-target kernels.  Only a larger cross-section divides, per round.
+__device__ __forceinline__ int far_side_recip(int K) { return (65536 + 2 * K) / (2 * K + 1); }
+
 template <typename P4, bool kCrop, bool kCollect>
 __device__ __forceinline__ void nn_search_wave_far(const GridDev& g, const P4* __restrict__ tp, typename Scalar<P4>::type qx,
                                                    typename Scalar<P4>::type qy, typename Scalar<P4>::type qz, int K,
-                                                   const CropDev& crop, NNBest<P4>& best, int lane, int2* s_list /* kFarList entries */,
-                                                   typename Scalar<P4>::type m, const Collect<typename Scalar<P4>::type>& col) {
+                                                   const CropDev& crop, NNBest<P4>& best, int lane, int side_recip /* far_side_recip(K) */,
+                                                   int2* s_list /* kFarList entries */, typename Scalar<P4>::type m,
+                                                   const Collect<typename Scalar<P4>::type>& col) {
   constexpr int kdone = 2;  // cells within offset 2 were scanned by the group stages
-  constexpr int kPer = 4;   // half-rows per lane and round: all their bounds are fetched in one batch
+  constexpr int kPer = 4;   // half-rows per lane and round (two rows): all their bounds are fetched in one batch
   const QueryCell c = locate(g, (double)qx, (double)qy, (double)qz);
   const float b2 = bound_cells2(best.d2, m, g);
   const int* __restrict__ cs = g.cell_start;
-  const int side = 2 * K + 1, entries = 2 * side * side;
+  const int side = 2 * K + 1, rows = side * side;
   NNBest<P4> mine = best;
-  for (int base = 0; base < entries; base += 64 * kPer) {  // wave-uniform; one round for K <= 5
+  for (int base = 0; base < rows; base += 128) {  // wave-uniform; one round for K <= 5
     int s_own[kPer], e_own[kPer];
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const int e = base + u * 64 + lane;
-      s_own[u] = e_own[u] = 0;
-      if (e < entries) {
-        const int half = e & 1, rr = e >> 1;
-        const int dy = rr % side - K, dz = rr / side - K;
-        const int y = c.iy + dy, z = c.iz + dz;
-        if ((unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz) {
-          const float ddy = slab_dist(dy, c.uy), ddz = slab_dist(dz, c.uz);
-          int xa, xb;
-          if (row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb)) {
-            xa = max(c.ix + xa, c.ix - K);
-            xb = min(c.ix + xb, c.ix + K);
-            const bool inner = abs(dy) <= kdone && abs(dz) <= kdone;
-            if (half == 0)
-              xb = min(xb, inner ? c.ix - kdone - 1 : c.ix);
-            else
-              xa = max(xa, inner ? c.ix + kdone + 1 : c.ix + 1);
-            xa = max(xa, 0);
-            xb = min(xb, g.nx - 1);
-            if (xa <= xb) {
-              const int row = (z * g.ny + y) * g.sx;
-              s_own[u] = cs[row + xa];
-              e_own[u] = cs[row + xb + 1];
-            }
-          }
-        }
-      }
+    for (int u = 0; u < kPer / 2; ++u) {
+      const int rr = base + 64 * u + lane;
+      const int rz = rows <= 128 ? (rr * side_recip) >> 16 : rr / side;  // (wave-uniform choice)
+      const int dy = rr - rz * side - K, dz = rz - K;
+      const bool have = rr < rows;
+      const int y = c.iy + dy, z = c.iz + dz;
+      // branch-free, as in stage 2: whatever is not to be scanned reads entry 0 of row 0 twice (start == end)
+      const float ddy = slab_dist(dy, c.uy), ddz = slab_dist(dz, c.uz);
+      int xa, xb;
+      const bool reach = row_extent(b2, ddy * ddy + ddz * ddz, c.ux, &xa, &xb) && have && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz;
+      xa = max(c.ix + max(xa, -K), 0);  // clamped to the block and to the grid once per row
+      xb = min(c.ix + min(xb, K), g.nx - 1);
+      const bool inner = abs(dy) <= kdone && abs(dz) <= kdone;
+      const int* __restrict__ rowp = cs + (reach ? (z * g.ny + y) * g.sx : 0);
+      const int xb0 = min(xb, inner ? c.ix - kdone - 1 : c.ix);      // the left half ends here,
+      const int xa1 = max(xa, inner ? c.ix + kdone + 1 : c.ix + 1);  // the right half starts here
+      const bool h0 = reach && xa <= xb0, h1 = reach && xa1 <= xb;
+      s_own[2 * u] = row_entry(rowp, h0 ? xa : 0);
+      e_own[2 * u] = row_entry(rowp, h0 ? xb0 + 1 : 0);
+      s_own[2 * u + 1] = row_entry(rowp, h1 ? xa1 : 0);
+      e_own[2 * u + 1] = row_entry(rowp, h1 ? xb + 1 : 0);
     }
     // compact the non-empty half-rows of all kPer slices into the wavefront's list
     int total = 0;
@@ -1221,6 +1246,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
       if (n_far > 0) {  // workgroup-uniform
         const int lane = threadIdx.x & 63;
         int2* list = s_seg + (threadIdx.x >> 6) * (64 / kGroup) * kSegMax;
+        const int side_recip = far_side_recip(a.kmax);
         for (int k = wave_pop(&s_far[1], lane); k < n_far; k = wave_pop(&s_far[1], lane)) {  // k is scalar: a uniform loop
           const int slot = s_far[2 + k];
           FarItem<P4>* it = (FarItem<P4>*)(s_rec_flat + slot * kStride);
@@ -1232,7 +1258,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
           col.tau2 = it->tau2;
           col.cnt = sets ? s_set + slot * (1 + kSetCap) : nullptr;
           col.list = col.cnt + 1;
-          if (a.debug != 32) nn_search_wave_far<P4, kCrop, kCollect>(a.grid, tp, it->x, it->y, it->z, a.kmax, a.crop, bq, lane, list, it->m, col);
+          if (a.debug != 32) nn_search_wave_far<P4, kCrop, kCollect>(a.grid, tp, it->x, it->y, it->z, a.kmax, a.crop, bq, lane, side_recip, list, it->m, col);
           // every lane holds the same winner and stores it (same address, same value): no lane-0 branch inside this loop --
           // with one, the structurised code re-ran the body for the other lanes forever (seen on ROCm 7.2)
           it->d2 = bq.d2;

@@ -85,6 +85,7 @@ __device__ __forceinline__ NNBest<P4> list_search_target(const GridDev& grid, co
   if (n_far > 0) {  // workgroup-uniform
     const int lane = threadIdx.x & 63;
     int2* list = s_seg + (threadIdx.x >> 6) * (64 / kGroup) * kSegMax;
+    const int side_recip = far_side_recip(kmax);
     for (int f = wave_pop(&s_far[1], lane); f < n_far; f = wave_pop(&s_far[1], lane)) {  // f is scalar: a uniform loop
       const int slot = s_far[2 + f];
       FarItem<P4>* it = (FarItem<P4>*)(s_rec + slot * kStride);
@@ -96,7 +97,7 @@ __device__ __forceinline__ NNBest<P4> list_search_target(const GridDev& grid, co
       col.tau2 = (R)0;
       col.cnt = nullptr;
       col.list = nullptr;
-      nn_search_wave_far<P4, kCrop, false>(grid, tp, it->x, it->y, it->z, kmax, crop, bq, lane, list, (R)0, col);
+      nn_search_wave_far<P4, kCrop, false>(grid, tp, it->x, it->y, it->z, kmax, crop, bq, lane, side_recip, list, (R)0, col);
       // every lane holds the same winner and stores it (same address, same value): no lane-0 branch inside this loop --
       // with one, the structurised code re-ran the body for the other lanes forever (seen on ROCm 7.2)
       it->d2 = bq.d2;
