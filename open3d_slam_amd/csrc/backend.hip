@@ -162,6 +162,7 @@ constexpr size_t kMaxCells = (size_t)1 << 27;  // 512 MiB of cell_start at most
 // for the 1 M-point map with f32 storage (built: configs[1] +8 %); 1.44 GB for an 8 M-point map, whose stage-1 gathers then come from HBM
 // and lost 3 % (not built), 324 MB with f64 storage (no gain measured: not built).
 constexpr size_t kReplicaMaxBytes = (size_t)256 << 20;
+static_assert(kReplicaMaxBytes <= kScanMaxBytes, "scan_strided addresses a searched array by 32-bit byte offsets");
 
 }  // namespace
 
@@ -1030,6 +1031,8 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
                  void** out_snrm, CloudRec* box /* in: a known box, if has_box; out: the box used */,
                  const int* n_dev = nullptr /* n is an upper bound, the exact count is here (a cloud whose size the host has not seen: it then brings its box) */) {
   if (n == 0) return fail(h, O3DS_ERR_EMPTY, "build_index: empty cloud");
+  if (n > kScanMaxBytes / sizeof(P4))
+    return fail(h, O3DS_ERR_CAPACITY, "build_index: the cell-sorted points exceed 2^32 bytes (2^28 points in f32 storage, 2^27 in f64): the search addresses them by 32-bit byte offsets");
   double mn[3], mx[3];
   int rc = O3DS_OK;
   static const bool no_box_cache = ab_getenv("O3DS_NO_BOX_CACHE") != nullptr;  // debugging aid: always reduce
@@ -3919,6 +3922,7 @@ int pm_enter_t(o3ds_handle h, CloudRec& c, double voxel, double max_corr_hint, s
   c.cell_start = cs;
   const size_t pool = 6 * n + 16 * scan_upper + ((size_t)1 << 22);
   if (pool >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_OOM, "persistent map: index pool beyond 2^31 positions");
+  if (pool > kScanMaxBytes / sizeof(P4)) return fail(h, O3DS_ERR_CAPACITY, "persistent map: index pool beyond 2^32 bytes (the search addresses it by 32-bit byte offsets)");
   HIP_TRY(dev_alloc(h, &c.spts, sizeof(P4) * pool));
   if (c.nrm) HIP_TRY(dev_alloc(h, &c.snrm, sizeof(P4) * pool));
   PM_ALLOC(d.row_cap, sizeof(int) * pm->rows);

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   NNBest<P4> best;
   best.d2 = (R)a.r2max;
   best.pos = -1;
-  best.idx = -1;
+  best.idx = NNBest<P4>::kNoIdx;
   if (live && use_cache) {
     const int prev = a.nn_cache[a.first + i];
     if (prev >= 0 && prev < a.n_tgt) consider<P4, kCrop>(tp[prev], prev, true, q.qx, q.qy, q.qz, crop, best);  // never trust the cache with an address

@@ -310,8 +310,26 @@ template <typename P4>
 struct NNBest {
   typename Scalar<P4>::type d2;
   int pos;  // position in the cell-sorted target arrays; -1 = none
-  typename Scalar<P4>::index idx;
+  typename Scalar<P4>::index idx;  // original index of the point at pos; kNoIdx with the empty bound {r^2, -1, kNoIdx}
+  // the index of "no point yet": below it there is no index, so a candidate at exactly d2 == r^2 loses the tie and stays excluded.  With
+  // f64 storage the comparison is signed (-1); with f32 storage it is unsigned (nn_before), where the smallest index is 0
+  static constexpr typename Scalar<P4>::index kNoIdx = sizeof(typename Scalar<P4>::type) == 8 ? -1 : 0;
 };
+
+// "(d2, idx) comes before (bd2, bidx)": nearer, or equally near with the smaller original index.
+// f32 storage: ONE unsigned 64-bit compare of (float bits of d2) << 32 | idx.  A squared distance is a non-negative float (squares and
+// fused steps from +0 never give -0), whose bit pattern orders as its value does, +inf above every finite value and the NaNs of either sign
+// above +inf -- a NaN distance comes before nothing, as under the float compare; an original index is below 2^31, so the unsigned order of
+// the low word is the signed one.  The two words sit in two registers already: no instruction packs them.  f64 storage (f64 distances,
+// 64-bit indices) keeps the three compares.
+template <typename R, typename I>
+__device__ __forceinline__ bool nn_before(R d2, I idx, R bd2, I bidx) {
+  return (d2 < bd2) | ((d2 == bd2) & (idx < bidx));
+}
+__device__ __forceinline__ unsigned long long nn_key(float d2, int32_t idx) {
+  return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)idx;
+}
+__device__ __forceinline__ bool nn_before(float d2, int32_t idx, float bd2, int32_t bidx) { return nn_key(d2, idx) < nn_key(bd2, bidx); }
 
 // squared candidate distance: with f32 storage two fused steps (this is the innermost loop of the search); with f64 storage the three
 // products and two sums the reference's k-d tree forms (nanoflann's L2 adaptor, built without FMA)
@@ -327,7 +345,7 @@ __device__ __forceinline__ typename Scalar<P4>::type consider(const P4& t, int p
   const R dx = t.x - qx, dy = t.y - qy, dz = t.z - qz;
   const R d2 = dist2(dx, dy, dz);
   // strict d2 < best (initially r^2); ties broken towards the smaller original index
-  bool better = valid & ((d2 < best.d2) | ((d2 == best.d2) & (t.i < best.idx)));
+  bool better = valid & nn_before(d2, t.i, best.d2, best.idx);
   if (kCrop) {
     if (better) better = crop_contains(crop, (double)t.x, (double)t.y, (double)t.z);
   }
@@ -349,6 +367,7 @@ __device__ __forceinline__ typename Scalar<P4>::type consider(const P4& t, int p
 // needs no search at all -- the listed points and their normals are fetched BEFORE the pose is known, while the previous pass's
 // 6x6 system is being solved (icp_pass_body, "verified match").  A list holds at most kSetCap points (one per lane of the query's
 // group); a longer one, or a margin of zero, means "no set": that query searches again next pass, from the bound it has.
+constexpr size_t kScanMaxBytes = (size_t)1 << 32;  // the largest array scan_strided can be pointed at (32-bit byte offsets): held where an index is built
 constexpr int kSetCap = 4;
 template <typename R>
 struct Collect {
@@ -373,6 +392,9 @@ __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, i
                                              NNBest<P4>& best, const Collect<typename Scalar<P4>::type>& col) {
   using R = typename Scalar<P4>::type;
   constexpr int kInFlight = sizeof(R) == 8 ? 2 : 4;
+  // the array's base is wave-uniform (scalar registers) and a candidate's address a 32-bit byte offset added to it by the load itself:
+  // a searched array holds at most kScanMaxBytes
+  const char* __restrict__ tb = (const char*)tp;
   for (int p = s + lane; p < e; p += kInFlight * stride) {
     int pk[kInFlight];
     bool vk[kInFlight];
@@ -382,8 +404,14 @@ __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, i
     for (int k = 0; k < kInFlight; ++k) {
       pk[k] = p + k * stride;
       vk[k] = pk[k] < e;
-      tk[k] = tp[vk[k] ? pk[k] : p];  // clamped, not predicated: branches around the loads measured slower
+      // clamped, not predicated: branches around the loads measured slower.  (The clamp selects the index and the offset is its shift:
+      // selecting among offsets o, o + step, ... keeps 2 * step and 3 * step in registers across the whole search)
+      tk[k] = *(const P4*)(tb + (unsigned)(vk[k] ? pk[k] : p) * (unsigned)sizeof(P4));
     }
+    // f64 storage: every load of the batch is issued before the first is consumed -- the scheduler otherwise put the first candidate's
+    // subtraction (and the wait for its load) in front of the second candidate's loads: two dependent memory rounds per iteration.
+    // (The f32 loop issues its four loads first on its own, and measured half a percent slower with the barrier than without)
+    if (sizeof(R) == 8) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < kInFlight; ++k) dk[k] = consider<P4, kCrop>(tk[k], pk[k], vk[k], qx, qy, qz, crop, best);
     if (kCollect) {
@@ -408,7 +436,7 @@ __device__ __forceinline__ void lanes_min(NNBest<P4>& b) {
     const auto od2 = __shfl_xor(b.d2, m, W);
     const int opos = __shfl_xor(b.pos, m, W);
     const auto oidx = __shfl_xor(b.idx, m, W);
-    const bool take = (opos != -1) & ((od2 < b.d2) | ((od2 == b.d2) & (oidx < b.idx)));
+    const bool take = (opos != -1) & nn_before(od2, oidx, b.d2, b.idx);
     b.d2 = take ? od2 : b.d2;
     b.pos = take ? opos : b.pos;
     b.idx = take ? oidx : b.idx;
@@ -544,8 +572,8 @@ __device__ __forceinline__ float bound_cells2(R d2, R m, const GridDev& g) {
 __device__ __forceinline__ int div3_row(int r) { return (r * 11) >> 5; }
 __device__ __forceinline__ int div5_row(int r) { return (r * 13) >> 6; }
 
-// All G lanes of a group call this with the same query and the same starting bound `best` (any eligible target point, or {r^2, -1,
-// -1}); every lane returns the same winner.  m / col: the candidate-set margin and list (m = 0, col.tau2 = 0: off); *kdone = the
+// All G lanes of a group call this with the same query and the same starting bound `best` (any eligible target point, or the empty
+// bound {r^2, -1, NNBest::kNoIdx}); every lane returns the same winner.  m / col: the candidate-set margin and list (m = 0, col.tau2 = 0: off); *kdone = the
 // block radius (cells) the search covered.
 template <typename P4, bool kCrop, int G, bool kCollect>
 __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4* __restrict__ tp, typename Scalar<P4>::type qx,
@@ -1135,7 +1163,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
     double px = 0, py = 0, pz = 0;
     NNBest<P4> nn;
     nn.pos = -1;
-    nn.idx = -1;
+    nn.idx = -1;  // (a result, not a bound: never compared -- the searches start from `best` below)
     nn.d2 = (R)0;
     bool unresolved = false;
     bool verified = false;   // the match was proven inside the prefetched candidate set: the winner's lane holds point and normal
@@ -1167,7 +1195,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
         NNBest<P4> best;
         best.d2 = (R)a.r2max;
         best.pos = -1;
-        best.idx = -1;
+        best.idx = NNBest<P4>::kNoIdx;
         consider<P4, kCrop>(qp.tprev, qp.prev, qp.prev >= 0, qx, qy, qz, a.crop, best);
         if (sets_in) {
           lanes_min<P4, kGroup>(best);

@@ -155,7 +155,11 @@ __device__ __forceinline__ void list_sum_row(const double* s_rec, double (*s_red
 #pragma unroll
     for (int s = 0; s < kSlices; ++s) v += s_red[s][threadIdx.x];
     if (threadIdx.x >= 30) v = 0.0;
-    row[threadIdx.x] = v;
+    // (the store's address is formed HERE: left to itself the compiler forms row + threadIdx.x in the prologue and keeps the pair of
+    // registers across the whole search, which the crop + generalized multi-target kernel does not have -- it spilt them)
+    int tx = threadIdx.x;
+    asm volatile("" : "+v"(tx));
+    row[tx] = v;
   }
 }
 

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   NNBest<P4> cur;
   cur.d2 = (R)a.r2max;
   cur.pos = -1;
-  cur.idx = -1;
+  cur.idx = NNBest<P4>::kNoIdx;
   int cur_slot = -1;
   if (!joint && live && use_cache) {
     const int c = ma.cache[a.first + i];
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
     NNBest<P4> best;
     best.d2 = (R)a.r2max;
     best.pos = -1;
-    best.idx = -1;
+    best.idx = NNBest<P4>::kNoIdx;
     if (joint) {
       if (live && use_cache) {
         const int prev = ma.cache[(size_t)k * ma.cache_stride + a.first + i];
