@@ -65,6 +65,8 @@ struct CloudRec {
   int* rstart = nullptr;
   int* rpos = nullptr;
   int index_regs = 0;       // registrations against this index so far (maybe_build_replica)
+  size_t spts_slack = 0;    // bytes allocated behind the last element of spts, and of rpts: the search's scan loop loads up to
+  size_t rpts_slack = 0;    // kScanSlackBytes beyond the end of a range (scan_strided) and is refused a target that has less
   // A box that is known to contain every point (not necessarily tight): set where a bounding box has been computed anyway
   // (VoxelDownSample, an index build) and carried to clouds derived from it (subsets, voxel means, rigid placements, unions), so
   // that the next index build of the per-scan pipeline does not pay a reduction kernel + read-back + host sync for it again.
@@ -162,6 +164,18 @@ constexpr size_t kMaxCells = (size_t)1 << 27;  // 512 MiB of cell_start at most
 // for the 1 M-point map with f32 storage (built: configs[1] +8 %); 1.44 GB for an 8 M-point map, whose stage-1 gathers then come from HBM
 // and lost 3 % (not built), 324 MB with f64 storage (no gain measured: not built).
 constexpr size_t kReplicaMaxBytes = (size_t)256 << 20;
+// How many elements of P4 a searched array may hold (build_grid_t, the persistent map's pool): kScanMaxBytes of them, i.e. 2^32 bytes less
+// the scan loop's slack.  A/B library: O3DS_SCAN_SPACE_BYTES=<b> stands in for the 2^32 (the slack still comes off it), so that a test
+// reaches the limit with a small cloud.
+template <typename P4>
+size_t scan_capacity() {
+  static_assert(kScanMaxBytes + kScanSlackBytes == (size_t)1 << 32, "capacity and slack share the 32-bit offset space");
+  const char* e = ab_getenv("O3DS_SCAN_SPACE_BYTES");
+  const size_t space = e ? (size_t)strtoull(e, nullptr, 10) : kScanMaxBytes + kScanSlackBytes;
+  return space > kScanSlackBytes ? (std::min(space, kScanMaxBytes + kScanSlackBytes) - kScanSlackBytes) / sizeof(P4) : 0;
+}
+// the slack an index array is allocated with; A/B library: O3DS_NO_SCAN_SLACK allocates as a caller unaware of the scan loop would
+inline size_t scan_slack_alloc() { return ab_getenv("O3DS_NO_SCAN_SLACK") ? 0 : kScanSlackBytes; }
 static_assert(kReplicaMaxBytes <= kScanMaxBytes, "scan_strided addresses a searched array by 32-bit byte offsets");
 
 }  // namespace
@@ -630,6 +644,7 @@ void free_index(o3ds_handle h, CloudRec& c) {
   c.spts = c.snrm = c.rpts = nullptr;
   c.rstart = c.rpos = nullptr;
   c.index_regs = 0;
+  c.spts_slack = c.rpts_slack = 0;
   c.has_index = false;
   c.index_byproduct = false;
 }
@@ -1028,11 +1043,12 @@ int bbox_of(o3ds_handle h, const P4* pts, size_t n, double mn[3], double mx[3], 
 // given) re-stored in cell order.  Output buffers are allocated here; the caller owns them.
 template <typename P4>
 int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double cell, GridDev* out_grid, int** out_cell_start, void** out_spts,
-                 void** out_snrm, CloudRec* box /* in: a known box, if has_box; out: the box used */,
+                 void** out_snrm, size_t* out_slack /* bytes allocated behind spts[n - 1] */,
+                 CloudRec* box /* in: a known box, if has_box; out: the box used */,
                  const int* n_dev = nullptr /* n is an upper bound, the exact count is here (a cloud whose size the host has not seen: it then brings its box) */) {
   if (n == 0) return fail(h, O3DS_ERR_EMPTY, "build_index: empty cloud");
-  if (n > kScanMaxBytes / sizeof(P4))
-    return fail(h, O3DS_ERR_CAPACITY, "build_index: the cell-sorted points exceed 2^32 bytes (2^28 points in f32 storage, 2^27 in f64): the search addresses them by 32-bit byte offsets");
+  if (n > scan_capacity<P4>())
+    return fail(h, O3DS_ERR_CAPACITY, "build_index: the cell-sorted points exceed 2^32 bytes less the scan loop's slack (the search addresses them by 32-bit byte offsets)");
   double mn[3], mx[3];
   int rc = O3DS_OK;
   static const bool no_box_cache = ab_getenv("O3DS_NO_BOX_CACHE") != nullptr;  // debugging aid: always reduce
@@ -1077,7 +1093,9 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
   counts = h->d_cells;
   TMP_ALLOC(cell_id, sizeof(int) * n);
   HIP_TRY(dev_alloc(h, (void**)&cell_start, sizeof(int) * (ncell + 1 + 4)));  // +4: the search reads rows as unaligned 16-B vectors
-  HIP_TRY(dev_alloc(h, (void**)&spts, sizeof(P4) * n));
+  // (the slack is never written and never looked at: scan_strided)
+  const size_t slack = scan_slack_alloc();
+  HIP_TRY(dev_alloc(h, (void**)&spts, sizeof(P4) * n + slack));
   if (nrm) HIP_TRY(dev_alloc(h, (void**)&snrm, sizeof(P4) * n));
   span_mark(h, kSpanIndexBuild);
   cell_count_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(pts, n, g, counts, cell_id, n_dev);
@@ -1092,6 +1110,7 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
   *out_grid = g;
   *out_cell_start = cell_start;
   *out_spts = spts;
+  *out_slack = slack;
   if (out_snrm) *out_snrm = snrm;
   return O3DS_OK;
 }
@@ -1103,7 +1122,7 @@ int build_index_t(o3ds_handle h, CloudRec& c, double cell) {
     const int rr = resolve_count(h, c, true);
     if (rr) return rr;
   }
-  int rc = build_grid_t<P4>(h, (const P4*)c.pts, (const P4*)c.nrm, c.n, cell, &c.grid, &c.cell_start, &c.spts, &c.snrm, &c,
+  int rc = build_grid_t<P4>(h, (const P4*)c.pts, (const P4*)c.nrm, c.n, cell, &c.grid, &c.cell_start, &c.spts, &c.snrm, &c.spts_slack, &c,
                             c.lazy_slot >= 0 ? cnt_word(h, c.lazy_slot) : nullptr);
   if (rc) return rc;
   c.has_index = true;
@@ -1128,7 +1147,7 @@ int build_replica_t(o3ds_handle h, CloudRec& c) {
   if (rcell > kMaxCells || 9 * n > (size_t)INT_MAX || 9 * n * (sizeof(P4) + sizeof(int)) + sizeof(int) * (rcell + 1) > kReplicaMaxBytes) return O3DS_OK;
   void* rpts = nullptr;
   int *rstart = nullptr, *rpos = nullptr;
-  if (dev_alloc(h, (void**)&rstart, sizeof(int) * (rcell + 1)) != hipSuccess || dev_alloc(h, &rpts, sizeof(P4) * 9 * n) != hipSuccess ||
+  if (dev_alloc(h, (void**)&rstart, sizeof(int) * (rcell + 1)) != hipSuccess || dev_alloc(h, &rpts, sizeof(P4) * 9 * n + scan_slack_alloc()) != hipSuccess ||
       dev_alloc(h, (void**)&rpos, sizeof(int) * 9 * n) != hipSuccess) {
     (void)hipGetLastError();
     if (rstart) dev_free(h, rstart);
@@ -1153,6 +1172,7 @@ int build_replica_t(o3ds_handle h, CloudRec& c) {
   HIP_TRY(hipGetLastError());
   h->cells_clean = true;
   c.rpts = rpts;
+  c.rpts_slack = scan_slack_alloc();
   c.rstart = rstart;
   c.rpos = rpos;
   c.grid.rpts = rpts;
@@ -1608,6 +1628,12 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
     rc = build_index(h, *tgt, params->max_correspondence_distance / index_cell_div());
     if (rc) return rc;
   }
+  rc = maybe_build_replica(h, *tgt);
+  if (rc) return rc;
+  // the scan loop loads candidates beyond the end of a range without looking at them (scan_strided): behind the last element of either
+  // array there must be memory of the same allocation.  Refused before anything of the handle is touched
+  if (tgt->spts_slack < kScanSlackBytes || (tgt->rpts && tgt->rpts_slack < kScanSlackBytes))
+    return fail(h, O3DS_ERR_INVALID_ARG, "icp: the target's index arrays end without the kScanSlackBytes the search's scan loop may load beyond a range");
   const size_t cap = (std::max<size_t>(src->n + src->n / 4, 1 << 16) + 7) & ~(size_t)7;
   bool fresh_cache = false;
   rc = handle_scratch(h, &h->d_nn_cache, &h->nn_cache_cap, src->n, cap, cap * sizeof(int), &fresh_cache);
@@ -1635,8 +1661,6 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   a.count = src->n;
   a.tpts = tgt->spts;
   a.tnrm = tgt->snrm;
-  rc = maybe_build_replica(h, *tgt);
-  if (rc) return rc;
   a.grid = tgt->grid;
   {  // A/B switch: O3DS_NN_REPLICA=0 searches the rows of cell_start although the index has a replica (read at every registration)
     const char* e = ab_getenv("O3DS_NN_REPLICA");
@@ -3176,6 +3200,7 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
   box_copy(c, tmp);  // the box an index build reduced is kept for the cloud
   free_index(h, c);  // the cloud's own index (if any) no longer matches its normals
   c.grid = tmp.grid, c.cell_start = tmp.cell_start, c.spts = tmp.spts, c.snrm = tmp.snrm;
+  c.spts_slack = tmp.spts_slack;
   c.has_index = true;
   c.index_byproduct = true;
   return O3DS_OK;
@@ -3922,8 +3947,13 @@ int pm_enter_t(o3ds_handle h, CloudRec& c, double voxel, double max_corr_hint, s
   c.cell_start = cs;
   const size_t pool = 6 * n + 16 * scan_upper + ((size_t)1 << 22);
   if (pool >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_OOM, "persistent map: index pool beyond 2^31 positions");
-  if (pool > kScanMaxBytes / sizeof(P4)) return fail(h, O3DS_ERR_CAPACITY, "persistent map: index pool beyond 2^32 bytes (the search addresses it by 32-bit byte offsets)");
-  HIP_TRY(dev_alloc(h, &c.spts, sizeof(P4) * pool));
+  if (pool > scan_capacity<P4>()) return fail(h, O3DS_ERR_CAPACITY, "persistent map: index pool beyond 2^32 bytes less the scan loop's slack (the search addresses it by 32-bit byte offsets)");
+  HIP_TRY(dev_alloc(h, &c.spts, sizeof(P4) * pool + scan_slack_alloc()));
+  c.spts_slack = scan_slack_alloc();
+  {  // no position of the pool or of the slack behind it keeps what its block held before (pm_pool_clear_kernel)
+    const size_t n_clear = pool + c.spts_slack / sizeof(P4);
+    pm_pool_clear_kernel<P4><<<(unsigned)std::min<size_t>((n_clear + kBlock - 1) / kBlock, 8192), kBlock, 0, h->stream>>>((P4*)c.spts, n_clear);
+  }
   if (c.nrm) HIP_TRY(dev_alloc(h, &c.snrm, sizeof(P4) * pool));
   PM_ALLOC(d.row_cap, sizeof(int) * pm->rows);
   PM_ALLOC(d.row_flag, sizeof(int) * pm->rows);

@@ -342,7 +342,17 @@ __device__ __forceinline__ typename Scalar<P4>::type consider(const P4& t, int p
                                                               typename Scalar<P4>::type qy, typename Scalar<P4>::type qz,
                                                               const CropDev& crop, NNBest<P4>& best) {
   using R = typename Scalar<P4>::type;
-  const R dx = t.x - qx, dy = t.y - qy, dz = t.z - qz;
+  R dx, dy;
+  if constexpr (sizeof(R) == 4) {
+    // f32 storage: x and y of a loaded candidate sit in an even-aligned register pair, so (dx, dy) is ONE packed subtraction from the
+    // pair (qx, qy), which is loop-invariant in every scan.  Each half rounds as the scalar subtraction does
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 d = f32x2{t.x, t.y} - f32x2{qx, qy};
+    dx = d.x, dy = d.y;
+  } else {
+    dx = t.x - qx, dy = t.y - qy;
+  }
+  const R dz = t.z - qz;
   const R d2 = dist2(dx, dy, dz);
   // strict d2 < best (initially r^2); ties broken towards the smaller original index
   bool better = valid & nn_before(d2, t.i, best.d2, best.idx);
@@ -367,7 +377,6 @@ __device__ __forceinline__ typename Scalar<P4>::type consider(const P4& t, int p
 // needs no search at all -- the listed points and their normals are fetched BEFORE the pose is known, while the previous pass's
 // 6x6 system is being solved (icp_pass_body, "verified match").  A list holds at most kSetCap points (one per lane of the query's
 // group); a longer one, or a margin of zero, means "no set": that query searches again next pass, from the bound it has.
-constexpr size_t kScanMaxBytes = (size_t)1 << 32;  // the largest array scan_strided can be pointed at (32-bit byte offsets): held where an index is built
 constexpr int kSetCap = 4;
 template <typename R>
 struct Collect {
@@ -381,32 +390,48 @@ __device__ __forceinline__ void collect_push(const Collect<R>& c, int p) {
   if (k < kSetCap) c.list[k] = p;
 }
 
+// scan_strided loads the candidates of a batch whether or not they lie inside the range: up to kInFlight - 1 strides of at most 64 elements
+// beyond its end, i.e. beyond the end of the ARRAY when the range is its last.  Every array a scan can be pointed at (the cell-sorted
+// points of an index, its replica, the index pool of a persistent map) is allocated with this much behind its last element; the
+// launch set-up refuses a target without it (begin_session).  What is loaded from there is never looked at.
+constexpr size_t kScanSlackBytes = 4096;
+// the largest array scan_strided can be pointed at: a candidate's address is a 32-bit byte offset, and an offset into the slack must not
+// wrap.  Held where an index is built
+constexpr size_t kScanMaxBytes = ((size_t)1 << 32) - kScanSlackBytes;
+
 // candidates s+lane, s+lane+stride, ... of [s,e): four loads issued before the first is consumed (two with f64 storage: a
 // candidate is eight registers there, and four in flight pushed the kernel over its register budget -- spills that the compiler
 // places inside divergent regions, which is not safe: a value stored under a narrow EXEC mask and reloaded under a wider one)
 // kRep: [s, e) is a range of the replica (GridDev::rpts); a listed candidate then goes into the list as -2 - (replica position), which the
 // writer of the set maps to the canonical position (rpos) -- one lookup per kept set instead of one per listed candidate
-template <typename P4, bool kCrop, bool kCollect, bool kRep = false>
+// kStride: the stride when the caller knows it at compile time (the lanes of a group), 0: `stride` (the far stage's regrouped lanes)
+template <typename P4, bool kCrop, bool kCollect, bool kRep = false, int kStride = 0>
 __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, int e, int lane, int stride, typename Scalar<P4>::type qx,
                                              typename Scalar<P4>::type qy, typename Scalar<P4>::type qz, const CropDev& crop,
                                              NNBest<P4>& best, const Collect<typename Scalar<P4>::type>& col) {
   using R = typename Scalar<P4>::type;
   constexpr int kInFlight = sizeof(R) == 8 ? 2 : 4;
+  static_assert((kInFlight - 1) * 64 * sizeof(P4) <= kScanSlackBytes && kStride <= 64, "what a batch loads beyond the end of a range lies in the slack");
+  const int st = kStride ? kStride : stride;
   // the array's base is wave-uniform (scalar registers) and a candidate's address a 32-bit byte offset added to it by the load itself:
   // a searched array holds at most kScanMaxBytes
   const char* __restrict__ tb = (const char*)tp;
-  for (int p = s + lane; p < e; p += kInFlight * stride) {
+  for (int p = s + lane; p < e; p += kInFlight * st) {
     int pk[kInFlight];
     bool vk[kInFlight];
     P4 tk[kInFlight];
     R dk[kInFlight];
 #pragma unroll
     for (int k = 0; k < kInFlight; ++k) {
-      pk[k] = p + k * stride;
+      pk[k] = p + k * st;
       vk[k] = pk[k] < e;
-      // clamped, not predicated: branches around the loads measured slower.  (The clamp selects the index and the offset is its shift:
-      // selecting among offsets o, o + step, ... keeps 2 * step and 3 * step in registers across the whole search)
-      tk[k] = *(const P4*)(tb + (unsigned)(vk[k] ? pk[k] : p) * (unsigned)sizeof(P4));
+      // neither predicated (branches around the loads measured slower) nor clamped to the range: a candidate at or beyond e is loaded
+      // from where it would lie -- inside the allocation, see kScanSlackBytes -- and vk[k] keeps it from winning and from being listed.
+      // With a compile-time stride the k-th address is the first plus a constant, which the load instruction adds itself
+      if (kStride)
+        tk[k] = *(const P4*)(tb + (size_t)((unsigned)p * (unsigned)sizeof(P4)) + (size_t)k * kStride * sizeof(P4));
+      else
+        tk[k] = *(const P4*)(tb + (unsigned)pk[k] * (unsigned)sizeof(P4));
     }
     // f64 storage: every load of the batch is issued before the first is consumed -- the scheduler otherwise put the first candidate's
     // subtraction (and the wait for its load) in front of the second candidate's loads: two dependent memory rounds per iteration.
@@ -415,8 +440,9 @@ __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, i
 #pragma unroll
     for (int k = 0; k < kInFlight; ++k) dk[k] = consider<P4, kCrop>(tk[k], pk[k], vk[k], qx, qy, qz, crop, best);
     if (kCollect) {
-      // the candidate-set list: a handful of points per query lie inside tau, so ONE test per batch of candidates (a clamped load
-      // repeats candidate p, so the minimum needs no masks; the flags sort it out inside)
+      // the candidate-set list: a handful of points per query lie inside tau, so ONE test per batch of candidates.  The minimum is
+      // taken over whatever was loaded, candidates beyond the range included: at worst the test fires for nothing, the flags sort it
+      // out inside
       R dmin = dk[0];
 #pragma unroll
       for (int k = 1; k < kInFlight; ++k) dmin = min(dmin, dk[k]);
@@ -429,17 +455,110 @@ __device__ __forceinline__ void scan_strided(const P4* __restrict__ tp, int s, i
   }
 }
 
+// ---- lane exchange inside a row of 16 lanes by DPP: the source lane is an operand modifier of a register move, where __shfl is an LDS
+// instruction (ds_bpermute) with its address arithmetic (lane number, xor, compare, select, shift) and a wait for the LDS queue.
+// Every lane a control reads from must be active; the callers' branches are uniform over the lanes that exchange (a group, or the
+// wavefront).  A lane whose source is not active reads zero.
+constexpr int kDppQuadXor1 = 0xB1;     // quad_perm:[1,0,3,2]  lane ^ 1
+constexpr int kDppQuadXor2 = 0x4E;     // quad_perm:[2,3,0,1]  lane ^ 2
+constexpr int kDppQuadShr1 = 0x90;     // quad_perm:[0,0,1,2]  lane - 1 inside the quad (lane 0 of a quad: itself, masked by the caller)
+constexpr int kDppQuadShr2 = 0x40;     // quad_perm:[0,0,0,1]  lane - 2 inside the quad
+constexpr int kDppQuadLane3 = 0xFF;    // quad_perm:[3,3,3,3]  the quad's last lane
+constexpr int kDppRowHalfMirror = 0x141;  // lane l of every 8 reads lane 7 - l
+constexpr int kDppRowMirror = 0x140;      // lane l of every 16 reads lane 15 - l
+template <int kCtrl>
+__device__ __forceinline__ int dpp_move(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xF, 0xF, true);  // (bound_ctrl with old = 0: no copy of v in front of the move)
+}
+template <int kCtrl>
+__device__ __forceinline__ float dpp_move(float v) {
+  return __int_as_float(dpp_move<kCtrl>(__float_as_int(v)));
+}
+template <int kCtrl>
+__device__ __forceinline__ double dpp_move(double v) {
+  return __hiloint2double(dpp_move<kCtrl>(__double2hiint(v)), dpp_move<kCtrl>(__double2loint(v)));
+}
+template <int kCtrl>
+__device__ __forceinline__ int64_t dpp_move(int64_t v) {
+  const unsigned lo = (unsigned)dpp_move<kCtrl>((int)(unsigned)v), hi = (unsigned)dpp_move<kCtrl>((int)(unsigned)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// b := the first of b and o under nn_before (o only if it is a point at all)
+template <typename P4>
+__device__ __forceinline__ void nn_take(NNBest<P4>& b, typename Scalar<P4>::type od2, int opos, typename Scalar<P4>::index oidx) {
+  const bool take = (opos != -1) & nn_before(od2, oidx, b.d2, b.idx);
+  b.d2 = take ? od2 : b.d2;
+  b.pos = take ? opos : b.pos;
+  b.idx = take ? oidx : b.idx;
+}
+template <typename P4, int kCtrl>
+__device__ __forceinline__ void nn_take_dpp(NNBest<P4>& b) {
+  nn_take<P4>(b, dpp_move<kCtrl>(b.d2), dpp_move<kCtrl>(b.pos), dpp_move<kCtrl>(b.idx));
+}
+// the two halves of a 32-bit (or 64-bit) value that the gfx950 lane swaps exchange: after swap(v, v), lanes of the lower half hold
+// {own, partner's} and lanes of the upper half {partner's, own}
+template <bool k32>
+__device__ __forceinline__ void lane_swap(int v, int* a, int* b) {
+  const auto r = k32 ? __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false)
+                     : __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  *a = (int)r[0], *b = (int)r[1];
+}
+template <bool k32>
+__device__ __forceinline__ void lane_swap(float v, float* a, float* b) {
+  int ia, ib;
+  lane_swap<k32>(__float_as_int(v), &ia, &ib);
+  *a = __int_as_float(ia), *b = __int_as_float(ib);
+}
+template <bool k32>
+__device__ __forceinline__ void lane_swap(double v, double* a, double* b) {
+  int la, lb, ha, hb;
+  lane_swap<k32>(__double2loint(v), &la, &lb);
+  lane_swap<k32>(__double2hiint(v), &ha, &hb);
+  *a = __hiloint2double(ha, la), *b = __hiloint2double(hb, lb);
+}
+template <bool k32>
+__device__ __forceinline__ void lane_swap(int64_t v, int64_t* a, int64_t* b) {
+  int la, lb, ha, hb;
+  lane_swap<k32>((int)(unsigned)v, &la, &lb);
+  lane_swap<k32>((int)(unsigned)((uint64_t)v >> 32), &ha, &hb);
+  *a = (int64_t)(((uint64_t)(unsigned)ha << 32) | (unsigned)la), *b = (int64_t)(((uint64_t)(unsigned)hb << 32) | (unsigned)lb);
+}
+// b := the first, under nn_before, of b and the lane 16 (k32: 32) lanes away.  The swap hands every lane the pair {lower lane's, upper
+// lane's}; both lanes reduce that same ordered pair, so neither needs to know which of the two is its own.
+template <typename P4, bool k32>
+__device__ __forceinline__ void nn_take_swap(NNBest<P4>& b) {
+  NNBest<P4> lo, hi;
+  lane_swap<k32>(b.d2, &lo.d2, &hi.d2);
+  lane_swap<k32>(b.pos, &lo.pos, &hi.pos);
+  lane_swap<k32>(b.idx, &lo.idx, &hi.idx);
+  // (for the upper lane this reads "keep mine if it comes before the other's", where nn_take reads "take the other's if it comes before
+  // mine": the same winner unless neither comes before the other -- equal keys, the same entry -- or the upper lane's is an empty bound
+  // that comes before the lower lane's point, which no scan leaves: a point is only ever taken in front of the bound it replaces)
+  nn_take<P4>(lo, hi.d2, hi.pos, hi.idx);
+  b = lo;
+}
+
+// every lane of a group of W := the first of the group's entries under nn_before (nearer, or as near with the smaller original index).
+// That order is a strict total order on (d2, idx), and two entries with equal keys are the same target point or the same empty bound, so
+// ANY exchange pattern in which every lane ends up combined with every other leaves the same winner in every lane: lane ^ 1 and lane ^ 2
+// inside a quad, then the mirror images inside 8 and 16 lanes (every lane of a quad holds the quad's winner by then, so the mirrored
+// lane stands for its whole quad), then the lane swaps across 16 and 32.  Widths 4 and 64 are what the kernels are built with; the
+// others keep the generic form.
 template <typename P4, int W>
 __device__ __forceinline__ void lanes_min(NNBest<P4>& b) {
+  if constexpr (W == 4 || W == 64) {
+    nn_take_dpp<P4, kDppQuadXor1>(b);
+    nn_take_dpp<P4, kDppQuadXor2>(b);
+    if constexpr (W == 64) {
+      nn_take_dpp<P4, kDppRowHalfMirror>(b);
+      nn_take_dpp<P4, kDppRowMirror>(b);
+      nn_take_swap<P4, false>(b);
+      nn_take_swap<P4, true>(b);
+    }
+  } else {
 #pragma unroll
-  for (int m = 1; m < W; m <<= 1) {
-    const auto od2 = __shfl_xor(b.d2, m, W);
-    const int opos = __shfl_xor(b.pos, m, W);
-    const auto oidx = __shfl_xor(b.idx, m, W);
-    const bool take = (opos != -1) & nn_before(od2, oidx, b.d2, b.idx);
-    b.d2 = take ? od2 : b.d2;
-    b.pos = take ? opos : b.pos;
-    b.idx = take ? oidx : b.idx;
+    for (int m = 1; m < W; m <<= 1) nn_take<P4>(b, __shfl_xor(b.d2, m, W), __shfl_xor(b.pos, m, W), __shfl_xor(b.idx, m, W));
   }
 }
 
@@ -482,12 +601,20 @@ __device__ __forceinline__ void lds_wave_sync() {
 template <int G>
 __device__ __forceinline__ int group_exclusive_sum(int c, int gl, int* total) {
   int incl = c;
+  if constexpr (G == 4) {  // a group is a quad: DPP (see dpp_move)
+    const int o1 = dpp_move<kDppQuadShr1>(incl);
+    if (gl >= 1) incl += o1;
+    const int o2 = dpp_move<kDppQuadShr2>(incl);
+    if (gl >= 2) incl += o2;
+    *total = dpp_move<kDppQuadLane3>(incl);
+  } else {
 #pragma unroll
-  for (int d = 1; d < G; d <<= 1) {
-    const int o = __shfl_up(incl, d, G);
-    if (gl >= d) incl += o;
+    for (int d = 1; d < G; d <<= 1) {
+      const int o = __shfl_up(incl, d, G);
+      if (gl >= d) incl += o;
+    }
+    *total = __shfl(incl, G - 1, G);
   }
-  *total = __shfl(incl, G - 1, G);
   return incl - c;
 }
 
@@ -612,7 +739,7 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
         e = jb == 1 ? v[1] : (jb == 2 ? v[2] : v[3]);
       }
     }
-    scan_strided<P4, kCrop, kCollect, true>(rp, s, e, gl, G, qx, qy, qz, crop, best, col);
+    scan_strided<P4, kCrop, kCollect, true, G>(rp, s, e, gl, G, qx, qy, qz, crop, best, col);
     lanes_min<P4, G>(best);
     if (best.pos != -1 && !(pos0 != -1 && best.idx == idx0)) best.pos = g.rpos[best.pos];
   } else {
@@ -658,7 +785,7 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
       lds_wave_sync();
       for (int t = 0; t < total; ++t) {
         const int2 se = seg[t];
-        scan_strided<P4, kCrop, kCollect>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
+        scan_strided<P4, kCrop, kCollect, false, G>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
       }
       lds_wave_sync();  // the list is rewritten by stage 2
       lanes_min<P4, G>(best);
@@ -710,7 +837,7 @@ __device__ __forceinline__ NNBest<P4> nn_search_group(const GridDev& g, const P4
       lds_wave_sync();
       for (int t = 0; t < total; ++t) {
         const int2 se = seg[t];
-        scan_strided<P4, kCrop, kCollect>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
+        scan_strided<P4, kCrop, kCollect, false, G>(tp, se.x, se.y, gl, G, qx, qy, qz, crop, best, col);
       }
       lds_wave_sync();
       lanes_min<P4, G>(best);
@@ -992,6 +1119,9 @@ template <typename P4>
 struct QueryPrefetch {
   P4 s, tprev;
   int prev;
+  // the query this lane's group serves (query_index of the batch): the pass body of a one-batch workgroup takes it from here and not
+  // from a second query_index, whose spread orders divide 64-bit numbers in software (passes 0 and 1).  32 bits: see prefetch_query
+  unsigned qi;
   // candidate-set mode: THIS LANE's listed point (prev / tprev above) and its normal, and the set's reference {p_ref, L}
   P4 nprev;
   typename Scalar<P4>::type rx, ry, rz, rL;
@@ -1022,6 +1152,8 @@ __device__ __forceinline__ QueryPrefetch<P4> prefetch_query(const IcpPassArgs& a
   q.rx = q.ry = q.rz = q.rL = (R)0;
   const bool sets = use_cache && use_sets && a.set_pos != nullptr;  // (use_sets: the fused kernel only, see icp_pass_body)
   const size_t i = query_index<kQPB, 64 / kGroup>(n_deal, batch, threadIdx.x / kGroup, order);
+  // (query_index returns at most n_deal <= a.count; a pass that reads qi back serves at most kFusedMaxQueries queries)
+  q.qi = (unsigned)i;
   if (a.count == 0) return q;
   // Straight-line loads, no branch per lane and none per mode (a lane past the end reads the last query and drops it; a mode that has no
   // use for a load reads a harmless address): a load inside a conditional block is followed by the moves that merge it with the other
@@ -1159,7 +1291,8 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
   if (threadIdx.x == 0) s_far[0] = s_far[1] = 0;
   lds_barrier();
   for (size_t b = (size_t)wg; b < n_batches; b += kSingle ? n_batches : (size_t)nwg) {
-    const size_t i = query_index<kQPB, 64 / kGroup>(n_live, b, ql, order);
+    // (one batch: first_batch was dealt with this n_live, this order and b = wg)
+    const size_t i = kSingle ? (size_t)first_batch.qi : query_index<kQPB, 64 / kGroup>(n_live, b, ql, order);
     double px = 0, py = 0, pz = 0;
     NNBest<P4> nn;
     nn.pos = -1;

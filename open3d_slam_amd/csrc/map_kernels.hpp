@@ -364,6 +364,20 @@ __global__ __launch_bounds__(kBlock) void pm_hash_init_kernel(PmHash* __restrict
   }
 }
 // per slot of the base [pass block | voxel block in key order]: history, hash chain, settled or not (its colour is the array's: nothing to do)
+// Every position of a fresh index pool, and of the scan loop's slack behind it, holds pm_kill's sentinel until a point is placed there.  A row
+// page ends with slots no point has been written to yet, rows that grow move to the pool's top, and the search's scan loop loads candidates
+// beyond the end of a range without clamping (icp_kernels.hpp: scan_strided): what it finds there is then a point that is never the
+// nearest neighbour of anything, not what a reused block was left with -- in this index no result rests on the loop's validity flags alone.
+// Once per fold (pm_enter_t), a plain store per position.
+template <typename P4>
+__global__ __launch_bounds__(kBlock) void pm_pool_clear_kernel(P4* __restrict__ pool, size_t n) {
+  using R = typename Scalar<P4>::type;
+  P4 far;  // (pm_kill's sentinel)
+  far.x = far.y = far.z = sizeof(R) == 4 ? (R)3.0e38f : (R)1.0e300;
+  far.i = (typename Scalar<P4>::index)0x7fffffff;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) pool[i] = far;
+}
+
 template <typename P4>
 __global__ __launch_bounds__(kBlock) void pm_enter_kernel(PmDev m, int n) {
   int* err = m.counters + kPmError;
