@@ -106,7 +106,8 @@ int o3ds_profile_enable(o3ds_handle h, int on);
 int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
 /* Tagged spans for bench.py's per-call table: while profiling is enabled, o3ds_profile_span(h, tag, 0) / (h, tag, 1) record a pair
  * of hipEvents on the handle's stream around whatever the caller enqueues in between (tags 0..7).  Tags 8 (the two kernels of
- * normal estimation) and 9 (the kernels of an index build) are marked inside the library.  span_read synchronises, returns the
+ * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
+ * are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -443,6 +444,48 @@ int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_
  * the host knew the size), so repeated calls give the same bits; non-finite points propagate into the mean; an empty cloud gives
  * (0, 0, 0).  A submap in its persistent form is first turned into its array (as a download would).  Waits for the result. */
 int o3ds_cloud_center(o3ds_handle h, o3ds_cloud c, double center[3]);
+
+/* ---- neighbour queries between device clouds: [O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid ------------------------------
+ * The neighbours in `target` of n_queries points of `queries` (the points query_idx[0..n_queries), repeats allowed; NULL: all its points,
+ * in order, and n_queries is its size).  Both ids may name the same cloud; a query that is a point of the target finds itself.
+ * The result of one query is defined without reference to a search structure:
+ *   - target coordinates are the stored ones; the query is the stored point, or with a pose storage(T s), T s = ((T00 x + T01 y) + T02 z)
+ *     + T03 per row in f64 (T column-major, rigid: the fourth row is not read);
+ *   - d2 = (dx*dx + dy*dy) + dz*dz in the storage type, every operation rounded on its own;
+ *   - a candidate is accepted iff d2 is finite and (radius <= 0, or d2 < storage(radius * radius) strictly, the product formed in f64);
+ *   - row i of idx / d2 holds the first max_nn accepted candidates in the order (d2, original target index), count[i] of them; entries
+ *     past count[i] are zero; d2 is the storage-type value widened;
+ *   - total[i] is the number of accepted candidates whatever max_nn is (truncation shows as total[i] > count[i]);
+ *   - a query with a non-finite coordinate has an empty list and total 0; target points with a NaN coordinate are never accepted.
+ * Modes:  KNN     radius <= 0, max_nn 1..128   (SearchKNN)
+ *         Hybrid  radius >  0, max_nn 1..128   (SearchHybrid)
+ *         Radius  radius >  0, max_nn 0..128   (SearchRadius; max_nn == 0 counts only: idx and d2 are NULL)
+ * Without `total` a Hybrid search ends at its max_nn-th neighbour; with it, it visits everything within the radius.
+ * The target's grid index is used if it has one (o3ds_cloud_build_index, o3ds_estimate_normals, an earlier search) and built and left
+ * with the cloud otherwise; a target in the persistent map form is first folded into its array.  An empty target is not an error: every
+ * list is empty.  O3DS_ERR_INVALID_ARG: max_nn < 0 or > 128, max_nn == 0 without a radius, idx NULL with max_nn > 0 (or the reverse),
+ * an unknown id, a query_idx entry beyond the query cloud, clouds of two storage types, a target with an infinite coordinate.
+ * Waits for the result. */
+int o3ds_neighbor_search(o3ds_handle h, o3ds_cloud queries, o3ds_cloud target, const double T[16] /* NULL: queries as stored */,
+                         const uint32_t* query_idx /* NULL: all points of `queries`, in order */, size_t n_queries, int max_nn, double radius,
+                         uint32_t* idx /* n_queries * max_nn, row i = list of query i; NULL iff max_nn == 0 */,
+                         double* d2 /* same shape; may be NULL */, uint32_t* count /* n_queries: entries of row i that are valid */,
+                         uint32_t* total /* n_queries; may be NULL */);
+/* [O3D] PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio), wholly on the device: the KNN search above with the cloud as its
+ * own target (self included, so one term is 0), a_i = (sum of sqrt(d2)) / count over point i's list, square root and sum in f64 in list
+ * order; a point is valid iff a_i > 0; mean = sum a_i / n_valid and std = sqrt(sum (a_i - mean)^2 / (n_valid - 1)) over the valid points,
+ * both sums in f64 in the fixed order of o3ds_cloud_center; point i is kept iff a_i > 0 && a_i < mean + std_ratio * std.  With
+ * n_valid < 2 the threshold is NaN (0 / 0) and nothing is kept.  `out` receives the kept points with their normals and colours, in cloud
+ * order, as o3ds_crop_cloud carries them (FPFH features are not carried); kept_idx (may be NULL) their indices in `in`, at most
+ * `capacity` of them -- more kept points than that: O3DS_ERR_CAPACITY, *n_kept holds their number and no cloud is made.
+ * O3DS_ERR_INVALID_ARG with Open3D's message for nb_neighbors < 1 or std_ratio <= 0; nb_neighbors > 128 is unsupported. */
+int o3ds_remove_statistical_outliers(o3ds_handle h, o3ds_cloud in, int nb_neighbors, double std_ratio, o3ds_cloud* out,
+                                     uint32_t* kept_idx /* may be NULL */, size_t capacity, size_t* n_kept);
+/* [O3D] PointCloud::RemoveRadiusOutliers(nb_points, radius): point i is kept iff total_i > nb_points, total_i the Radius-mode count of
+ * the search above with the cloud as its own target, self included.  Output and errors as for the statistical filter (Open3D's message
+ * for nb_points < 1 or radius <= 0). */
+int o3ds_remove_radius_outliers(o3ds_handle h, o3ds_cloud in, int nb_points, double radius, o3ds_cloud* out, uint32_t* kept_idx /* may be NULL */,
+                                size_t capacity, size_t* n_kept);
 /* mapCloud_ += cloud (Submap.cpp:70; [O3D] PointCloud::operator+=). Appends `add` to `map` in place. */
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add);
 /* A copy of a cloud of handle `src` as a cloud of handle `dst` (same device, same storage precision), device to device: points,

@@ -186,6 +186,12 @@ SIGNATURES = {
     "o3ds_random_down_sample": (C.c_int, [_H, _CL, C.c_double, C.c_uint64, C.POINTER(_CL)]),
     "o3ds_transform_cloud": (C.c_int, [_H, _CL, _dp, C.POINTER(_CL)]),
     "o3ds_cloud_center": (C.c_int, [_H, _CL, _dp]),
+    "o3ds_neighbor_search": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(C.c_uint32), C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_uint32), _dp,
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "o3ds_remove_statistical_outliers": (C.c_int, [_H, _CL, C.c_int, C.c_double, C.POINTER(_CL), C.POINTER(C.c_uint32), C.c_size_t,
+                                                   C.POINTER(C.c_size_t)]),
+    "o3ds_remove_radius_outliers": (C.c_int, [_H, _CL, C.c_int, C.c_double, C.POINTER(_CL), C.POINTER(C.c_uint32), C.c_size_t,
+                                              C.POINTER(C.c_size_t)]),
     "o3ds_cloud_append": (C.c_int, [_H, _CL, _CL]),
     "o3ds_cloud_copy_across": (C.c_int, [_H, _H, _CL, C.POINTER(_CL)]),
     "o3ds_voxelize_within_volume": (C.c_int, [_H, _CL, C.c_double, C.POINTER(Crop)]),
@@ -831,6 +837,45 @@ class Backend:
         out = np.zeros(3)
         self._ck(self.lib.o3ds_cloud_center(self.h, cid, out.ctypes.data_as(_dp)))
         return out
+
+    # -- neighbour queries and the outlier filters
+    def neighbor_search(self, queries: int, target: int, max_nn: int, radius: float = 0.0, T=None, query_idx=None):
+        """o3ds_neighbor_search: (idx, d2, count, total) of every query -- idx (n, max_nn) uint32 and d2 (n, max_nn) float64, row i the
+        first max_nn accepted target points in the order (d2, index), entries past count[i] zero; total[i] the number of accepted points
+        whatever max_nn is.  radius <= 0: the max_nn nearest (SearchKNN); radius > 0: of those with d2 < radius^2 (SearchHybrid;
+        max_nn == 0 counts only and idx / d2 have no columns: SearchRadius).  T moves the queries first; query_idx picks (and may repeat)
+        points of the query cloud, default all of them in order."""
+        u32p = C.POINTER(C.c_uint32)
+        if query_idx is None:
+            n, qp, qi = self.size(queries)[0], None, None
+        else:
+            qi = np.ascontiguousarray(query_idx, dtype=np.uint32).ravel()
+            n, qp = len(qi), qi.ctypes.data_as(u32p)
+        k = int(max_nn)
+        rows = max(n, 1)  # (numpy may hand out a NULL pointer for an empty array; the ABI reads NULL as "absent")
+        idx = np.zeros((rows, max(k, 0)), np.uint32)[:n]
+        d2 = np.zeros((rows, max(k, 0)), np.float64)[:n]
+        count = np.zeros(rows, np.uint32)[:n]
+        total = np.zeros(rows, np.uint32)[:n]
+        Tc, tp = _d(None if T is None else colmajor(T))
+        self._ck(self.lib.o3ds_neighbor_search(self.h, queries, target, tp, qp, n, k, float(radius), idx.ctypes.data_as(u32p) if k > 0 else None,
+                                               d2.ctypes.data_as(_dp) if k > 0 else None, count.ctypes.data_as(u32p), total.ctypes.data_as(u32p)))
+        return idx, d2, count, total
+
+    def _outlier_filter(self, fn, cid: int, k: int, v: float):
+        n = self.size(cid)[0]
+        kept = np.zeros(max(n, 1), np.uint32)
+        out, n_kept = _CL(), C.c_size_t()
+        self._ck(fn(self.h, cid, int(k), float(v), C.byref(out), kept.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(n_kept)))
+        return out.value, kept[: n_kept.value].copy()
+
+    def remove_statistical_outliers(self, cid: int, nb_neighbors: int, std_ratio: float):
+        """[O3D] RemoveStatisticalOutliers on the device: (new cloud id, indices of the kept points in `cid`, ascending)"""
+        return self._outlier_filter(self.lib.o3ds_remove_statistical_outliers, cid, nb_neighbors, std_ratio)
+
+    def remove_radius_outliers(self, cid: int, nb_points: int, radius: float):
+        """[O3D] RemoveRadiusOutliers on the device: (new cloud id, indices of the kept points in `cid`, ascending)"""
+        return self._outlier_filter(self.lib.o3ds_remove_radius_outliers, cid, nb_points, radius)
 
     def cloud_append(self, map_id: int, add_id: int):
         self._ck(self.lib.o3ds_cloud_append(self.h, map_id, add_id))

@@ -26,6 +26,7 @@
 #include "feature_kernels.hpp"
 #include "icp_kernels.hpp"
 #include "map_kernels.hpp"
+#include "neighbor_kernels.hpp"
 #include "normals_kernel.hpp"
 #include "pose_graph_kernels.hpp"
 
@@ -589,7 +590,7 @@ void span_mark(o3ds_handle h, int tag) {
   }
   (void)hipEventRecord(v[h->span_used[tag]++], h->stream);
 }
-constexpr int kSpanNormalsKernels = 8, kSpanIndexBuild = 9;  // internal tags
+constexpr int kSpanNormalsKernels = 8, kSpanIndexBuild = 9, kSpanNeighborKernel = 10;  // internal tags
 
 #define TMP_ALLOC(ptr, bytes)                                   \
   do {                                                          \
@@ -3522,6 +3523,158 @@ int dense_carve_t(o3ds_handle h, DenseRec& d, const CloudRec& c, const double* s
   if (n_removed) *n_removed = (size_t)removed;
   return O3DS_OK;
 }
+
+// ---- neighbour queries and the outlier filters (neighbor_kernels.hpp) ---------------------------------------------------------------
+// The classic grid index of a search target: the one the cloud has, whatever its cell (any cell gives the same lists, only slower), or a
+// new one whose cell is chosen as normals_t chooses one -- a pilot grid, the mean number of points per occupied pilot cell, cell = pilot *
+// sqrt(max_nn / (pi * mean)) -- with the pilot at radius / 8 and the clamp to [radius / 64, radius] of a bounded search, and for an
+// unbounded one a pilot of the box's longest side / min(128, max(4, sqrt(n))) -- a small cloud gets a small grid: a list that cannot be
+// filled walks all of it --, clamped to [pilot / 16, 16 pilot].  The new index stays with the cloud, marked as a by-product: a
+// registration keeps it only if its cell suits.
+template <typename P4>
+int neighbor_index_t(o3ds_handle h, CloudRec& c, double radius, int max_nn) {
+  if (c.has_index && c.cell_start && c.spts && c.grid.sx == c.grid.nx) return O3DS_OK;
+  double pilot = radius / 8.0;
+  if (!(radius > 0.0)) {
+    if (!c.has_box) {
+      double mn[3], mx[3];
+      const int rb = bbox_of<P4>(h, (const P4*)c.pts, c.n, mn, mx);
+      if (rb) return rb;
+      c.has_box = true;
+      c.box_padded = false;
+      for (int a = 0; a < 3; ++a) c.bmn[a] = mn[a], c.bmx[a] = mx[a];
+    }
+    pilot = std::max(std::max(c.bmx[0] - c.bmn[0], c.bmx[1] - c.bmn[1]), c.bmx[2] - c.bmn[2]) / std::min(128.0, std::max(4.0, std::sqrt((double)c.n)));
+    if (!(pilot > 0.0) || !std::isfinite(pilot)) pilot = 1.0;
+  }
+  int rc = build_index_t<P4>(h, c, pilot);
+  if (rc) return rc;
+  const size_t ncell = (size_t)c.grid.nx * c.grid.ny * c.grid.nz;
+  unsigned long long* d_occ = nullptr;
+  TMP_ALLOC(d_occ, sizeof(unsigned long long));
+  HIP_TRY(hipMemsetAsync(d_occ, 0, sizeof(unsigned long long), h->stream));
+  count_occupied_kernel<<<grid_for(ncell), kBlock, 0, h->stream>>>(c.cell_start, ncell, d_occ);
+  unsigned long long occ = 0;
+  rc = read_back(h, {{&occ, d_occ, sizeof(occ)}});
+  if (rc) return rc;
+  const double avg = occ ? (double)c.n / (double)occ : 1.0;
+  double cell = c.grid.cell * std::sqrt(std::max(1.0, (double)max_nn) / (3.14159265358979 * avg));
+  cell = radius > 0.0 ? std::min(std::max(cell, radius / 64.0), radius) : std::min(std::max(cell, pilot / 16.0), pilot * 16.0);
+  rc = build_index_t<P4>(h, c, cell);
+  if (rc) return rc;
+  c.index_byproduct = true;
+  return O3DS_OK;
+}
+
+// The search of `nq` queries (points d_qidx[0..nq) of `q`, null: its points in order; moved by T if given) in `t`, results in device arrays:
+// d_idx / d_d2 [nq * max_nn] (either may be null), d_cnt [nq], d_tot [nq] (null: not wanted, and a bounded search may stop at its
+// max_nn-th key), d_avg [nq] (null: not wanted).  *empty: the target has no point with three finite coordinates -- nothing was launched,
+// every list is empty.
+template <typename P4>
+int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const double* T, const uint32_t* d_qidx, size_t nq, int max_nn, double radius,
+                      uint32_t* d_idx, double* d_d2, uint32_t* d_cnt, uint32_t* d_tot, double* d_avg, bool* empty) {
+  *empty = true;
+  if (t.n == 0 || nq == 0) return O3DS_OK;
+  unsigned int* d_fin = nullptr;
+  TMP_ALLOC(d_fin, sizeof(unsigned int));
+  HIP_TRY(hipMemsetAsync(d_fin, 0, sizeof(unsigned int), h->stream));
+  count_finite_kernel<P4><<<grid_for(t.n), kBlock, 0, h->stream>>>((const P4*)t.pts, t.n, d_fin);
+  unsigned int n_fin = 0;
+  int rc = read_back(h, {{&n_fin, d_fin, sizeof(n_fin)}});
+  if (rc) return rc;
+  if (n_fin == 0) return O3DS_OK;
+  rc = neighbor_index_t<P4>(h, t, radius, max_nn);
+  if (rc) return rc;
+  *empty = false;
+  const unsigned int gsz = (unsigned int)((nq + kNbrQueriesPerBlock - 1) / kNbrQueriesPerBlock);
+  const Mat34 M = mat34(T);
+  const P4* qp = (const P4*)q.pts;  // (q may be t: its points did not move)
+  const P4* sp = (const P4*)t.spts;
+  span_mark(h, kSpanNeighborKernel);
+  if (max_nn <= 32)
+    neighbor_kernel<P4, 32><<<gsz, 64, 0, h->stream>>>(qp, d_qidx, nq, T ? 1 : 0, M, t.grid, sp, max_nn, radius, d_tot ? 1 : 0, d_fin, d_idx, d_d2, d_cnt,
+                                                      d_tot, d_avg);
+  else
+    neighbor_kernel<P4, 128><<<gsz, 64, 0, h->stream>>>(qp, d_qidx, nq, T ? 1 : 0, M, t.grid, sp, max_nn, radius, d_tot ? 1 : 0, d_fin, d_idx, d_d2, d_cnt,
+                                                       d_tot, d_avg);
+  span_mark(h, kSpanNeighborKernel);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+// [O3D] RemoveStatisticalOutliers (mode 0: k = nb_neighbors, v = std_ratio) and RemoveRadiusOutliers (mode 1: k = nb_points, v = radius):
+// the search with the cloud as its own target, the mask, the croppers' stable compaction
+template <typename P4>
+int outlier_filter_t(o3ds_handle h, CloudRec& in, int mode, int k, double v, CloudRec& out, uint32_t* kept_idx, size_t capacity, size_t* n_kept) {
+  out.precision = in.precision;
+  out.n = 0;
+  box_copy(out, in);  // a subset
+  *n_kept = 0;
+  const size_t n = in.n;
+  if (n == 0) return O3DS_OK;
+  int *flags = nullptr, *pos = nullptr;
+  uint32_t *d_cnt = nullptr, *d_tot = nullptr, *d_kept = nullptr;
+  double *d_avg = nullptr, *partial = nullptr, *stat = nullptr;
+  TMP_ALLOC(flags, sizeof(int) * (n + 1));
+  TMP_ALLOC(pos, sizeof(int) * (n + 1));
+  TMP_ALLOC(d_cnt, sizeof(uint32_t) * n);
+  bool empty = false;
+  int rc;
+  if (mode == 0) {
+    TMP_ALLOC(d_avg, sizeof(double) * n);
+    TMP_ALLOC(partial, sizeof(double) * 2 * kCenterChunks);
+    TMP_ALLOC(stat, sizeof(double) * 4);
+    rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, k, 0.0, nullptr, nullptr, d_cnt, nullptr, d_avg, &empty);
+    if (rc) return rc;
+    if (empty) HIP_TRY(hipMemsetAsync(d_avg, 0, sizeof(double) * n, h->stream));  // no list, no valid point
+    stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, nullptr, partial);
+    stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 0, v, stat);
+    stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, stat, partial);
+    stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 1, v, stat);
+    stat_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_avg, n, stat, flags);
+  } else {
+    TMP_ALLOC(d_tot, sizeof(uint32_t) * n);
+    rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, 0, v, nullptr, nullptr, d_cnt, d_tot, nullptr, &empty);
+    if (rc) return rc;
+    if (empty) HIP_TRY(hipMemsetAsync(d_tot, 0, sizeof(uint32_t) * n, h->stream));
+    radius_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_tot, n, (uint32_t)k, flags);
+  }
+  HIP_TRY(hipGetLastError());
+  rc = exclusive_scan_int(h, flags, pos, n + 1, pub_slot<int>(h, 0));
+  if (rc) return rc;
+  rc = wait_stream(h);
+  if (rc) return rc;
+  const int total = pub_value<int>(h, 0);
+  *n_kept = (size_t)total;
+  if (kept_idx && (size_t)total > capacity) return fail(h, O3DS_ERR_CAPACITY, "outlier filter: kept_idx is too small for the kept points (*n_kept holds their number)");
+  out.n = (size_t)total;
+  if (total > 0) {
+    rc = compact_cloud<P4>(h, in, n, flags, pos, 1, out.n, &out.pts, &out.nrm, &out.col);
+    if (rc) return rc;
+    if (kept_idx) {
+      TMP_ALLOC(d_kept, sizeof(uint32_t) * (size_t)total);
+      kept_index_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(flags, pos, n, d_kept);
+      HIP_TRY(hipGetLastError());
+      rc = d2h_copy(h, kept_idx, d_kept, sizeof(uint32_t) * (size_t)total);
+      if (rc) return rc;
+    }
+  }
+  return O3DS_OK;
+}
+
+int outlier_filter(o3ds_handle h, o3ds_cloud in, int mode, int k, double v, const char* what, o3ds_cloud* out, uint32_t* kept_idx, size_t capacity,
+                   size_t* n_kept) {
+  CloudRec* c = find_cloud(h, in);  // (with its exact size; a persistent map as its array)
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown cloud id");
+  if (!out || !n_kept) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": out and n_kept are required");
+  CloudRec o;
+  CloudGuard o_guard(h, o);
+  const int rc = DISPATCH(c->precision, outlier_filter_t, h, *c, mode, k, v, o, kept_idx, capacity, n_kept);
+  if (rc) return rc;
+  o_guard.release();
+  *out = add_cloud(h, std::move(o));
+  return O3DS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3679,6 +3832,75 @@ int o3ds_cloud_center(o3ds_handle h, o3ds_cloud cloud, double center[3]) {
   center_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, cnt, d_out);
   HIP_TRY(hipGetLastError());
   return read_back(h, {{center, d_out, sizeof(double) * 3}});
+}
+
+int o3ds_neighbor_search(o3ds_handle h, o3ds_cloud queries, o3ds_cloud target, const double T[16], const uint32_t* query_idx, size_t n_queries, int max_nn,
+                         double radius, uint32_t* idx, double* d2, uint32_t* count, uint32_t* total) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (max_nn < 0) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: max_nn < 0");
+  if (max_nn > 128) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: max_nn > 128 unsupported");
+  if (radius != radius) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: the radius is not a number");
+  if (max_nn == 0 && !(radius > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: a count (max_nn == 0) needs a radius > 0");
+  if ((max_nn == 0) != (idx == nullptr)) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: idx is NULL iff max_nn == 0");
+  if (max_nn == 0 && d2) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: d2 without a list (max_nn == 0)");
+  if (n_queries && !count) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: count is required");
+  CloudRec* q = find_cloud(h, queries);  // (exact sizes; a persistent map as its array)
+  if (!q) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: unknown query cloud id");
+  CloudRec* t = find_cloud(h, target);
+  if (!t) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: unknown target cloud id");
+  if (q->precision != t->precision) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: the clouds have different storage types");
+  if (!query_idx && n_queries != q->n) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: without query_idx, n_queries is the size of the query cloud");
+  for (size_t i = 0; query_idx && i < n_queries; ++i)
+    if (query_idx[i] >= q->n) return fail(h, O3DS_ERR_INVALID_ARG, "neighbor_search: query_idx out of range");
+  if (n_queries == 0) return O3DS_OK;
+  const size_t rows = n_queries * (size_t)max_nn;
+  uint32_t *d_qidx = nullptr, *d_idx = nullptr, *d_cnt = nullptr, *d_tot = nullptr;
+  double* d_d2 = nullptr;
+  if (query_idx) {
+    TMP_ALLOC(d_qidx, sizeof(uint32_t) * n_queries);
+    const int rc = h2d_copy(h, d_qidx, query_idx, sizeof(uint32_t) * n_queries);
+    if (rc) return rc;
+  }
+  if (idx) TMP_ALLOC(d_idx, sizeof(uint32_t) * rows);
+  if (d2) TMP_ALLOC(d_d2, sizeof(double) * rows);
+  TMP_ALLOC(d_cnt, sizeof(uint32_t) * n_queries);
+  if (total) TMP_ALLOC(d_tot, sizeof(uint32_t) * n_queries);
+  bool empty = false;
+  int rc = DISPATCH(t->precision, neighbor_launch_t, h, *q, *t, T, d_qidx, n_queries, max_nn, radius, d_idx, d_d2, d_cnt, d_tot, nullptr, &empty);
+  if (rc) return rc;
+  if (empty) {  // an empty target is not an error: every list is empty
+    HIP_TRY(hipStreamSynchronize(h->stream));  // (query_idx may be released by the caller)
+    if (idx) memset(idx, 0, sizeof(uint32_t) * rows);
+    if (d2) memset(d2, 0, sizeof(double) * rows);
+    memset(count, 0, sizeof(uint32_t) * n_queries);
+    if (total) memset(total, 0, sizeof(uint32_t) * n_queries);
+    return O3DS_OK;
+  }
+  if (idx) rc = d2h_copy(h, idx, d_idx, sizeof(uint32_t) * rows);
+  if (!rc && d2) rc = d2h_copy(h, d2, d_d2, sizeof(double) * rows);
+  if (!rc) rc = d2h_copy(h, count, d_cnt, sizeof(uint32_t) * n_queries);
+  if (!rc && total) rc = d2h_copy(h, total, d_tot, sizeof(uint32_t) * n_queries);
+  return rc;
+}
+
+int o3ds_remove_statistical_outliers(o3ds_handle h, o3ds_cloud in, int nb_neighbors, double std_ratio, o3ds_cloud* out, uint32_t* kept_idx, size_t capacity,
+                                     size_t* n_kept) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (nb_neighbors < 1 || !(std_ratio > 0.0))
+    return fail(h, O3DS_ERR_INVALID_ARG, "[RemoveStatisticalOutliers] Illegal input parameters, the number of neighbors and standard deviation ratio must be positive.");  // [O3D]
+  if (nb_neighbors > 128) return fail(h, O3DS_ERR_INVALID_ARG, "remove_statistical_outliers: nb_neighbors > 128 unsupported");
+  return outlier_filter(h, in, 0, nb_neighbors, std_ratio, "remove_statistical_outliers", out, kept_idx, capacity, n_kept);
+}
+
+int o3ds_remove_radius_outliers(o3ds_handle h, o3ds_cloud in, int nb_points, double radius, o3ds_cloud* out, uint32_t* kept_idx, size_t capacity,
+                                size_t* n_kept) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (nb_points < 1 || !(radius > 0.0))
+    return fail(h, O3DS_ERR_INVALID_ARG, "[RemoveRadiusOutliers] Illegal input parameters, number of points and radius must be positive.");  // [O3D]
+  return outlier_filter(h, in, 1, nb_points, radius, "remove_radius_outliers", out, kept_idx, capacity, n_kept);
 }
 
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add) {

@@ -1,0 +1,71 @@
+"""Neighbour queries and outlier filters on device clouds: what callers of the reference reach for next to every cloud operation --
+[O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid, PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers -- and
+o3d_slam::computePointCloudDistance (helpers.hpp:29, helpers.cpp:185-218).  Same names; the search runs in the HIP kernel behind
+o3ds_neighbor_search on the target's grid index, no k-d tree is built and no cloud is downloaded.
+
+Where Open3D's searches take one query point, these take a cloud of queries and answer all of them in one launch: row i of the result
+belongs to query i.  The result of a query is defined in include/o3ds_backend.h (the order (d2, index), strict radius, storage-type d2).
+The filters are offered, not switched on: nothing in the frame loop calls them."""
+from __future__ import annotations
+
+import numpy as np
+
+from .pointcloud import PointCloud
+
+
+def _check(queries: PointCloud, target: PointCloud):
+    if queries.be is not target.be:
+        raise ValueError("the query cloud and the target live on different handles")
+    return target.be
+
+
+def SearchKNN(target: PointCloud, queries: PointCloud, knn: int, T=None, query_idx=None):
+    """[O3D] KDTreeFlann::SearchKNN for every query: (indices (n, knn), distance2 (n, knn), count (n,)) -- the knn nearest points of
+    `target` in the order (distance2, index), count[i] of them valid (fewer than knn only if the target is smaller)."""
+    be = _check(queries, target)
+    idx, d2, count, _ = be.neighbor_search(queries.id, target.id, int(knn), 0.0, T, query_idx)
+    return idx, d2, count
+
+
+def SearchRadius(target: PointCloud, queries: PointCloud, radius: float, max_nn: int = 0, T=None, query_idx=None):
+    """[O3D] KDTreeFlann::SearchRadius for every query: (indices, distance2, count, total).  total[i] is the number of target points with
+    distance2 < radius^2 -- what SearchRadius returns.  The lists are capped at max_nn <= 128 places (nearest first); the default 0 only
+    counts, which is what the radius filter needs."""
+    be = _check(queries, target)
+    if not radius > 0.0:
+        raise ValueError("SearchRadius: radius must be > 0")
+    return be.neighbor_search(queries.id, target.id, int(max_nn), float(radius), T, query_idx)
+
+
+def SearchHybrid(target: PointCloud, queries: PointCloud, radius: float, max_nn: int, T=None, query_idx=None):
+    """[O3D] KDTreeFlann::SearchHybrid for every query: (indices (n, max_nn), distance2, count) -- at most max_nn points with
+    distance2 < radius^2, nearest first."""
+    be = _check(queries, target)
+    if not radius > 0.0 or int(max_nn) < 1:
+        raise ValueError("SearchHybrid: radius must be > 0 and max_nn >= 1")
+    idx, d2, count, _ = be.neighbor_search(queries.id, target.id, int(max_nn), float(radius), T, query_idx)
+    return idx, d2, count
+
+
+def RemoveStatisticalOutliers(cloud: PointCloud, nb_neighbors: int, std_ratio: float):
+    """[O3D] PointCloud::RemoveStatisticalOutliers: (the kept points as a new cloud -- normals and colours carried --, their indices)"""
+    cid, kept = cloud.be.remove_statistical_outliers(cloud.id, nb_neighbors, std_ratio)
+    return PointCloud(cloud.be, cid), kept
+
+
+def RemoveRadiusOutliers(cloud: PointCloud, nb_points: int, search_radius: float):
+    """[O3D] PointCloud::RemoveRadiusOutliers: (the kept points as a new cloud -- normals and colours carried --, their indices)"""
+    cid, kept = cloud.be.remove_radius_outliers(cloud.id, nb_points, search_radius)
+    return PointCloud(cloud.be, cid), kept
+
+
+def computePointCloudDistance(reference: PointCloud, cloud: PointCloud, idsInReference):
+    """helpers.cpp:185-218: for every id, the distance from reference.points_[id] to its nearest point of `cloud` (an unbounded 1-NN);
+    returns (distances, ids), entries dropped from both where nothing was found (an empty `cloud`, a non-finite point)."""
+    ids = np.asarray(idsInReference, dtype=np.int64).ravel()
+    if len(ids) == 0:
+        return np.zeros(0), np.zeros(0, dtype=np.int64)
+    be = _check(reference, cloud)
+    _, d2, count, _ = be.neighbor_search(reference.id, cloud.id, 1, 0.0, None, ids.astype(np.uint32))
+    found = count > 0
+    return np.sqrt(d2[found, 0]), ids[found]
