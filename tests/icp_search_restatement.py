@@ -17,7 +17,9 @@ clouds with a central void, queries outside the grid, thin and tiny targets, a r
 """
 from __future__ import annotations
 
+import functools
 import math
+import sys
 from typing import NamedTuple
 
 import numpy as np
@@ -302,7 +304,7 @@ def ulp32(x):
     return (np.nextafter(x, np.float32(np.inf)) - x).astype(np.float64)
 
 
-D2_F32_REL = 8.0 * 2.0 ** -24  # see tests/test_icp_search_exact_gpu.py
+D2_F32_REL = 8.0 * 2.0 ** -24  # see tests/icp_search_harness.py
 
 
 # ---- inputs -------------------------------------------------------------------------------------------------------------------------
@@ -664,3 +666,29 @@ def all_cases():
     out += [stage_case(v, c) for v in STAGE_VOIDS for c in STAGE_CELLS] + [stage_case(0.9, 0.25, r=0.5)]
     out += [outside_case()] + tiny_cases() + [far_radius_case()] + large_cases()
     return out
+
+
+# ---- the generalized cases by name, their brute-force matches and the DEFECT table: shared by tests/test_icp_search_restatement_cpu.py,
+# which proves them, and tests/test_icp_search_exact_gpu.py, which runs them on the device (computed once per process, left unchanged)
+rs = sys.modules[__name__]  # (the three helpers below name this module as their users do)
+GICP_CASES = gicp_cases()
+DEFECT = {}          # (case name, storage) -> rs.gicp_defect of the whole case, filled by defect()
+
+
+@functools.lru_cache(maxsize=None)
+def _gicp_case(name):
+    return {c.name: c for c in GICP_CASES}[name]
+
+
+@functools.lru_cache(maxsize=None)
+def gicp_matches(name, storage):
+    c = _gicp_case(name)
+    return rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
+
+
+def defect(name, storage) -> float:
+    """DEFECT[name, storage], computed on first use"""
+    if (name, storage) not in DEFECT:
+        c = _gicp_case(name)
+        DEFECT[name, storage] = rs.gicp_defect(c.nrm, c.src_nrm, gicp_matches(name, storage).idx, c.T, c.eps, storage)
+    return DEFECT[name, storage]

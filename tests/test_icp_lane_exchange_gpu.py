@@ -4,7 +4,7 @@ PARENT commit's library: tests/golden/icp_lane_exchange_parent.npz (the commit i
 
 What is held:
   * quad, quad-radius, wave -- per query, both storages, row search and replica, point-to-plane: match or none and the float bits of d2
-    as the brute force says (the lattice inputs are exact), the pass record within the bound of tests/test_icp_search_exact_gpu.py,
+    as the brute force says (the lattice inputs are exact), the pass record within the bound of tests/icp_search_harness.py,
     and in every island with a tie the record of that query alone against the record each tied point would give (the winner's normal
     names the original index where d2 cannot).  Which lane scanned a winner is read back from its position: the premise that the wave
     case's winners fell on every one of the 64 lanes is asserted, the quad case's lanes are asserted to be all four;
@@ -38,6 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # (run as a script to record: the package)
 import icp_lane_exchange_cases as lc  # noqa: E402
 import icp_scan_loop_cases as sc  # noqa: E402
+import icp_search_harness as harness  # noqa: E402
 import icp_search_restatement as rs  # noqa: E402
 
 from open3d_slam_amd import backend  # noqa: E402
@@ -45,41 +46,24 @@ from open3d_slam_amd import backend  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "icp_lane_exchange_parent.npz")
-PATHS = ("rows", "replica")
-PREC = {rs.F32: backend.PRECISION_F32, rs.F64: backend.PRECISION_F64}
+PATHS, PREC = harness.PATHS, harness.PREC
 FIXED = dict(rel_fitness=0.0, rel_rmse=0.0)
 END_ITERS = 3
 
 
-@pytest.fixture(scope="module")
-def ex():
-    import test_icp_search_exact_gpu as ex_  # Session, _check_keys, _check_record: the checks of the search tests, unchanged
-
-    return ex_
-
-
 @pytest.fixture(autouse=True)
 def _eager_replica(monkeypatch):
-    monkeypatch.setenv("O3DS_NN_REPLICA_AFTER", "1")
-    monkeypatch.setenv("O3DS_NN_REPLICA", "1")
-    for v in ("O3DS_DEBUG_ACC", "O3DS_ICP_SETS", "O3DS_NO_SCAN_SLACK", "O3DS_SCAN_SPACE_BYTES"):
-        monkeypatch.delenv(v, raising=False)
+    harness.eager_replica(monkeypatch, replica="replica", clear=("O3DS_DEBUG_ACC", "O3DS_ICP_SETS", "O3DS_NO_SCAN_SLACK", "O3DS_SCAN_SPACE_BYTES"))
 
 
 @pytest.fixture(scope="module")
 def ab():
-    bes = {s: backend.Backend(0, p, ab=True) for s, p in PREC.items()}
-    yield bes
-    for be in bes.values():
-        be.close()
+    yield from harness.backends(True)
 
 
 @pytest.fixture(scope="module")
 def shipped():
-    bes = {s: backend.Backend(0, p) for s, p in PREC.items()}
-    yield bes
-    for be in bes.values():
-        be.close()
+    yield from harness.backends(False)
 
 
 @pytest.fixture(scope="module")
@@ -135,20 +119,20 @@ def _lanes(keys, c, owner, islands, width, start_of):
 
 @pytest.mark.parametrize("storage", rs.STORAGES)
 @pytest.mark.parametrize("name", list(lc.builders()))
-def test_lane_exchange_per_query(ex, ab, monkeypatch, name, storage):
+def test_lane_exchange_per_query(ab, monkeypatch, name, storage):
     c, owner, want = _built(name)
     m = _ref(name, storage)
     assert np.array_equal(m.idx, lc.winners(c, owner, want)), "premise (tests/test_icp_lane_exchange_cpu.py): the brute force's winners"
     n_src = len(c.src)
-    ses = ex.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
+    ses = harness.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
     try:
         for path in PATHS:
             what = f"{name} {storage} {path}"
-            ex._path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(c.T, path)
             keys = ses.keys(rank=3)
-            ex._check_keys(keys, m, storage, True, 3, len(c.tgt), 0, n_src, what)
-            ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, what)
+            harness.check_keys(keys, m, storage, True, 3, len(c.tgt), 0, n_src, what)
+            harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, what)
             n_ties = _check_tie_winners(ses, c, m, owner, storage, what)
             ses.be.icp_finish()
             if name == "quad":
@@ -202,33 +186,25 @@ def test_lane_exchange_in_the_crop_generalized_multi_target_kernel(shipped, name
 
 
 # ---- the end of the array ---------------------------------------------------------------------------------------------------------------
-def _open_end(ex_, be, c, stale):
-    """the stale cloud is uploaded, indexed, registered against once (which builds its replica) and freed, so that the pool holds its
-    blocks when the target asks for its own (tests/test_icp_scan_loop_cpu.py: same pool class)"""
-    pre = ex_.Session(be, c.src, stale, rs.unit_normals(np.random.default_rng(1), len(stale)), c.r, c.cell)
-    pre.begin(c.T, "replica")
-    pre.keys()
-    pre.be.icp_finish()
-    pre.close()
-    return ex_.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
+def _open_end(be, c, stale):
+    """the target behind the stale cloud (harness.open_behind_stale, whose session ends with icp_finish before it is closed: the calls the
+    parent's record was made with)"""
+    return harness.open_behind_stale(be, c, stale, finish=True)
 
 
 def _end_registrations(storage):
     """{case|storage|path: (floats, ints)} of the array-end cases of a storage, on a handle of its own"""
-    import test_icp_scan_loop_gpu as loop_
-    import test_icp_search_exact_gpu as ex_
-
     os.environ["O3DS_NN_REPLICA_AFTER"] = "1"
     out = {}
     be = backend.Backend(0, PREC[storage], ab=True)
     try:
         for n_last in lc.END_LENGTHS:
             c, stale = lc.array_end_case(n_last)
-            ses = _open_end(ex_, be, c, stale)
+            ses = _open_end(be, c, stale)
             for path in PATHS:
-                loop_._set_path(path)
+                harness.set_path(path)
                 ses.begin(c.T, path)
-                out[f"{c.name}|{storage}|{path}"] = loop_._pack(be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, max_iter=END_ITERS, **FIXED))
+                out[f"{c.name}|{storage}|{path}"] = harness.pack(be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, max_iter=END_ITERS, **FIXED))
             ses.close()
     finally:
         be.close()
@@ -236,37 +212,23 @@ def _end_registrations(storage):
 
 
 def _end_child(storage):
-    import json
-    import subprocess
-
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r); import torch; import test_icp_lane_exchange_gpu as t; "
-            "print(json.dumps({k: [f.view('u8').tolist(), i.tolist()] for k, (f, i) in t._end_registrations(%r).items()}))"
-            % (os.path.dirname(here), here, storage))
-    env = dict(os.environ, O3DS_ICP_STATS="1")
-    for v in ("O3DS_ICP_SETS", "O3DS_DEBUG_ACC", "O3DS_NO_SCAN_SLACK"):
-        env.pop(v, None)
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lines = [ln.strip() for ln in p.stderr.splitlines() if ln.startswith("icp stats")]
-    res = {k: (np.array(f, np.uint64).view(np.float64), np.array(i, np.int64)) for k, (f, i) in json.loads(p.stdout.strip().splitlines()[-1]).items()}
-    return res, lines
+    return harness.child_with_stats("test_icp_lane_exchange_gpu", f"t._end_registrations({storage!r})", unset=("O3DS_ICP_SETS", "O3DS_DEBUG_ACC", "O3DS_NO_SCAN_SLACK"))
 
 
 @pytest.mark.parametrize("storage", rs.STORAGES)
-def test_array_end_per_query(ex, ab, monkeypatch, storage):
+def test_array_end_per_query(ab, monkeypatch, storage):
     for n_last in lc.END_LENGTHS:
         c, stale = lc.array_end_case(n_last)
         m = rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
-        ses = _open_end(ex, ab[storage], c, stale)
+        ses = _open_end(ab[storage], c, stale)
         try:
             for path in PATHS:
                 what = f"{c.name} {storage} {path}"
-                ex._path(monkeypatch, path)
+                harness.set_path(path, monkeypatch)
                 ses.begin(c.T, path)
                 # (the corner queries: the d2 bound is relative, and the fill queries stand AT their match -- the record counts those)
-                ex._check_keys(ses.keys(0, 64, 3), m, storage, False, 3, len(c.tgt), 0, 64, what)
-                ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(c.src), what)
+                harness.check_keys(ses.keys(0, 64, 3), m, storage, False, 3, len(c.tgt), 0, 64, what)
+                harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(c.src), what)
                 ses.be.icp_finish()
         finally:
             ses.close()
@@ -286,10 +248,11 @@ def test_array_end_lists_and_registrations_equal_the_parents(golden, storage):
         c = lc.array_end_case(n_last)[0]
         m = rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
         assert i.tolist() == [END_ITERS, int((m.idx >= 0).sum())], (k, i)
-        passes = [dict((t[0], int(t[1:])) for t in p.replace("]", "").split()[1:]) for p in ln.split("[")[1:]]
+        passes = harness.parse_stats(ln)
         assert passes[1]["k"] > 0, f"{k}: premise: pass 1 lists candidates: {ln}"
         g = want[k]
-        assert np.array_equal(i, golden["end_ints"][g]) and np.array_equal(f.view(np.uint64), golden["end_floats"][g].view(np.uint64)), (k, f, i)
+        assert np.array_equal(i, golden["end_ints"][g]), (k, i)
+        harness.assert_bits(f, golden["end_floats"][g], k)
         assert ln == str(golden["end_stats"][g]), (k, ln, str(golden["end_stats"][g]))
 
 
@@ -297,7 +260,7 @@ PM_STALE = 4_600_000  # points of the cloud whose cell-sorted array leaves the b
 
 
 @pytest.mark.parametrize("storage", rs.STORAGES)
-def test_a_persistent_map_whose_pool_takes_a_block_full_of_nearer_points(ex, ab, storage):
+def test_a_persistent_map_whose_pool_takes_a_block_full_of_nearer_points(ab, storage):
     """tests/test_icp_search_exact_gpu.py::test_persistent_map_target in a reused block.  Every range of a row-paged index is followed by
     page slots no point was written to, and the scan loop now loads them: a cloud of PM_STALE points around the queries, nearer to each
     than any map point, is uploaded, indexed and freed first, and its cell-sorted array is of the block class the pool asks for (asserted
@@ -320,7 +283,7 @@ def test_a_persistent_map_whose_pool_takes_a_block_full_of_nearer_points(ex, ab,
     crop = backend.make_crop(backend.CROP_MAX_RADIUS, center=tuple(rs.VOID_CENTRE), rmax=2.5)
     mp = be.upload(np.zeros((0, 3)))
     scans = [be.upload(tgt[:10_000]), be.upload(tgt[10_000:])]
-    ses = ex.Session(be, src, None, None, 1.0, None, target_id=mp)
+    ses = harness.Session(be, src, None, None, 1.0, None, target_id=mp)
     try:
         for s_ in scans:
             be.map_insert_scan(mp, s_, np.eye(4), 0.1, crop, max_corr_hint=1.0)
@@ -333,9 +296,9 @@ def test_a_persistent_map_whose_pool_takes_a_block_full_of_nearer_points(ex, ab,
         m = rs.nearest_within(src, pts, np.eye(4), 1.0, storage)
         assert (near.d2 < m.d2).all(), "premise: a stale point is nearer to every query than any map point"
         what = f"persistent map in a reused block {storage}"
-        ex._premises(m, 1.0, what)
-        ex._check_keys(keys, m, storage, False, 2, None, 0, len(src), what)
-        ex._check_record(rec, m, pts, None, storage, backend.ICP_POINT_TO_POINT, 0, len(src), what)
+        harness.premises(m, 1.0, what)
+        harness.check_keys(keys, m, storage, False, 2, None, 0, len(src), what)
+        harness.check_record(rec, m, pts, None, storage, backend.ICP_POINT_TO_POINT, 0, len(src), what)
         be.icp_finish()
     finally:
         for s_ in scans:
@@ -349,7 +312,7 @@ def _refused(ses, T, path=None, method=backend.ICP_POINT_TO_PLANE):
     assert "kScanSlackBytes" in str(e.value), str(e.value)
 
 
-def test_a_target_without_the_slack_is_refused(ex, ab, monkeypatch):
+def test_a_target_without_the_slack_is_refused(ab, monkeypatch):
     """O3DS_NO_SCAN_SLACK (A/B library, read when an index array is allocated) allocates the cell-sorted points, the replica and a
     persistent map's pool as a caller unaware of the scan loop would: icp_begin refuses each such target, and says why, before it runs
     anything against it"""
@@ -357,13 +320,13 @@ def test_a_target_without_the_slack_is_refused(ex, ab, monkeypatch):
     be = ab[rs.F32]
     # ---- the cell-sorted points
     monkeypatch.setenv("O3DS_NO_SCAN_SLACK", "1")
-    ses = ex.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
+    ses = harness.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
     monkeypatch.delenv("O3DS_NO_SCAN_SLACK")
     try:
         _refused(ses, c.T)
         be.build_index(ses.t, c.r, c.cell)  # rebuilt as the library does it: accepted
         ses.begin(c.T)
-        ex._check_keys(ses.keys(rank=1), _ref("quad-radius", rs.F32), rs.F32, True, 1, len(c.tgt), 0, len(c.src), "rebuilt with the slack")
+        harness.check_keys(ses.keys(rank=1), _ref("quad-radius", rs.F32), rs.F32, True, 1, len(c.tgt), 0, len(c.src), "rebuilt with the slack")
         be.icp_finish()
         # ---- the replica alone: the index has its slack, the replica built at this registration (O3DS_NN_REPLICA_AFTER=1) has none
         be.build_index(ses.t, c.r, c.cell)
@@ -380,7 +343,7 @@ def test_a_target_without_the_slack_is_refused(ex, ab, monkeypatch):
     crop = backend.make_crop(backend.CROP_MAX_RADIUS, center=tuple(rs.VOID_CENTRE), rmax=2.5)
     mp = be.upload(np.zeros((0, 3)))
     scans = [be.upload(tgt[:10_000]), be.upload(tgt[10_000:])]
-    ses = ex.Session(be, c.src, None, None, 1.0, None, target_id=mp)
+    ses = harness.Session(be, c.src, None, None, 1.0, None, target_id=mp)
     try:
         monkeypatch.setenv("O3DS_NO_SCAN_SLACK", "1")
         for s_ in scans:
@@ -441,8 +404,6 @@ def _order_run(be, n_src):
     """(fused floats, fused ints, step-wise floats, step-wise ints, records [ORDER_ITERS + 1][32]) of one source size on a handle"""
     import torch
 
-    import test_icp_scan_loop_gpu as loop_
-
     src, tgt, nrm, T0 = lc.order_inputs(n_src)
     s, t = be.upload(src), be.upload(tgt, nrm)
     rec = torch.zeros(32, dtype=torch.float64, device="cuda:0")
@@ -450,7 +411,7 @@ def _order_run(be, n_src):
     try:
         be.build_index(t, 1.0, 0.25)
         kw = dict(init=T0, max_iter=lc.ORDER_ITERS, method=backend.ICP_POINT_TO_POINT, **FIXED)
-        ff, fi = loop_._pack(be.icp_register_dev(s, t, 1.0, **kw))
+        ff, fi = harness.pack(be.icp_register_dev(s, t, 1.0, **kw))
         be.icp_begin(s, t, 1.0, **kw)
         recs = []
         for _ in range(lc.ORDER_ITERS + 1):
@@ -460,7 +421,7 @@ def _order_run(be, n_src):
             be.icp_update(rec.data_ptr(), n_src)
             if be.icp_done():
                 break
-        sf, si = loop_._pack(be.icp_finish())
+        sf, si = harness.pack(be.icp_finish())
     finally:
         be.free(s)
         be.free(t)
@@ -477,7 +438,7 @@ def test_query_order_is_the_parents(shipped, golden, n_src, storage):
     assert fi[0] == lc.ORDER_ITERS and (ff[:16] != rs.LATER_INIT.reshape(16)).any() and fi[1] > 0, "premise: two updates were taken, and they landed"
     for what, a, b in (("fused result", ff, golden["order_fused_floats"][g]), ("step-wise result", sf, golden["order_step_floats"][g]),
                        ("step-wise records", recs, golden["order_records"][g])):
-        assert np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64)), (what, n_src, storage, a, b)
+        harness.assert_bits(a, b, (what, n_src, storage))
     assert np.array_equal(fi, golden["order_fused_ints"][g]) and np.array_equal(si, golden["order_step_ints"][g])
     assert np.array_equal(ff.view(np.uint64), sf.view(np.uint64)) and np.array_equal(fi, si), "the fused form and the step-wise form differ"
 

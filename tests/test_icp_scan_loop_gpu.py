@@ -14,7 +14,7 @@ What is held, per case, in the storages the case names, row search and replica:
     After each, icp_finish must report one iteration and the pose meant (the premise that the update was taken), and the keys must be
     those of the first pass.  That a pass above zero READS the cache, and that the cache holds the last search's positions, is shown
     once, by a search that cannot find the matches itself (test_a_search_after_an_update_starts_from_the_cached_matches);
-  * the pass record over all queries within the bound of tests/test_icp_search_exact_gpu.py, and in the tie case the record of each query
+  * the pass record over all queries within the bound of tests/icp_search_harness.py, and in the tie case the record of each query
     alone against the record each of its tied points would give: the winner's normal enters every term, which names the original index
     where d2 cannot -- under every one of the bounds above;
   * the bound formed from the candidate sets exists in the fused kernel only, which computes its own updates: radius_still_case is a
@@ -29,9 +29,7 @@ target point (tests/test_icp_scan_loop_cpu.py: same pool class, stale points nea
 Recording (parent commit's library only):
     O3DS_BACKEND_LIB=<A/B library built from the parent commit> python tests/test_icp_scan_loop_gpu.py --record FILE"""
 import functools
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -40,6 +38,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # (run as a script to record: the package)
 import icp_scan_loop_cases as sc  # noqa: E402
+import icp_search_harness as harness  # noqa: E402
 import icp_search_restatement as rs  # noqa: E402
 
 from open3d_slam_amd import backend  # noqa: E402
@@ -47,9 +46,9 @@ from open3d_slam_amd import backend  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "icp_scan_loop_parent.npz")
-PATHS = ("rows", "replica")
+PATHS = harness.PATHS
 FIXED = dict(max_iter=3, rel_fitness=0.0, rel_rmse=0.0)
-PREC = {rs.F32: backend.PRECISION_F32, rs.F64: backend.PRECISION_F64}
+PREC = harness.PREC
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,31 +66,16 @@ def _ids():
     return [(c.name, s) for c in sc.all_cases() for s in c.storages]
 
 
-def _pack(r):
-    f = np.concatenate([np.ascontiguousarray(r["transformation"], np.float64).reshape(16), [r["fitness"], r["inlier_rmse"]]])
-    return f.astype(np.float64), np.array([r["iterations"], r["n_corr"]], np.int64)
-
-
-def _open(ex_, be, c):
-    """the session of a case on a handle.  array-end: first a larger cloud around the queries is uploaded, indexed, registered against
-    once (which builds its replica) and freed, so that the pool holds its blocks when the target asks for its own"""
+def _open(be, c):
+    """the session of a case on a handle.  array-end: behind a larger cloud around the queries (harness.open_behind_stale, whose session is
+    closed without an icp_finish: the calls the parent's record was made with)"""
     if c.name == "array-end":
-        stale = sc.array_end_case()[1]
-        pre = ex_.Session(be, c.src, stale, rs.unit_normals(np.random.default_rng(1), len(stale)), c.r, c.cell)
-        pre.begin(c.T, "replica")
-        pre.keys()
-        pre.close()
-    return ex_.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
-
-
-def _set_path(path):
-    os.environ["O3DS_NN_REPLICA"] = "1" if path == "replica" else "0"
+        return harness.open_behind_stale(be, c, sc.array_end_case()[1], finish=False)
+    return harness.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
 
 
 def _registrations(storage):
     """{case|storage|path: (floats, ints)} of every case of a storage, in the order of sc.all_cases() x PATHS, on a handle of its own"""
-    import test_icp_search_exact_gpu as ex_
-
     os.environ["O3DS_NN_REPLICA_AFTER"] = "1"
     out = {}
     be = backend.Backend(0, PREC[storage], ab=True)
@@ -99,11 +83,11 @@ def _registrations(storage):
         for c in sc.all_cases():
             if storage not in c.storages:
                 continue
-            ses = _open(ex_, be, c)
+            ses = _open(be, c)
             for path in PATHS:
-                _set_path(path)
+                harness.set_path(path)
                 ses.begin(c.T, path)
-                out[f"{c.name}|{storage}|{path}"] = _pack(ses.be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED))
+                out[f"{c.name}|{storage}|{path}"] = harness.pack(ses.be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED))
             ses.close()
     finally:
         be.close()
@@ -113,47 +97,22 @@ def _registrations(storage):
 def _child(call):
     """a call of this module that returns registrations, such as "_registrations('f32')", in a child process with O3DS_ICP_STATS=1
     (looked at once per process): (results, the stats lines in order)"""
-    code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r); import torch; import test_icp_scan_loop_gpu as t; "
-            "print(json.dumps({k: [f.view('u8').tolist(), i.tolist()] for k, (f, i) in t.%s.items()}))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), call))
-    env = dict(os.environ, O3DS_ICP_STATS="1")
-    env.pop("O3DS_ICP_SETS", None)
-    env.pop("O3DS_DEBUG_ACC", None)
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lines = [ln.strip() for ln in p.stderr.splitlines() if ln.startswith("icp stats")]
-    res = {k: (np.array(f, np.uint64).view(np.float64), np.array(i, np.int64)) for k, (f, i) in json.loads(p.stdout.strip().splitlines()[-1]).items()}
-    return res, lines
-
-
-@pytest.fixture(scope="module")
-def ex():
-    import test_icp_search_exact_gpu as ex_  # Session, _check_keys, _check_record: the checks of the search tests, unchanged
-
-    return ex_
+    return harness.child_with_stats("test_icp_scan_loop_gpu", f"t.{call}", unset=("O3DS_ICP_SETS", "O3DS_DEBUG_ACC"))
 
 
 @pytest.fixture(autouse=True)
 def _eager_replica(monkeypatch):
-    monkeypatch.setenv("O3DS_NN_REPLICA_AFTER", "1")
-    monkeypatch.setenv("O3DS_NN_REPLICA", "1")
-    monkeypatch.delenv("O3DS_DEBUG_ACC", raising=False)
-    monkeypatch.delenv("O3DS_ICP_SETS", raising=False)
+    harness.eager_replica(monkeypatch, replica="replica", clear=("O3DS_DEBUG_ACC", "O3DS_ICP_SETS"))
 
 
 @pytest.fixture(scope="module")
 def ab():
-    bes = {s: backend.Backend(0, p, ab=True) for s, p in PREC.items()}
-    yield bes
-    for be in bes.values():
-        be.close()
+    yield from harness.backends(True)
 
 
 @pytest.fixture(scope="module")
 def golden():
-    g = np.load(GOLDEN)
-    return ({str(n): (g["floats"][k], g["ints"][k]) for k, n in enumerate(g["names"])},
-            {str(s): [str(x) for x in g[f"stats_{s}"]] for s in rs.STORAGES})
+    return harness.load_parent_record(GOLDEN)
 
 
 def _golden_names():
@@ -213,28 +172,28 @@ def _ref_start(name, storage, start):
 
 
 @pytest.mark.parametrize("name,storage", _ids())
-def test_scan_loop_per_query_and_the_parents_registration(ex, ab, golden, monkeypatch, name, storage):
+def test_scan_loop_per_query_and_the_parents_registration(ab, golden, monkeypatch, name, storage):
     import torch
 
     c, m = _cases()[name], _ref(name, storage)
     n_src = len(c.src)
-    ses = _open(ex, ab[storage], c)
+    ses = _open(ab[storage], c)
     try:
         for path in PATHS:
             what = f"{name} {storage} {path}"
-            ex._path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(c.T, path)
             first = ses.keys(rank=3)
-            ex._check_keys(first, m, storage, c.exact, 3, len(c.tgt), 0, n_src, f"{what} first search")
-            ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, f"{what} first pass")
+            harness.check_keys(first, m, storage, c.exact, 3, len(c.tgt), 0, n_src, f"{what} first search")
+            harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, f"{what} first pass")
             if name == "ties":
                 _check_tie_winners(ses, c, m, storage, f"{what} first pass")
             # ---- pass 1 at the same pose: every query starts from what the first search cached for it, its match or `none`
             _update(ses, sc.ZERO_RECORD)
             again = ses.keys(rank=3)
-            ex._check_keys(again, m, storage, c.exact, 3, len(c.tgt), 0, n_src, f"{what} from its own cached matches")
+            harness.check_keys(again, m, storage, c.exact, 3, len(c.tgt), 0, n_src, f"{what} from its own cached matches")
             assert torch.equal(first, again), f"{what}: the search from the cached bound finds other keys"
-            ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, f"{what} from its own cached matches")
+            harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, f"{what} from its own cached matches")
             if name == "ties":
                 _check_tie_winners(ses, c, m, storage, f"{what} from its own cached matches")
             _finish_after_one_update(ses, c.T, what)
@@ -243,28 +202,28 @@ def test_scan_loop_per_query_and_the_parents_registration(ex, ab, golden, monkey
                 ms, at = _ref_start(name, storage, start), f"{what} start `{start}`"
                 assert (c.T == np.eye(4)).all() and ((ms.idx != m.idx).any() if start == "stale" else (ms.idx == -1).all()), at
                 ses.begin(sc.translation(sc.STARTS[start]), path)
-                ex._check_keys(ses.keys(rank=3), ms, storage, True, 3, len(c.tgt), 0, n_src, f"{at}, first search")
+                harness.check_keys(ses.keys(rank=3), ms, storage, True, 3, len(c.tgt), 0, n_src, f"{at}, first search")
                 _update(ses, sc.step_back_record(sc.STARTS[start]))
                 back = ses.keys(rank=3)
-                ex._check_keys(back, m, storage, True, 3, len(c.tgt), 0, n_src, f"{at}, back at the identity")
+                harness.check_keys(back, m, storage, True, 3, len(c.tgt), 0, n_src, f"{at}, back at the identity")
                 assert torch.equal(first, back), f"{at}: the search from this bound finds other keys"
-                ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, at)
+                harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, n_src, at)
                 if name == "ties":
                     _check_tie_winners(ses, c, m, storage, at)
                 _finish_after_one_update(ses, np.eye(4), at)
             ses.begin(c.T, path)
             got = ses.be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED)
             print(f"SCAN {what}: iterations {got['iterations']} n_corr {got['n_corr']} fitness {got['fitness']} rmse {got['inlier_rmse']}")
-            f, i = _pack(got)
+            f, i = harness.pack(got)
             gf, gi = golden[0][f"{name}|{storage}|{path}"]
             assert np.array_equal(i, gi), (what, i, gi)
-            assert np.array_equal(f.view(np.uint64), gf.view(np.uint64)), (what, f, gf)
+            harness.assert_bits(f, gf, what)
     finally:
         ses.close()
 
 
 @pytest.mark.parametrize("storage", rs.STORAGES)
-def test_a_search_after_an_update_starts_from_the_cached_matches(ex, ab, monkeypatch, storage):
+def test_a_search_after_an_update_starts_from_the_cached_matches(ab, monkeypatch, storage):
     """The premise of the later-pass checks above, shown by a search that cannot find the matches itself.  O3DS_DEBUG_ACC=16 (A/B
     library, read when a session begins) skips stage 3, and every match of the half-rows case lies three rows away: a first pass finds
     none.  After a full search of an ordinary session on the same handle (the handle's match cache outlives a session), a session with
@@ -274,14 +233,14 @@ def test_a_search_after_an_update_starts_from_the_cached_matches(ex, ab, monkeyp
 
     c, m = _cases()["half-rows"], _ref("half-rows", storage)
     n_src = len(c.src)
-    ses = _open(ex, ab[storage], c)
+    ses = _open(ab[storage], c)
     try:
         for path in PATHS:
             what = f"cache premise {storage} {path}"
-            ex._path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(c.T, path)
             full = ses.keys(rank=3)
-            ex._check_keys(full, m, storage, True, 3, len(c.tgt), 0, n_src, what)
+            harness.check_keys(full, m, storage, True, 3, len(c.tgt), 0, n_src, what)
             assert (m.idx >= 0).all()
             ses.be.icp_finish()
             monkeypatch.setenv("O3DS_DEBUG_ACC", "16")
@@ -301,19 +260,17 @@ def test_a_search_after_an_update_starts_from_the_cached_matches(ex, ab, monkeyp
 
 def _still_registrations():
     """{case|path: (floats, ints)} of the fused kernel's radius cases (both storages), each on a handle of its own"""
-    import test_icp_search_exact_gpu as ex_
-
     os.environ["O3DS_NN_REPLICA_AFTER"] = "1"
     out = {}
     for storage in rs.STORAGES:
         c = sc.radius_still_case(storage)[0]
         be = backend.Backend(0, PREC[storage], ab=True)
         try:
-            ses = ex_.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
+            ses = harness.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
             for path in PATHS:
-                _set_path(path)
+                harness.set_path(path)
                 ses.begin(c.T, path)
-                out[f"{c.name}|{path}"] = _pack(be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED))
+                out[f"{c.name}|{path}"] = harness.pack(be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED))
             ses.close()
         finally:
             be.close()
@@ -334,7 +291,7 @@ def test_the_radius_under_a_bound_from_the_candidate_sets():
         c = sc.radius_still_case(storage)[0]
         m = rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
         n = len(c.src)
-        passes = [dict((t[0], int(t[1:])) for t in p.replace("]", "").split()[1:]) for p in ln.split("[")[1:]]
+        passes = harness.parse_stats(ln)
         assert len(passes) >= 4 and passes[0]["k"] == 0 and passes[1]["k"] == n, f"{k}: premise: pass 1 leaves a candidate set per query: {ln}"
         assert all(p["v"] + p["s"] == n for p in passes[:4]), ln
         assert np.array_equal(f[:16].reshape(4, 4), np.eye(4)), f"{k}: premise: the pose moved\n{f[:16].reshape(4, 4)}"
@@ -355,7 +312,8 @@ def test_counters_and_registrations_of_a_fresh_process_equal_the_parents(golden,
     assert names == [f"{c.name}|{storage}|{p}" for c in sc.all_cases() if storage in c.storages for p in PATHS]
     for k, (f, i) in res.items():
         gf, gi = golden[0][k]
-        assert np.array_equal(i, gi) and np.array_equal(f.view(np.uint64), gf.view(np.uint64)), (k, f, gf, i, gi)
+        assert np.array_equal(i, gi), (k, i, gi)
+        harness.assert_bits(f, gf, k)
     # (the array-end case's preparation registers nothing through the fused kernel: one line per registration above)
     assert lines == golden[1][storage], [(a, b) for a, b in zip(lines, golden[1][storage]) if a != b]
     assert any(" k" in ln and any(int(t[1:]) > 0 for t in ln.replace("]", "").split() if t.startswith("k")) for ln in lines), \

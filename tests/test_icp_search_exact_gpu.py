@@ -6,22 +6,8 @@ sets of the fused kernel).  Here its per-query observable -- o3ds_icp_nn_keys: f
 step record of the same session state are held against tests/icp_search_restatement.py, whose agreement with the oracle
 tests/test_icp_search_restatement_cpu.py proves without a GPU.  Row search and replica, f32 and f64 storage.
 
-Bounds (derived, not measured; every test prints the largest observed ratio before it asserts):
-  * exact cases (coordinates small integers times a power of two, pose the identity or an exact translation): every operation is exact
-    in both storages, the float bits of d2 are equal.
-  * f32 storage, seeded clouds: |d2_dev - d2_ref| <= 8 * 2^-24 * d2_ref.  dist2 is fmaf(dz, dz, fmaf(dy, dy, dx * dx)): the three
-    differences are each within 2^-24 relative of the exact ones (one rounding; exact when the operands are within a factor of two), so
-    each SQUARE is within (1 + 2^-24)^2 - 1 < 2.0001 * 2^-24; the product dx * dx and the two fused steps add one rounding each, and as
-    all terms are non-negative a relative error of the terms is a relative error of the sum: 2 + 3 = 5 units of 2^-24 to first order,
-    under 8 with every higher-order term.  The reference forms d2 in f64 from the same stored coordinates (error 2^-52, nothing).
-  * f64 storage: float(d2_ref) within one float ulp of the key's float -- the device's d2 differs from the reference's by a few f64 ulps
-    (its own three products and two sums, and the f64 rounding of p = T s, whose multiply-adds the compiler may fuse), so the double-to-
-    float cast is the only rounding that can differ, and only by landing on the other side of a rounding boundary.
-  * records: |term_dev - term_ref| <= 1e-12 * sum |addends| per term: an addend carries at most about eight f64 roundings (1e-15), the
-    workgroup sums add n * 2^-53, the sums across workgroups are exact by design; three orders of margin.  In f32 storage terms [27]
-    and [29] take the d2 bound above instead.
-The key cannot show WHICH of several equidistant points won; the record can (duplicated target points carry different normals), and it
-pins the position -> point -> normal gather with it.
+The checks and the derivation of their bounds are in tests/icp_search_harness.py (check_keys, check_record, check_record_gicp); every
+test prints the largest observed ratio before it asserts.
 
 The generalized estimator's record (write_record<P4, true>, gicp_record, the 32-slot LDS stride and its zeroing, the source-normal gather
 at a.first + i under all three dealing orders) is held per term to rs.record_gicp twice: to the closed form the device documents
@@ -51,7 +37,6 @@ unit to 6e-8 only).  scale is the restatement's: sum over the pairs of |B|_2 tim
   9.3e3 / 5.5e11 (source side) times the bound against Open3D's form.
 The fused kernel's generalized records are tied to the same restatement through the step-wise ABI: o3ds_icp_register_dev equals begin /
 accumulate / update / finish bit for bit, and the step-wise records are the ones checked here."""
-import contextlib
 import functools
 import os
 import sys
@@ -60,45 +45,29 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import icp_search_harness as harness  # noqa: E402
 import icp_search_restatement as rs  # noqa: E402
-import test_icp_search_restatement_cpu as cpu  # noqa: E402  (the generalized cases, their brute-force matches and the DEFECT table)
 
 from open3d_slam_amd import backend  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -0x0123456789ABCDEF
-PREC = {rs.F32: backend.PRECISION_F32, rs.F64: backend.PRECISION_F64}
-PATHS = ("rows", "replica")
-REC_TOL = 1e-12
-GAP_MIN, NEAR_R_MIN = 1e-5, 1e-6  # the premises of tests/test_icp_search_restatement_cpu.py, asserted here where the pose comes from the device
+PREC, PATHS, REC_TOL = harness.PREC, harness.PATHS, harness.REC_TOL
 
 
 @pytest.fixture(autouse=True)
 def _eager_replica(monkeypatch):
-    monkeypatch.setenv("O3DS_NN_REPLICA_AFTER", "1")
-    monkeypatch.delenv("O3DS_DEBUG_ACC", raising=False)
+    harness.eager_replica(monkeypatch)
 
 
 @pytest.fixture(scope="module")
 def ab():
-    """one handle of the A/B library per storage (the switches O3DS_NN_REPLICA, O3DS_NN_REPLICA_AFTER, O3DS_DEBUG_ACC exist only there)"""
-    bes = {s: backend.Backend(0, p, ab=True) for s, p in PREC.items()}
-    yield bes
-    for be in bes.values():
-        be.close()
+    yield from harness.backends(True)
 
 
 @pytest.fixture(scope="module")
 def shipped():
-    bes = {s: backend.Backend(0, p) for s, p in PREC.items()}
-    yield bes
-    for be in bes.values():
-        be.close()
-
-
-def _path(monkeypatch, path):
-    monkeypatch.setenv("O3DS_NN_REPLICA", "1" if path == "replica" else "0")
+    yield from harness.backends(False)
 
 
 @functools.lru_cache(maxsize=None)
@@ -112,158 +81,21 @@ def _ref(name, storage):
     return rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
 
 
-class Session:
-    """source and target of one case on a handle, its index built with the case's cell"""
-
-    def __init__(self, be, src, tgt, nrm, r, cell, target_id=None, src_nrm=None):
-        self.be, self.r, self.n = be, r, len(src)
-        self.s = be.upload(src, src_nrm)
-        self.t = be.upload(tgt, nrm) if target_id is None else target_id  # (a target the caller has built keeps the index it has)
-        if target_id is None:
-            be.build_index(self.t, r, cell)
-
-    def begin(self, T, path=None, crop=None, method=backend.ICP_POINT_TO_PLANE, max_iter=10):
-        self.be.icp_begin(self.s, self.t, self.r, init=T, max_iter=max_iter, rel_fitness=0.0, rel_rmse=0.0, target_crop=crop, method=method)
-        if path == "replica":
-            assert self.be.index_replica(self.t) > 0, "the target has no replica: this run would take the row search"
-
-    @contextlib.contextmanager
-    def eps(self, epsilon):
-        """the generalized estimator's epsilon for the sessions begun inside (the handles are shared by the module: always put back)"""
-        try:
-            self.be.set_gicp_epsilon(epsilon)
-            yield
-        finally:
-            self.be.set_gicp_epsilon(rs.GICP_EPSILON)
-
-    def keys(self, first=0, count=None, rank=0):
-        import torch
-
-        count = self.n - first if count is None else count
-        k = torch.full((max(self.n, 1),), SENTINEL, dtype=torch.int64, device="cuda:0")
-        torch.cuda.synchronize()
-        self.be.icp_nn_keys(first, count, rank, k.data_ptr())
-        self.be.synchronize()
-        return k
-
-    def record(self, first=0, count=None, keys=None, rank=0):
-        import torch
-
-        count = self.n - first if count is None else count
-        rec = torch.full((32,), 7.0, dtype=torch.float64, device="cuda:0")
-        torch.cuda.synchronize()
-        if keys is None:
-            self.be.icp_accumulate(first, count, rec.data_ptr())
-        else:
-            self.be.icp_accumulate_keys(first, count, rank, keys.data_ptr(), rec.data_ptr())
-        self.be.synchronize()
-        return rec
-
-    def close(self):
-        self.be.free(self.s)
-        self.be.free(self.t)
-
-
-def _check_keys(keys, m, storage, exact, rank, n_tgt, first, count, what):
-    """the keys of queries [first, first + count) against the brute-force matches m (of ALL queries); returns the largest d2 deviation
-    as a fraction of its bound"""
-    k = keys.cpu().numpy()[:len(m.idx)]
-    outside = np.ones(len(k), dtype=bool)
-    outside[first:first + count] = False
-    assert (k[outside] == SENTINEL).all(), f"{what}: keys outside the range were written"
-    sel = slice(first, first + count)
-    none, d2, rk, pos = rs.decode_keys(k[sel])
-    want_none = m.idx[sel] < 0
-    bad = np.flatnonzero(none != want_none)
-    assert bad.size == 0, f"{what}: {bad.size} of {count} queries differ in match / no match, first {first + bad[:8]}, reference d {np.sqrt(m.best[sel][bad[:8]])}"
-    hit = ~none
-    assert (rk[hit] == rank).all(), f"{what}: rank not echoed"
-    if n_tgt is not None:
-        assert (pos[hit] < n_tgt).all(), f"{what}: position beyond the target"
-    ref = m.d2[sel][hit]
-    dev = d2[hit].astype(np.float64)
-    if exact:
-        np.testing.assert_array_equal(d2[hit].view(np.uint32), ref.astype(np.float32).view(np.uint32), err_msg=f"{what}: float bits of d2")
-        return 0.0
-    if not hit.any():
-        return 0.0
-    if storage == rs.F32:
-        ratio = np.abs(dev - ref) / (rs.D2_F32_REL * ref)
-    else:
-        ratio = np.abs(dev - ref.astype(np.float32).astype(np.float64)) / rs.ulp32(ref)
-    worst = float(ratio.max())
-    print(f"SEARCH {what}: d2 deviation / bound {worst:.3f}")
-    assert worst <= 1.0, f"{what}: d2 off by {worst:.3f} x its bound at query {first + np.flatnonzero(hit)[ratio.argmax()]}"
-    return worst
-
-
-def _check_record(rec, m, tgt, nrm, storage, method, first, count, what):
-    got = rec.cpu().numpy()
-    idx = np.full_like(m.idx, -1)
-    idx[first:first + count] = m.idx[first:first + count]
-    ref, scale = rs.record(m.p, tgt, nrm, idx, storage, method)
-    tol = np.full(32, REC_TOL)
-    if storage == rs.F32:
-        tol[[27, 29]] = rs.D2_F32_REL
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(scale > 0, np.abs(got - ref) / (tol * scale), np.where(got == ref, 0.0, np.inf))
-    worst = float(ratio.max())
-    print(f"SEARCH {what}: record deviation / bound {worst:.3e} (term {int(ratio.argmax())}), {int(ref[28])} matches of {count}")
-    assert got[28] == ref[28], f"{what}: {got[28]} correspondences, brute force {ref[28]}"
-    assert worst <= 1.0, f"{what}: record term {int(ratio.argmax())} off by {worst:.3e} x its bound: {got[ratio.argmax()]} vs {ref[ratio.argmax()]}"
-    return worst
-
-
-def _check_record_gicp(rec, m, tgt, nrm, src_nrm, storage, T, eps, first, count, what, defect=None):
-    """the generalized record of queries [first, first + count) against both forms of the restatement; returns the largest deviation
-    as a fraction of its bound (of both comparisons).  defect: the DEFECT of a set of pairs that contains these (default: of these)."""
-    got = rec.cpu().numpy() if hasattr(rec, "cpu") else np.asarray(rec)
-    idx = np.full_like(m.idx, -1)
-    idx[first:first + count] = m.idx[first:first + count]
-    if defect is None:
-        defect = rs.gicp_defect(nrm, src_nrm, idx, T, eps, storage)
-    worst = 0.0
-    for form, extra in ((rs.FORM_O3D, 2.0 * defect), (rs.FORM_CLOSED, 0.0)):
-        ref, scale = rs.record_gicp(m.p, tgt, nrm, src_nrm, idx, T, eps, storage, form)
-        tol = np.full(32, REC_TOL + extra)
-        if storage == rs.F32:
-            tol[29] = rs.D2_F32_REL
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(scale > 0, np.abs(got - ref) / (tol * scale), np.where(got == ref, 0.0, np.inf))
-        w = float(ratio.max())
-        print(f"SEARCH {what}: generalized record against the {form} form, deviation / bound {w:.3e} (term {int(ratio.argmax())}), "
-              f"{int(ref[28])} matches of {count}, DEFECT {defect:.3e}")
-        assert got[28] == ref[28], f"{what}: {got[28]} correspondences, brute force {ref[28]}"
-        assert w <= 1.0, f"{what}: {form} form, record term {int(ratio.argmax())} off by {w:.3e} x its bound: {got[ratio.argmax()]} vs {ref[ratio.argmax()]}"
-        worst = max(worst, w)
-    return worst
-
-
-def _premises(m, r, what):
-    hit = m.idx >= 0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rel = m.gap[hit] / m.d2[hit]
-    assert rel.size == 0 or rel.min() >= GAP_MIN, f"{what}: premise: relative gap {rel.min():.3e}"
-    fin = np.isfinite(m.best)
-    near = np.abs(np.sqrt(m.best[fin]) - r) / r
-    assert near.size == 0 or near.min() >= NEAR_R_MIN, f"{what}: premise: |d - r| / r = {near.min():.3e}"
-
-
 def _run_case(ab, monkeypatch, name, storage, first=0, count=None, rank=3):
     c = _case(name)
     m = _ref(name, storage)
     count = len(c.src) - first if count is None else count
-    ses = Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
+    ses = harness.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
     try:
         for path in PATHS:
             what = f"{name} {storage} {path} [{first},{first + count})"
-            _path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             for method in (backend.ICP_POINT_TO_PLANE, backend.ICP_POINT_TO_POINT):
                 ses.begin(c.T, path, method=method)
                 keys = ses.keys(first, count, rank)
                 rec = ses.record(first, count)
-                _check_keys(keys, m, storage, c.exact, rank, len(c.tgt), first, count, what)
-                _check_record(rec, m, c.tgt, c.nrm, storage, method, first, count, f"{what} method {method}")
+                harness.check_keys(keys, m, storage, c.exact, rank, len(c.tgt), first, count, what)
+                harness.check_record(rec, m, c.tgt, c.nrm, storage, method, first, count, f"{what} method {method}")
     finally:
         ses.close()
 
@@ -349,16 +181,16 @@ def test_crops(ab, monkeypatch, k, storage):
     src, tgt, nrm = rs.void_cloud(rs.CROP_VOID)
     m = _crop_ref(k, storage)
     crop = backend.make_crop(**rs.CROPS[k])
-    ses = Session(ab[storage], src, tgt, nrm, 1.0, 0.25)
+    ses = harness.Session(ab[storage], src, tgt, nrm, 1.0, 0.25)
     try:
         for path in PATHS:
             what = f"crop{k} {storage} {path}"
-            _path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(np.eye(4), path, crop=crop)
             keys = ses.keys(rank=1)
             rec = ses.record()
-            _check_keys(keys, m, storage, False, 1, len(tgt), 0, len(src), what)
-            _check_record(rec, m, tgt, nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(src), what)
+            harness.check_keys(keys, m, storage, False, 1, len(tgt), 0, len(src), what)
+            harness.check_record(rec, m, tgt, nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(src), what)
             if k == 0:  # [O3D] GetInformationMatrixFromPointClouds with the crop that excludes every query's nearest points
                 got = ses.be.information_matrix_dev(ses.s, ses.t, 1.0, np.eye(4), target_crop=crop)
                 ref = rs.information(tgt, m.idx, storage)
@@ -385,10 +217,10 @@ def test_later_passes(ab, monkeypatch, void, method, storage):
     src, tgt, nrm = rs.void_cloud(void)
     sn = rs.void_source_normals(void)
     n = len(src)
-    ses = Session(ab[storage], src, tgt, nrm, 1.0, 0.25, src_nrm=sn)
+    ses = harness.Session(ab[storage], src, tgt, nrm, 1.0, 0.25, src_nrm=sn)
     try:
         for path in PATHS:
-            _path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             for k in range(4):
                 what = f"later void{void} method {method} {storage} {path} round {k}"
                 ses.begin(rs.LATER_INIT, path, method=method)
@@ -404,12 +236,12 @@ def test_later_passes(ab, monkeypatch, void, method, storage):
                 T = ses.be.icp_finish()["transformation"]
                 assert (T != rs.LATER_INIT).any() == (k > 0), what
                 m = rs.nearest_within(src, tgt, T, 1.0, storage)
-                _premises(m, 1.0, what)
-                _check_keys(keys, m, storage, False, 0, len(tgt), 0, n, what)
+                harness.premises(m, 1.0, what)
+                harness.check_keys(keys, m, storage, False, 0, len(tgt), 0, n, what)
                 if method == backend.ICP_GENERALIZED:
-                    _check_record_gicp(rec_plain, m, tgt, nrm, sn, storage, T, rs.GICP_EPSILON, 0, n, what)
+                    harness.check_record_gicp(rec_plain, m, tgt, nrm, sn, storage, T, rs.GICP_EPSILON, 0, n, what)
                 else:
-                    _check_record(rec_plain, m, tgt, nrm, storage, method, 0, n, what)
+                    harness.check_record(rec_plain, m, tgt, nrm, storage, method, 0, n, what)
                 a, b = rec_keys.cpu().numpy(), rec_plain.cpu().numpy()
                 same = np.ones(32, dtype=bool)
                 same[[27, 29]] = False  # (these may carry the float-rounded d2 of the key)
@@ -434,11 +266,11 @@ def test_two_shards(ab, monkeypatch, name, storage):
     other = backend.Backend(0, PREC[storage], ab=True)
     parts = []
     try:
-        parts += [Session(ab[storage], c.src, c.tgt[:h], c.nrm[:h], c.r, c.cell, src_nrm=sn),
-                  Session(other, c.src, c.tgt[h:], c.nrm[h:], c.r, c.cell, src_nrm=sn)]
+        parts += [harness.Session(ab[storage], c.src, c.tgt[:h], c.nrm[:h], c.r, c.cell, src_nrm=sn),
+                  harness.Session(other, c.src, c.tgt[h:], c.nrm[h:], c.r, c.cell, src_nrm=sn)]
         for path in PATHS:
             what = f"shards {name} {storage} {path}"
-            _path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ks = []
             for rank, ses in enumerate(parts):
                 ses.begin(c.T, path)
@@ -475,7 +307,7 @@ def test_two_shards(ab, monkeypatch, name, storage):
             for rank, ses in enumerate(parts):
                 ses.begin(c.T, path, method=backend.ICP_GENERALIZED)
                 total += ses.record(keys=merged, rank=rank).cpu().numpy()
-            _check_record_gicp(total, m, c.tgt, c.nrm, sn, storage, c.T, rs.GICP_EPSILON, 0, len(c.src), f"{what} generalized")
+            harness.check_record_gicp(total, m, c.tgt, c.nrm, sn, storage, c.T, rs.GICP_EPSILON, 0, len(c.src), f"{what} generalized")
     finally:
         for ses in parts:
             ses.close()
@@ -493,7 +325,7 @@ def test_persistent_map_target(ab, storage):
     crop = backend.make_crop(backend.CROP_MAX_RADIUS, center=tuple(rs.VOID_CENTRE), rmax=2.5)
     mp = be.upload(np.zeros((0, 3)))
     scans = [be.upload(tgt[:10_000]), be.upload(tgt[10_000:])]
-    ses = Session(be, src, None, None, 1.0, None, target_id=mp)
+    ses = harness.Session(be, src, None, None, 1.0, None, target_id=mp)
     try:
         for sc in scans:
             be.map_insert_scan(mp, sc, np.eye(4), 0.1, crop, max_corr_hint=1.0)
@@ -505,10 +337,10 @@ def test_persistent_map_target(ab, storage):
         pts, _ = be.download(mp)
         m = rs.nearest_within(src, pts, np.eye(4), 1.0, storage)
         what = f"persistent map {storage}"
-        _premises(m, 1.0, what)
+        harness.premises(m, 1.0, what)
         assert 15_000 < len(pts) <= len(tgt)
-        _check_keys(keys, m, storage, False, 2, None, 0, len(src), what)  # (positions are slots of the row-paged index, not array positions)
-        _check_record(rec, m, pts, None, storage, backend.ICP_POINT_TO_POINT, 0, len(src), what)
+        harness.check_keys(keys, m, storage, False, 2, None, 0, len(src), what)  # (positions are slots of the row-paged index, not array positions)
+        harness.check_record(rec, m, pts, None, storage, backend.ICP_POINT_TO_POINT, 0, len(src), what)
     finally:
         for c in scans:
             be.free(c)
@@ -564,7 +396,7 @@ def test_fused_kernel_counts_and_rmse(shipped, inp, storage):
                 key = got["transformation"].tobytes()
                 if key not in seen:
                     m = rs.nearest_within(src, tgt, got["transformation"], r, storage, keep=keep)
-                    _premises(m, r, what)
+                    harness.premises(m, r, what)
                     # (terms [28] and [29], the ones read below, are the same in every method)
                     seen[key] = rs.record(m.p, tgt, nrm, m.idx, storage, rs.METHOD_POINT_TO_POINT if method == backend.ICP_GENERALIZED else method)[0]
                 ref = seen[key]
@@ -623,13 +455,13 @@ def test_negative_control_stage_three_skipped(ab, monkeypatch):
     """O3DS_DEBUG_ACC=16 (A/B library) skips stage 3.  The comparison of the stage cases must then report mismatches on the void-0.9 cloud
     and none on the void-0 cloud: the inputs reach the far stage, and the comparison notices a search that stops early.  The count per
     case is a lower bound of the queries stage 3 serves (an unproven stage-2 result is often the right one already)."""
-    _path(monkeypatch, "rows")
+    harness.set_path("rows", monkeypatch)
     counts = {}
     for void in rs.STAGE_VOIDS:
         for cell in (0.25, 0.1):
             name = f"void{void}-cell{cell}-r1.0"
             c, m = _case(name), _ref(name, rs.F32)
-            ses = Session(ab[rs.F32], c.src, c.tgt, c.nrm, c.r, c.cell)
+            ses = harness.Session(ab[rs.F32], c.src, c.tgt, c.nrm, c.r, c.cell)
             try:
                 monkeypatch.setenv("O3DS_DEBUG_ACC", "16")
                 ses.begin(c.T)
@@ -647,28 +479,26 @@ def test_negative_control_stage_three_skipped(ab, monkeypatch):
 
 
 # ---- n. the generalized estimator's record per correspondence (both forms of the restatement, see the module docstring)
-@functools.lru_cache(maxsize=None)
-def _gicp_case(name):
-    return cpu._gicp_case(name)
+_gicp_case = rs._gicp_case
 
 
 def _run_gicp(ab, monkeypatch, name, storage, ranges=None, paths=PATHS):
     """the generalized record of a case on both paths; ranges: (label, first, count) sub-ranges, default the whole source"""
     c = _gicp_case(name)
-    m = cpu.gicp_matches(name, storage)
-    defect = cpu.defect(name, storage)   # the largest over ALL pairs of the case: covers every sub-range
+    m = rs.gicp_matches(name, storage)
+    defect = rs.defect(name, storage)   # the largest over ALL pairs of the case: covers every sub-range
     ranges = [("all", 0, len(c.src))] if ranges is None else ranges
-    ses = Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell, src_nrm=c.src_nrm)
+    ses = harness.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell, src_nrm=c.src_nrm)
     worst = 0.0
     try:
         with ses.eps(c.eps):
             for path in paths:
-                _path(monkeypatch, path)
+                harness.set_path(path, monkeypatch)
                 ses.begin(c.T, path, method=backend.ICP_GENERALIZED)
                 for label, first, count in ranges:
                     what = f"gicp {name} {storage} {path} {label} [{first},{first + count})"
                     rec = ses.record(first, count)
-                    worst = max(worst, _check_record_gicp(rec, m, c.tgt, c.nrm, c.src_nrm, storage, c.T, c.eps, first, count, what, defect))
+                    worst = max(worst, harness.check_record_gicp(rec, m, c.tgt, c.nrm, c.src_nrm, storage, c.T, c.eps, first, count, what, defect))
     finally:
         ses.close()
     return worst
@@ -740,11 +570,11 @@ def test_gicp_crop(ab, monkeypatch, storage):
     sn = rs.void_source_normals(rs.CROP_VOID)
     m = _crop_ref(0, storage)
     crop = backend.make_crop(**rs.CROPS[0])
-    ses = Session(ab[storage], src, tgt, nrm, 1.0, 0.25, src_nrm=sn)
+    ses = harness.Session(ab[storage], src, tgt, nrm, 1.0, 0.25, src_nrm=sn)
     try:
         for path in PATHS:
-            _path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(np.eye(4), path, crop=crop, method=backend.ICP_GENERALIZED)
-            _check_record_gicp(ses.record(), m, tgt, nrm, sn, storage, np.eye(4), rs.GICP_EPSILON, 0, len(src), f"gicp crop0 {storage} {path}")
+            harness.check_record_gicp(ses.record(), m, tgt, nrm, sn, storage, np.eye(4), rs.GICP_EPSILON, 0, len(src), f"gicp crop0 {storage} {path}")
     finally:
         ses.close()

@@ -16,7 +16,6 @@ iterations of the oracle's icp_generalized, and against the closed form the devi
 two forms per pair is DEFECT[case, storage]: below 1e-12 in f64 storage, a few 1e-6 in f32 storage, where the stored normals are unit
 only to 6e-8 -- the GPU tests widen their comparison with Open3D's form by it and hold the closed form at full sharpness.  It compares one
 reference with the other, never with the device."""
-import functools
 import os
 import sys
 
@@ -146,28 +145,9 @@ def test_later_pass_inputs_and_decode():
 
 
 # ---- the generalized estimator ---------------------------------------------------------------------------------------------------------
-GICP_CASES = rs.gicp_cases()
+GICP_CASES = rs.GICP_CASES
 ORACLE_TOL = 1e-12   # the oracle forms M^-1/2 by Jacobi rotations in f64 and sums in query order; agreement was 4e-15 of the scale
-DEFECT = {}          # (case name, storage) -> rs.gicp_defect of the whole case, filled by defect()
-
-
-@functools.lru_cache(maxsize=None)
-def _gicp_case(name):
-    return {c.name: c for c in GICP_CASES}[name]
-
-
-@functools.lru_cache(maxsize=None)
-def gicp_matches(name, storage):
-    c = _gicp_case(name)
-    return rs.nearest_within(c.src, c.tgt, c.T, c.r, storage)
-
-
-def defect(name, storage) -> float:
-    """DEFECT[name, storage], computed on first use"""
-    if (name, storage) not in DEFECT:
-        c = _gicp_case(name)
-        DEFECT[name, storage] = rs.gicp_defect(c.nrm, c.src_nrm, gicp_matches(name, storage).idx, c.T, c.eps, storage)
-    return DEFECT[name, storage]
+_gicp_case, gicp_matches, defect = rs._gicp_case, rs.gicp_matches, rs.defect  # (shared with the GPU tests: tests/icp_search_restatement.py)
 
 
 def _oracle_gicp(oracle, p, tgt_s, nt_s, ns_s, idx, T, eps):

@@ -4,7 +4,7 @@ of each against a record made with the PARENT commit's library (tests/golden/icp
 profiles/search_rows.txt).
 
 What is held, per case, f32 and f64 storage, row search and replica (the replica serves stage 1 only: stages 2 and 3 are the same code):
-  * o3ds_icp_nn_keys per query: match or none as the brute force says; d2 within the bounds of tests/test_icp_search_exact_gpu.py (equal
+  * o3ds_icp_nn_keys per query: match or none as the brute force says; d2 within the bounds of tests/icp_search_harness.py (equal
     float bits in the exact case) -- islands hold one point within r, so d2 names the point;
   * the pass record over all queries within that file's bound: the winner's normal enters every term, which pins the original index;
     in the tie case per query, where d2 cannot tell the two candidates apart;
@@ -19,10 +19,7 @@ pass 0 again -- the recorded correspondence count, fitness and rmse say so.
 Recording (parent commit's library only):
     O3DS_BACKEND_LIB=<A/B library built from the parent commit> python tests/test_icp_search_rows_gpu.py --record FILE"""
 import functools
-import json
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -30,6 +27,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # (run as a script to record: the package)
+import icp_search_harness as harness  # noqa: E402
 import icp_search_restatement as rs  # noqa: E402
 import icp_search_rows_cases as rc  # noqa: E402
 
@@ -38,7 +36,7 @@ from open3d_slam_amd import backend  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "icp_search_rows_parent.npz")
-PATHS = ("rows", "replica")
+PATHS = harness.PATHS
 FIXED = dict(max_iter=3, rel_fitness=0.0, rel_rmse=0.0)
 
 
@@ -57,47 +55,29 @@ def _names():
     return [c.name for c in rc.all_cases()]
 
 
-def _pack(r):
-    f = np.concatenate([np.ascontiguousarray(r["transformation"], np.float64).reshape(16), [r["fitness"], r["inlier_rmse"]]])
-    return f.astype(np.float64), np.array([r["iterations"], r["n_corr"]], np.int64)
-
-
 def _register(ses, c):
     return ses.be.icp_point_to_plane_dev(ses.s, ses.t, c.r, init=c.T, **FIXED)
 
 
-def _registration_session(ex_, be, c, ses):
+def _registration_session(be, c, ses):
     """the session the registration of a case runs in: the case's own, or one whose target carries rc.registration_normals"""
     nrm = rc.registration_normals(c)
-    return ses if nrm is c.nrm else ex_.Session(be, c.src, c.tgt, nrm, c.r, c.cell)
-
-
-@pytest.fixture(scope="module")
-def ex():
-    import test_icp_search_exact_gpu as ex_  # Session, _check_keys, _check_record: the checks of the search tests, unchanged
-
-    return ex_
+    return ses if nrm is c.nrm else harness.Session(be, c.src, c.tgt, nrm, c.r, c.cell)
 
 
 @pytest.fixture(autouse=True)
 def _eager_replica(monkeypatch):
-    monkeypatch.setenv("O3DS_NN_REPLICA_AFTER", "1")
-    monkeypatch.delenv("O3DS_DEBUG_ACC", raising=False)
-    monkeypatch.delenv("O3DS_ICP_SETS", raising=False)
+    harness.eager_replica(monkeypatch, clear=("O3DS_DEBUG_ACC", "O3DS_ICP_SETS"))
 
 
 @pytest.fixture(scope="module")
 def ab():
-    bes = {s: backend.Backend(0, p, ab=True) for s, p in ((rs.F32, backend.PRECISION_F32), (rs.F64, backend.PRECISION_F64))}
-    yield bes
-    for be in bes.values():
-        be.close()
+    yield from harness.backends(True)
 
 
 @pytest.fixture(scope="module")
 def golden():
-    g = np.load(GOLDEN)
-    return {str(n): (g["floats"][k], g["ints"][k]) for k, n in enumerate(g["names"])}
+    return harness.load_parent_record(GOLDEN)[0]
 
 
 def test_golden_file_lists_exactly_the_cases(golden):
@@ -106,46 +86,41 @@ def test_golden_file_lists_exactly_the_cases(golden):
 
 @pytest.mark.parametrize("storage", rs.STORAGES)
 @pytest.mark.parametrize("name", _names())
-def test_rows_per_query_and_the_parents_registration(ex, ab, golden, monkeypatch, name, storage):
+def test_rows_per_query_and_the_parents_registration(ab, golden, monkeypatch, name, storage):
     c, m = _cases()[name], _ref(name, storage)
-    ses = ex.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
-    reg = _registration_session(ex, ab[storage], c, ses)
+    ses = harness.Session(ab[storage], c.src, c.tgt, c.nrm, c.r, c.cell)
+    reg = _registration_session(ab[storage], c, ses)
     try:
         for path in PATHS:
             what = f"{name} {storage} {path}"
-            ex._path(monkeypatch, path)
+            harness.set_path(path, monkeypatch)
             ses.begin(c.T, path)
-            ex._check_keys(ses.keys(rank=3), m, storage, c.exact, 3, len(c.tgt), 0, len(c.src), what)
-            ex._check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(c.src), what)
+            harness.check_keys(ses.keys(rank=3), m, storage, c.exact, 3, len(c.tgt), 0, len(c.src), what)
+            harness.check_record(ses.record(), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, 0, len(c.src), what)
             if name == "ties":  # which of the two won: one query at a time (the winner's normal is in every term)
                 assert (m.idx == np.array([min(1 + 2 * i, 2 + 2 * i) for i in range(len(c.src))])).all(), "premise: the first of each pair"
                 for q in range(len(c.src)):
-                    ex._check_record(ses.record(q, 1), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, q, 1, f"{what} query {q}")
+                    harness.check_record(ses.record(q, 1), m, c.tgt, c.nrm, storage, backend.ICP_POINT_TO_PLANE, q, 1, f"{what} query {q}")
             reg.begin(c.T, path)
             got = _register(reg, c)
             print(f"ROWS {what}: iterations {got['iterations']} n_corr {got['n_corr']} fitness {got['fitness']} rmse {got['inlier_rmse']}")
-            f, i = _pack(got)
+            f, i = harness.pack(got)
             gf, gi = golden[f"{name}|{storage}|{path}"]
             assert np.array_equal(i, gi), (what, i, gi)
-            assert np.array_equal(f.view(np.uint64), gf.view(np.uint64)), (what, f, gf)
+            harness.assert_bits(f, gf, what)
     finally:
         ses.close()
         if reg is not ses:
             reg.close()
 
 
-STATS = re.compile(r"\[(\d+) v(\d+) s(\d+) k(\d+) f(\d+)\]")
-
-
 def _lists_registration(storage):
     """the `lists-far` registration on a handle of its own (replica on, the set policy of the environment)"""
     c = _cases()["lists-far"]
-    import test_icp_search_exact_gpu as ex_
-
-    be = backend.Backend(0, backend.PRECISION_F32 if storage == rs.F32 else backend.PRECISION_F64, ab=True)
+    be = backend.Backend(0, harness.PREC[storage], ab=True)
     try:
-        ses = ex_.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
-        out = _pack(_register(ses, c))
+        ses = harness.Session(be, c.src, c.tgt, c.nrm, c.r, c.cell)
+        out = harness.pack(_register(ses, c))
         ses.close()
     finally:
         be.close()
@@ -169,17 +144,10 @@ def test_sets_listed_by_the_far_stage_serve_the_next_passes(golden, monkeypatch,
     searches: a neighbour the lists left out would show).  The listed positions themselves have no accessor in the ABI."""
     c = _cases()["lists-far"]
     monkeypatch.setenv("O3DS_NN_REPLICA", "1")
-    code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r); import torch; import test_icp_search_rows_gpu as t; "
-            "f, i = t._lists_registration(%r); print(json.dumps([f.view('u8').tolist(), i.tolist()]))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), storage))
-    env = dict(os.environ, O3DS_ICP_STATS="1")
-    env.pop("O3DS_ICP_SETS", None)
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lines = [ln for ln in p.stderr.splitlines() if ln.startswith("icp stats")]
+    child, lines = harness.child_with_stats("test_icp_search_rows_gpu", f"t._lists_registration({storage!r})", unset=("O3DS_ICP_SETS",))
     print(f"ROWS lists-far {storage}: {lines}")
-    assert len(lines) == 1, p.stderr[-2000:]
-    st = {int(k): tuple(int(x) for x in (v, s, kk, f)) for k, v, s, kk, f in STATS.findall(lines[0])}
+    assert len(lines) == 1, lines
+    st = [(p["v"], p["s"], p["k"], p["f"]) for p in harness.parse_stats(lines[0])]
     n = len(c.src)
     assert st[0][:3] == (0, n, 0), "pass 0 follows no update: it searches and lists nothing"
     assert all(st[j][0] + st[j][1] == n for j in range(4)), "every query of a pass is verified or searches"
@@ -188,14 +156,14 @@ def test_sets_listed_by_the_far_stage_serve_the_next_passes(golden, monkeypatch,
     print(f"ROWS lists-far {storage}: sets left by far queries >= {listed}, matches of the next pass verified inside them >= {served}")
     assert any(st[j][3] >= 200 and listed[j] >= 100 and served[j] >= 100 for j in (1, 2)), \
         "premise: the far stage of a pass listed at least a hundred sets in which the next pass verified its matches"
-    cf, ci = json.loads(p.stdout.strip().splitlines()[-1])
-    out = {"child": (np.array(cf, np.uint64).view(np.float64), np.array(ci, np.int64))}
+    out = {"child": child}
     for sets in ("1", "0"):
         monkeypatch.setenv("O3DS_ICP_SETS", sets)  # (read when the handle is made)
         out[sets] = _lists_registration(storage)
     gf, gi = golden[f"lists-far|{storage}|replica"]
     for which, (f, i) in out.items():
-        assert np.array_equal(i, gi) and np.array_equal(f.view(np.uint64), gf.view(np.uint64)), (which, f, gf, i, gi)
+        assert np.array_equal(i, gi), (which, i, gi)
+        harness.assert_bits(f, gf, which)
     assert gi[1] >= 1000, "premise: the registration keeps its correspondences"
 
 
@@ -205,22 +173,20 @@ if __name__ == "__main__":
         sys.exit("usage: O3DS_BACKEND_LIB=<A/B library built from the PARENT commit> python tests/test_icp_search_rows_gpu.py --record FILE")
     import torch  # noqa: F401  (before the backend library is loaded: see tests/conftest.py)
 
-    import test_icp_search_exact_gpu as ex_
-
     os.environ["O3DS_NN_REPLICA_AFTER"] = "1"
     names, floats, ints = [], [], []
-    for storage, prec in ((rs.F32, backend.PRECISION_F32), (rs.F64, backend.PRECISION_F64)):
+    for storage, prec in harness.PREC.items():
         be_ = backend.Backend(0, prec, ab=True)
         for c_ in rc.all_cases():
-            ses_ = ex_.Session(be_, c_.src, c_.tgt, c_.nrm, c_.r, c_.cell)
-            reg_ = _registration_session(ex_, be_, c_, ses_)
+            ses_ = harness.Session(be_, c_.src, c_.tgt, c_.nrm, c_.r, c_.cell)
+            reg_ = _registration_session(be_, c_, ses_)
             for path_ in PATHS:
-                os.environ["O3DS_NN_REPLICA"] = "1" if path_ == "replica" else "0"
+                harness.set_path(path_)
                 ses_.begin(c_.T, path_)
                 ses_.keys(rank=3), ses_.record()  # (the same calls in the same order as the test)
                 reg_.begin(c_.T, path_)
                 res = _register(reg_, c_)
-                f_, i_ = _pack(res)
+                f_, i_ = harness.pack(res)
                 names.append(f"{c_.name}|{storage}|{path_}"), floats.append(f_), ints.append(i_)
                 print(names[-1], res["iterations"], res["n_corr"], res["fitness"], res["inlier_rmse"], flush=True)
             ses_.close()

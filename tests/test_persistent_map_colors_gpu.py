@@ -4,14 +4,10 @@ Every comparison is against the ARRAY form -- the same calls in a child process 
 the golden and oracle tests hold to the reference -- and is byte for byte: points, normals and colours.  Every raw scan point gets a
 colour of its own (frame, index); VoxelDownSample averages them per scan voxel, the frame channel (a dyadic number) stays exact, so
 the winner of a map voxel -- its last member in cloud order -- cannot tie with another frame's."""
-import os
-import pickle
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from child_process import run_child
 from open3d_slam_amd import backend, synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -141,14 +137,15 @@ def _other_cases(be, make_backend):
     return out
 
 
-def _in_child(prec, call):
-    """`call` (an expression over `t` = this module, `be` = the backend, `mk` = a factory of further ones) in a child process with the
-    array form at every insertion: the switch is read once per process, and only by the A/B library"""
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_persistent_map_colors_gpu as t; "
-            "from open3d_slam_amd import backend; mk = lambda: backend.Backend(0, %d, ab=True); be = mk(); "
-            "sys.stdout.buffer.write(pickle.dumps(%s))" % (os.path.dirname(here), here, prec, call))
-    return pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True, env=dict(os.environ, O3DS_NO_PERSISTENT_MAP="1")).stdout)
+def _ab(prec):
+    return backend.Backend(0, prec, ab=True)
+
+
+def _in_child(call):
+    """`call` (an expression over `t` = this module) in a child process with the array form at every insertion: the switch is read once
+    per process, and only by the A/B library (t._ab)"""
+    return run_child("test_persistent_map_colors_gpu", call, env=dict(O3DS_NO_PERSISTENT_MAP="1"),
+                     timeout=300)[0]  # (a guard against a hang: no test of this module took more than 1.2 s on an MI355X)
 
 
 _PREC = {"f64": backend.PRECISION_F64, "f32": backend.PRECISION_F32}
@@ -160,7 +157,7 @@ _cache = {}
 
 def _sequence_runs(prec, case):  # (got, ref) of one case: computed once, shared by the tests that look at it, left unchanged
     if (prec, case) not in _cache:
-        ref = _in_child(_PREC[prec], "t._coloured_sequence(be, 24, **%r)" % (_CASES[case],))
+        ref = _in_child(f"t._coloured_sequence(t._ab({_PREC[prec]}), 24, **{_CASES[case]!r})")
         be = backend.Backend(0, _PREC[prec])
         got = _coloured_sequence(be, 24, **_CASES[case])
         be.close()
@@ -170,7 +167,7 @@ def _sequence_runs(prec, case):  # (got, ref) of one case: computed once, shared
 
 def _other_runs(prec):
     if prec not in _cache:
-        ref = _in_child(_PREC[prec], "t._other_cases(be, mk)")
+        ref = _in_child(f"t._other_cases(t._ab({_PREC[prec]}), lambda: t._ab({_PREC[prec]}))")
         be = backend.Backend(0, _PREC[prec])
         got = _other_cases(be, lambda: backend.Backend(0, _PREC[prec]))
         be.close()

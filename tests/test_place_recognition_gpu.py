@@ -11,6 +11,7 @@ from scipy.spatial import cKDTree
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fpfh_ransac_restatement as rs  # noqa: E402
+from child_process import ROOT, run_child  # noqa: E402
 
 from open3d_slam_amd import backend  # noqa: E402
 from open3d_slam_amd import parameters as prm  # noqa: E402
@@ -314,35 +315,20 @@ def test_determinism_two_handles():
     assert r1["best_t"] >= 0
 
 
+def _ransac_on_a_handle_of_its_own(ab):
+    pa, pb = _pair_points()
+    be = backend.Backend(0, backend.PRECISION_F64, ab=ab)
+    r = _plain(_ransac_on(be, pa, pb)[0])
+    be.close()
+    return r
+
+
 def test_batch_sizes_in_fresh_processes():
     """the A/B library with fixed batches of 1024 and 65536 hypotheses (the switch is read once per process: each size in a child
     process) and the shipped library's growing batches give bit-identical results"""
-    import json
-    import subprocess
-
-    code = r'''
-import json, os, sys
-import numpy as np
-sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
-import test_place_recognition_gpu as t
-from open3d_slam_amd import backend
-pa, pb = t._pair_points()
-be = backend.Backend(0, backend.PRECISION_F64, ab=True)
-r = t._ransac_on(be, pa, pb)[0]
-be.close()
-print(json.dumps(t._plain(r)))
-'''
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for batch in ("1024", "65536"):
-        env = dict(os.environ, O3DS_RANSAC_BATCH=batch)
-        p = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-2000:]
-        outs.append(json.loads(p.stdout.strip().splitlines()[-1]))
-    pa, pb = _pair_points()
-    be = backend.Backend(0, backend.PRECISION_F64)
-    shipped = json.loads(json.dumps(_plain(_ransac_on(be, pa, pb)[0])))
-    be.close()
+    outs = [run_child("test_place_recognition_gpu", "t._ransac_on_a_handle_of_its_own(True)", env=dict(O3DS_RANSAC_BATCH=batch), timeout=600, cwd=ROOT)[0]
+            for batch in ("1024", "65536")]
+    shipped = _ransac_on_a_handle_of_its_own(False)
     assert outs[0] == outs[1] == shipped
 
 

@@ -1,13 +1,13 @@
 """Scan pre-processing and map-fusion kernels vs the CPU oracle, through the C-ABI (needs an MI355X)."""
-import os
-
 import numpy as np
 import pytest
 
 import placed_binning_cases as pb
+from child_process import run_child
 from open3d_slam_amd import backend, synthetic as syn
 
 pytestmark = pytest.mark.gpu
+ME = "test_preprocess_map_gpu"  # (the module a child process imports as `t`)
 
 
 def _match(got, ref, tol):
@@ -1429,15 +1429,8 @@ def _big_map_inserts(be):
 def test_map_merge_by_merging_beyond_two_million_points():
     """the merging path counts the three classes of entries with two 32-bit counters in one 64-bit scan (the third is the remainder), so it
     holds for maps of any size the 32-bit point indices allow; checked against the full sort on a 3 M-point map"""
-    import pickle
-    import subprocess
-    import sys
-
-    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preprocess_map_gpu as t; from open3d_slam_amd import backend; "
-            "be = backend.Backend(0, ab=True); sys.stdout.buffer.write(pickle.dumps(t._big_map_inserts(be)))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))))
-    ref = pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True,
-                                      env=dict(os.environ, O3DS_NO_INCREMENTAL_MERGE="1")).stdout)
+    ref, _ = run_child(ME, "t._big_map_inserts(t.backend.Backend(0, ab=True))", env=dict(O3DS_NO_INCREMENTAL_MERGE="1"),
+                       timeout=300)  # (a guard against a hang: the whole test took 2.0 s on an MI355X)
     be = backend.Backend(0)
     got = _big_map_inserts(be)
     be.close()
@@ -1452,17 +1445,10 @@ def test_map_merge_by_merging_is_bitwise_the_full_sort(prec, monkeypatch):
     the same map byte for byte after every one of 14 insertions along an out-and-back path with a small builder volume (points leave
     the volume, become pass-through, and re-enter on the way back), with a carve in between (which resets the layout)."""
     p = backend.PRECISION_F64 if prec == "f64" else backend.PRECISION_F32
-    import subprocess
-    import sys
-
     # the switch is read once per process: the reference run goes to a child process
-    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preprocess_map_gpu as t; from open3d_slam_amd import backend; "
-            "be = backend.Backend(0, %d, ab=True); sys.stdout.buffer.write(pickle.dumps(t._insert_sequence(be, 14, 12.0, 0.2, carve_at=(9,))))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), p))
-    import pickle
-
-    ref = pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True,
-                                      env=dict(os.environ, O3DS_NO_INCREMENTAL_MERGE="1", O3DS_NO_PERSISTENT_MAP="1")).stdout)
+    ref, _ = run_child(ME, f"t._insert_sequence(t.backend.Backend(0, {p}, ab=True), 14, 12.0, 0.2, carve_at=(9,))",
+                       env=dict(O3DS_NO_INCREMENTAL_MERGE="1", O3DS_NO_PERSISTENT_MAP="1"),
+                       timeout=300)  # (a guard against a hang: the whole test took 0.8 s on an MI355X)
     be = backend.Backend(0, p)
     got = _insert_sequence(be, 14, 12.0, 0.2, carve_at=(9,))
     be.close()
@@ -1483,20 +1469,13 @@ def test_persistent_map_is_bitwise_the_array_form(prec, case):
     volume, pass through for a while and re-enter, scan points beyond the volume join the map unmerged, means round across voxel faces,
     several old points of one voxel merge when the volume comes back over them -- looked at rarely (long histories) or only at the end,
     with a carve in between (which folds the map), and a registration against the persistent map's index after every insertion."""
-    import pickle
-    import subprocess
-    import sys
-
     p = backend.PRECISION_F64 if prec == "f64" else backend.PRECISION_F32
     kw = {"look_rarely": dict(look_at=(3, 4, 11, 17, 23), carve_at=(14,)), "scan_inside_volume": dict(look_at=(7, 15, 23), scan_rmax=11.5),
           "never_until_the_end": dict(look_at=(23,)),
           # the carving voxel is the map's voxel: the persistent map is carved where it is (its voxel hash is the reference's table), twice
           "carved_in_place": dict(look_at=(5, 12, 23), carve_at=(8, 16), carve_voxel=0.2)}[case]
-    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preprocess_map_gpu as t; from open3d_slam_amd import backend; "
-            "be = backend.Backend(0, %d, ab=True); sys.stdout.buffer.write(pickle.dumps(t._insert_sequence(be, 24, 12.0, 0.2, **%r)))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), p, kw))
-    ref = pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True,
-                                      env=dict(os.environ, O3DS_NO_PERSISTENT_MAP="1")).stdout)
+    ref, _ = run_child(ME, f"t._insert_sequence(t.backend.Backend(0, {p}, ab=True), 24, 12.0, 0.2, **{kw!r})", env=dict(O3DS_NO_PERSISTENT_MAP="1"),
+                       timeout=300)  # (a guard against a hang: the whole test took 0.6 to 0.9 s per case on an MI355X)
     be = backend.Backend(0, p)
     got = _insert_sequence(be, 24, 12.0, 0.2, **kw)
     be.close()
@@ -1562,10 +1541,6 @@ def test_points_on_voxel_faces_fall_where_the_oracle_puts_them(backend_f64, back
     bit for bit in f64 storage (identity poses: the placement rounds nothing; tests/test_placed_binning_gpu.py does the same under a
     general pose).  In f32 storage every decision -- what a carve removes, which points overlap, which voxels exist -- is held exactly as
     well, the oracle working on the f32-rounded values the device holds; only voxel means stored in f32 keep the neighbouring tests' bounds."""
-    import pickle
-    import subprocess
-    import sys
-
     from scipy.spatial import cKDTree
 
     be = backend_f64 if prec == "f64" else backend_f32
@@ -1593,12 +1568,8 @@ def test_points_on_voxel_faces_fall_where_the_oracle_puts_them(backend_f64, back
         be.free(cid)
 
     # the array form of the map sequences: the A/B library in a child process (the switch is read once per process)
-    code = ("import sys, pickle; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preprocess_map_gpu as t; from open3d_slam_amd import backend; "
-            "be = backend.Backend(0, %d, ab=True); sys.stdout.buffer.write(pickle.dumps(t._face_map_sequences(be, %r)))"
-            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)),
-               backend.PRECISION_F64 if f64 else backend.PRECISION_F32, prec))
-    array_form = pickle.loads(subprocess.run([sys.executable, "-c", code], capture_output=True, check=True,
-                                             env=dict(os.environ, O3DS_NO_PERSISTENT_MAP="1")).stdout)
+    array_form, _ = run_child(ME, f"t._face_map_sequences(t.backend.Backend(0, {backend.PRECISION_F64 if f64 else backend.PRECISION_F32}, ab=True), {prec!r})",
+                              env=dict(O3DS_NO_PERSISTENT_MAP="1"), timeout=300)  # (a guard against a hang: the whole test took 0.6 s on an MI355X)
     persistent = _face_map_sequences(be, prec)
     ocrop = oracle.make_crop(oracle.CROP_MIN_MAX_RADIUS, rmin=0.0, rmax=1.5)
     raw = _face_carve_scan(prec)
@@ -1769,18 +1740,26 @@ def test_normals_with_exact_ties_duplicates_and_tiny_clouds(backend_f64, oracle)
         backend_f64.free(c)
 
 
+def _normals_digest_of_eight_scans():
+    """(child side) eight scans of varying size down-sampled, their normals estimated and downloaded, everything freed: the digest"""
+    import hashlib
+
+    be = backend.Backend(0)
+    scene = syn.make_scene()
+    h = hashlib.sha1()
+    for k in range(8):
+        c = be.voxel_down_sample(be.upload(syn.vlp16_scan(scene, syn.make_pose([0.3 * k, 0, 0], [0, 0, 2.0 * k]), frame=k, n_az=256 + 64 * (k % 3))), 0.1)
+        be.estimate_normals(c, 2.0, 10)
+        h.update(be.download(c)[1].tobytes())
+        be.free(c)
+    return h.hexdigest()
+
+
 def test_allocator_cache_is_bounded_and_survives_a_trim():
     """The handle's caching allocator gives everything cached back to the driver beyond O3DS_POOL_CAP_MB (size classes drift as a map
     grows); a tiny cap forces that path on every few calls -- results must not change."""
-    import subprocess
-    import sys
-
-    code = ("import sys, hashlib; sys.path.insert(0, %r); import numpy as np; from open3d_slam_amd import backend, synthetic as syn; "
-            "be = backend.Backend(0); scene = syn.make_scene(); h = hashlib.sha1(); "
-            "[ (lambda c: (be.estimate_normals(c, 2.0, 10), h.update(be.download(c)[1].tobytes()), be.free(c)))"
-            "(be.voxel_down_sample(be.upload(syn.vlp16_scan(scene, syn.make_pose([0.3 * k, 0, 0], [0, 0, 2.0 * k]), frame=k, n_az=256 + 64 * (k %% 3))), 0.1)) "
-            "for k in range(8) ]; print(h.hexdigest())" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    outs = [subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True, env=dict(os.environ, O3DS_POOL_CAP_MB=cap)).stdout.strip()
+    outs = [run_child(ME, "t._normals_digest_of_eight_scans()", env=dict(O3DS_POOL_CAP_MB=cap),
+                      timeout=300)[0]  # (a guard against a hang: the whole test, both children, took 0.8 s on an MI355X)
             for cap in ("32768", "1")]
     assert outs[0] == outs[1] and len(outs[0]) == 40
 
