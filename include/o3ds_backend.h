@@ -107,7 +107,7 @@ int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
 /* Tagged spans for bench.py's per-call table: while profiling is enabled, o3ds_profile_span(h, tag, 0) / (h, tag, 1) record a pair
  * of hipEvents on the handle's stream around whatever the caller enqueues in between (tags 0..7).  Tags 8 (the two kernels of
  * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
- * are marked inside the library.  span_read synchronises, returns the
+ * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -486,6 +486,34 @@ int o3ds_remove_statistical_outliers(o3ds_handle h, o3ds_cloud in, int nb_neighb
  * for nb_points < 1 or radius <= 0). */
 int o3ds_remove_radius_outliers(o3ds_handle h, o3ds_cloud in, int nb_points, double radius, o3ds_cloud* out, uint32_t* kept_idx /* may be NULL */,
                                 size_t capacity, size_t* n_kept);
+/* ---- [O3D] PointCloud::ClusterDBSCAN(eps, min_points) on a device cloud, and the filter that drops the noise and the small clusters ----
+ * The labels are defined without reference to a search structure, with the arithmetic of the neighbour search above:
+ *   - coordinates are the stored ones; d2(i, j) = (dx*dx + dy*dy) + dz*dz in the storage type, every operation rounded on its own;
+ *   - j is a neighbour of i iff d2 is finite and d2 < storage(eps * eps), strictly, the product formed in f64;
+ *   - N_i is the neighbour set of point i in its own cloud, self included; a point with a non-finite coordinate has an empty N_i;
+ *   - i is a core point iff |N_i| >= min_points;
+ *   - the clusters are the connected components of the graph on the core points with an edge i - j iff j is in N_i (the relation is
+ *     symmetric bit for bit); cluster ids are 0 .. n_clusters - 1, in the order of each component's smallest core index;
+ *   - a point that is not core gets the smallest cluster id among the core points in N_i, or -1 if there is none.  (The smallest id is
+ *     not the cluster of its lowest-index core neighbour.)
+ * This closed form equals Open3D v0.15.1's sequential procedure -- seeds in index order, a breadth-first walk, a point first marked
+ * noise relabelled by the first cluster that reaches it.  |N_i| has no upper limit.
+ * labels receives one entry per point; cluster_sizes (may be NULL) the number of points labelled c, core and border, for c in
+ * 0 .. n_clusters - 1.  An empty cloud gives *n_clusters = 0 and is not an error.  The cloud's grid index is used if it has one and built
+ * and left with the cloud otherwise (no result depends on its cell size); a cloud in the persistent map form is first folded into its
+ * array.  O3DS_ERR_INVALID_ARG: eps not greater than 0 or not finite, min_points < 1, an unknown id, labels NULL for a non-empty cloud,
+ * an infinite coordinate (reported by the index build), 2^31 points or more.  O3DS_ERR_CAPACITY: capacity smaller than the cloud, or
+ * size_capacity < n_clusters when cluster_sizes is given; *n_clusters is set all the same and neither array is written.
+ * O3DS_ERR_HIP if a loop of the device's union-find exceeded its bound (never expected): nothing is published.  Waits for the result.
+ * While profiling is enabled (o3ds_profile_enable) the library marks spans 11 (the hooking kernel), 12 (flatten and the rank scan) and
+ * 13 (the border walk, labels and sizes); the count of |N_i| is span 10. */
+int o3ds_cluster_dbscan(o3ds_handle h, o3ds_cloud cloud, double eps, int min_points, int32_t* labels /* n */, size_t capacity, size_t* n_clusters,
+                        uint32_t* cluster_sizes /* may be NULL; n_clusters entries, at most size_capacity */, size_t size_capacity);
+/* Point i is kept iff label_i >= 0 and cluster_sizes[label_i] >= min_cluster_size (>= 1; 1 drops the noise only), labels and sizes those
+ * of o3ds_cluster_dbscan(eps, min_points), which never leave the device.  out, kept_idx, capacity, n_kept and O3DS_ERR_CAPACITY exactly as
+ * for o3ds_remove_radius_outliers: points, normals and colours of the kept points in cloud order, FPFH features not carried. */
+int o3ds_remove_small_clusters(o3ds_handle h, o3ds_cloud in, double eps, int min_points, int min_cluster_size, o3ds_cloud* out,
+                               uint32_t* kept_idx /* may be NULL */, size_t capacity, size_t* n_kept);
 /* mapCloud_ += cloud (Submap.cpp:70; [O3D] PointCloud::operator+=). Appends `add` to `map` in place. */
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add);
 /* A copy of a cloud of handle `src` as a cloud of handle `dst` (same device, same storage precision), device to device: points,

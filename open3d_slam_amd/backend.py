@@ -192,6 +192,10 @@ SIGNATURES = {
                                                    C.POINTER(C.c_size_t)]),
     "o3ds_remove_radius_outliers": (C.c_int, [_H, _CL, C.c_int, C.c_double, C.POINTER(_CL), C.POINTER(C.c_uint32), C.c_size_t,
                                               C.POINTER(C.c_size_t)]),
+    "o3ds_cluster_dbscan": (C.c_int, [_H, _CL, C.c_double, C.c_int, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                      C.c_size_t]),
+    "o3ds_remove_small_clusters": (C.c_int, [_H, _CL, C.c_double, C.c_int, C.c_int, C.POINTER(_CL), C.POINTER(C.c_uint32), C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
     "o3ds_cloud_append": (C.c_int, [_H, _CL, _CL]),
     "o3ds_cloud_copy_across": (C.c_int, [_H, _H, _CL, C.POINTER(_CL)]),
     "o3ds_voxelize_within_volume": (C.c_int, [_H, _CL, C.c_double, C.POINTER(Crop)]),
@@ -876,6 +880,27 @@ class Backend:
     def remove_radius_outliers(self, cid: int, nb_points: int, radius: float):
         """[O3D] RemoveRadiusOutliers on the device: (new cloud id, indices of the kept points in `cid`, ascending)"""
         return self._outlier_filter(self.lib.o3ds_remove_radius_outliers, cid, nb_points, radius)
+
+    def cluster_dbscan(self, cid: int, eps: float, min_points: int):
+        """[O3D] ClusterDBSCAN on the device: (labels (n,) int32 with -1 for noise, n_clusters, sizes (n_clusters,) uint32) -- cluster ids
+        in the order of each cluster's smallest core index, a border point in the smallest id among its core neighbours; sizes count
+        core and border points"""
+        n = self.size(cid)[0]
+        rows = max(n, 1)  # (numpy may hand out a NULL pointer for an empty array; the ABI reads NULL as "absent")
+        labels, sizes, nc = np.full(rows, -1, np.int32), np.zeros(rows, np.uint32), C.c_size_t()
+        self._ck(self.lib.o3ds_cluster_dbscan(self.h, cid, float(eps), int(min_points), labels.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(nc),
+                                              sizes.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return labels[:n].copy(), int(nc.value), sizes[: nc.value].copy()
+
+    def remove_small_clusters(self, cid: int, eps: float, min_points: int, min_cluster_size: int):
+        """the points of the DBSCAN clusters (eps, min_points) of at least min_cluster_size points, noise dropped: (new cloud id, indices
+        of the kept points in `cid`, ascending).  The labels stay on the device."""
+        n = self.size(cid)[0]
+        kept = np.zeros(max(n, 1), np.uint32)
+        out, n_kept = _CL(), C.c_size_t()
+        self._ck(self.lib.o3ds_remove_small_clusters(self.h, cid, float(eps), int(min_points), int(min_cluster_size), C.byref(out),
+                                                     kept.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(n_kept)))
+        return out.value, kept[: n_kept.value].copy()
 
     def cloud_append(self, map_id: int, add_id: int):
         self._ck(self.lib.o3ds_cloud_append(self.h, map_id, add_id))

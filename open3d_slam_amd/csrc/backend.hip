@@ -29,6 +29,7 @@
 #include "neighbor_kernels.hpp"
 #include "normals_kernel.hpp"
 #include "pose_graph_kernels.hpp"
+#include "cluster_kernels.hpp"  // (last: its kernels follow every other one in the code object, whose layout the registration was measured with)
 
 using namespace o3ds;
 
@@ -3602,6 +3603,35 @@ int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const doubl
   return O3DS_OK;
 }
 
+// The tail of every filter that judges point by point: flags[0..n) (flags[n] = 0, the scan's sentinel) -> the croppers' scan and stable
+// compaction into `out` (points, normals and colours in cloud order), the kept indices on request.  pos: n + 1 ints of scratch.
+template <typename P4>
+int compact_kept_t(o3ds_handle h, CloudRec& in, size_t n, const int* flags, int* pos, const char* what, CloudRec& out, uint32_t* kept_idx, size_t capacity,
+                   size_t* n_kept) {
+  uint32_t* d_kept = nullptr;
+  int rc = exclusive_scan_int(h, flags, pos, n + 1, pub_slot<int>(h, 0));
+  if (rc) return rc;
+  rc = wait_stream(h);
+  if (rc) return rc;
+  const int total = pub_value<int>(h, 0);
+  *n_kept = (size_t)total;
+  if (kept_idx && (size_t)total > capacity)
+    return fail(h, O3DS_ERR_CAPACITY, std::string(what) + ": kept_idx is too small for the kept points (*n_kept holds their number)");
+  out.n = (size_t)total;
+  if (total > 0) {
+    rc = compact_cloud<P4>(h, in, n, flags, pos, 1, out.n, &out.pts, &out.nrm, &out.col);
+    if (rc) return rc;
+    if (kept_idx) {
+      TMP_ALLOC(d_kept, sizeof(uint32_t) * (size_t)total);
+      kept_index_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(flags, pos, n, d_kept);
+      HIP_TRY(hipGetLastError());
+      rc = d2h_copy(h, kept_idx, d_kept, sizeof(uint32_t) * (size_t)total);
+      if (rc) return rc;
+    }
+  }
+  return O3DS_OK;
+}
+
 // [O3D] RemoveStatisticalOutliers (mode 0: k = nb_neighbors, v = std_ratio) and RemoveRadiusOutliers (mode 1: k = nb_points, v = radius):
 // the search with the cloud as its own target, the mask, the croppers' stable compaction
 template <typename P4>
@@ -3613,7 +3643,7 @@ int outlier_filter_t(o3ds_handle h, CloudRec& in, int mode, int k, double v, Clo
   const size_t n = in.n;
   if (n == 0) return O3DS_OK;
   int *flags = nullptr, *pos = nullptr;
-  uint32_t *d_cnt = nullptr, *d_tot = nullptr, *d_kept = nullptr;
+  uint32_t *d_cnt = nullptr, *d_tot = nullptr;
   double *d_avg = nullptr, *partial = nullptr, *stat = nullptr;
   TMP_ALLOC(flags, sizeof(int) * (n + 1));
   TMP_ALLOC(pos, sizeof(int) * (n + 1));
@@ -3640,26 +3670,7 @@ int outlier_filter_t(o3ds_handle h, CloudRec& in, int mode, int k, double v, Clo
     radius_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_tot, n, (uint32_t)k, flags);
   }
   HIP_TRY(hipGetLastError());
-  rc = exclusive_scan_int(h, flags, pos, n + 1, pub_slot<int>(h, 0));
-  if (rc) return rc;
-  rc = wait_stream(h);
-  if (rc) return rc;
-  const int total = pub_value<int>(h, 0);
-  *n_kept = (size_t)total;
-  if (kept_idx && (size_t)total > capacity) return fail(h, O3DS_ERR_CAPACITY, "outlier filter: kept_idx is too small for the kept points (*n_kept holds their number)");
-  out.n = (size_t)total;
-  if (total > 0) {
-    rc = compact_cloud<P4>(h, in, n, flags, pos, 1, out.n, &out.pts, &out.nrm, &out.col);
-    if (rc) return rc;
-    if (kept_idx) {
-      TMP_ALLOC(d_kept, sizeof(uint32_t) * (size_t)total);
-      kept_index_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(flags, pos, n, d_kept);
-      HIP_TRY(hipGetLastError());
-      rc = d2h_copy(h, kept_idx, d_kept, sizeof(uint32_t) * (size_t)total);
-      if (rc) return rc;
-    }
-  }
-  return O3DS_OK;
+  return compact_kept_t<P4>(h, in, n, flags, pos, "outlier filter", out, kept_idx, capacity, n_kept);
 }
 
 int outlier_filter(o3ds_handle h, o3ds_cloud in, int mode, int k, double v, const char* what, o3ds_cloud* out, uint32_t* kept_idx, size_t capacity,
@@ -5439,3 +5450,147 @@ int o3ds_global_optimization(o3ds_handle h, double* node_poses, size_t n_nodes, 
 #include "sharded.hpp"
 #include "multi_icp.hpp"
 #include "batch_icp.hpp"
+
+// The clustering sits at the end of the file: its kernels are instantiated after every other one.
+namespace {
+// ---- DBSCAN clustering and the small-cluster filter (cluster_kernels.hpp) -------------------------------------------------------------
+// The labels of cloud `c` (n > 0 points, n < 2^31) in d_labels [n] and the number of points per label in d_sizes [n] (entries from
+// *n_clusters on are zero), both device arrays; nothing is copied to the host but the number of clusters and the error word.
+constexpr int kSpanClusterHook = 11, kSpanClusterFlatten = 12, kSpanClusterBorder = 13;
+template <typename P4>
+int cluster_labels_t(o3ds_handle h, CloudRec& c, double eps, int min_points, int* d_labels, uint32_t* d_sizes, size_t* n_clusters) {
+  const size_t n = c.n;
+  *n_clusters = 0;
+  int *parent = nullptr, *flags = nullptr, *pos = nullptr, *d_err = nullptr;
+  uint32_t *d_cnt = nullptr, *d_tot = nullptr;
+  TMP_ALLOC(d_cnt, sizeof(uint32_t) * n);
+  TMP_ALLOC(d_tot, sizeof(uint32_t) * n);
+  TMP_ALLOC(parent, sizeof(int) * n);
+  TMP_ALLOC(flags, sizeof(int) * (n + 1));
+  TMP_ALLOC(pos, sizeof(int) * (n + 1));
+  TMP_ALLOC(d_err, sizeof(int));
+  HIP_TRY(hipMemsetAsync(d_sizes, 0, sizeof(uint32_t) * n, h->stream));
+  bool empty = false;
+  int rc = neighbor_launch_t<P4>(h, c, c, nullptr, nullptr, n, 0, eps, nullptr, nullptr, d_cnt, d_tot, nullptr, &empty);  // |N_i|
+  if (rc) return rc;
+  if (empty) {  // no point with three finite coordinates: everything is noise
+    HIP_TRY(hipMemsetAsync(d_labels, 0xff, sizeof(int) * n, h->stream));
+    return O3DS_OK;
+  }
+  HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int), h->stream));
+  const unsigned int gsz = (unsigned int)((n + kNbrQueriesPerBlock - 1) / kNbrQueriesPerBlock);
+  const P4 *pts = (const P4*)c.pts, *sp = (const P4*)c.spts;
+  const uint32_t mp = (uint32_t)min_points;
+  cluster_init_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(parent, n);
+  span_mark(h, kSpanClusterHook);
+  cluster_walk_kernel<P4, false><<<gsz, 64, 0, h->stream>>>(pts, n, c.grid, sp, eps, mp, d_tot, parent, nullptr, nullptr, d_err);
+  span_mark(h, kSpanClusterHook);
+  span_mark(h, kSpanClusterFlatten);
+  cluster_flatten_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(parent, d_tot, mp, n, flags, d_err);
+  HIP_TRY(hipGetLastError());
+  rc = exclusive_scan_int(h, flags, pos, n + 1, pub_slot<int>(h, 0));
+  if (rc) return rc;
+  span_mark(h, kSpanClusterFlatten);
+  span_mark(h, kSpanClusterBorder);
+  cluster_walk_kernel<P4, true><<<gsz, 64, 0, h->stream>>>(pts, n, c.grid, sp, eps, mp, d_tot, parent, pos, d_labels, d_err);
+  cluster_sizes_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(d_labels, n, d_sizes);
+  span_mark(h, kSpanClusterBorder);
+  HIP_TRY(hipGetLastError());
+  int err = 0;
+  rc = read_back(h, {{&err, d_err, sizeof(err)}});  // (waits for the stream: the scan's total is in its slot)
+  if (rc) return rc;
+  if (err) return fail(h, O3DS_ERR_HIP, "cluster_dbscan: a union-find loop exceeded its bound (never expected); no label is published");
+  *n_clusters = (size_t)pub_value<int>(h, 0);
+  return O3DS_OK;
+}
+
+int cluster_args(o3ds_handle h, const char* what, double eps, int min_points) {
+  if (!(eps > 0.0) || !std::isfinite(eps)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": eps must be a finite number greater than 0");
+  if (min_points < 1) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": min_points < 1");
+  return O3DS_OK;
+}
+constexpr const char* kClusterTooLarge = ": clouds of 2^31 points and more are unsupported (labels are 32-bit)";
+
+template <typename P4>
+int cluster_dbscan_t(o3ds_handle h, CloudRec& c, double eps, int min_points, int32_t* labels, size_t capacity, size_t* n_clusters, uint32_t* cluster_sizes,
+                     size_t size_capacity) {
+  const size_t n = c.n;
+  int* d_labels = nullptr;
+  uint32_t* d_sizes = nullptr;
+  TMP_ALLOC(d_labels, sizeof(int) * n);
+  TMP_ALLOC(d_sizes, sizeof(uint32_t) * n);
+  size_t nc = 0;
+  int rc = cluster_labels_t<P4>(h, c, eps, min_points, d_labels, d_sizes, &nc);
+  if (rc) return rc;
+  if (n_clusters) *n_clusters = nc;
+  if (capacity < n) return fail(h, O3DS_ERR_CAPACITY, "cluster_dbscan: labels has room for fewer entries than the cloud has points");
+  if (cluster_sizes && size_capacity < nc)
+    return fail(h, O3DS_ERR_CAPACITY, "cluster_dbscan: cluster_sizes is too small for the clusters (*n_clusters holds their number)");
+  rc = d2h_copy(h, labels, d_labels, sizeof(int32_t) * n);
+  if (!rc && cluster_sizes && nc) rc = d2h_copy(h, cluster_sizes, d_sizes, sizeof(uint32_t) * nc);
+  return rc;
+}
+
+template <typename P4>
+int small_cluster_filter_t(o3ds_handle h, CloudRec& in, double eps, int min_points, int min_cluster_size, CloudRec& out, uint32_t* kept_idx, size_t capacity,
+                           size_t* n_kept) {
+  out.precision = in.precision;
+  out.n = 0;
+  box_copy(out, in);  // a subset
+  *n_kept = 0;
+  const size_t n = in.n;
+  if (n == 0) return O3DS_OK;
+  int *d_labels = nullptr, *flags = nullptr, *pos = nullptr;
+  uint32_t* d_sizes = nullptr;
+  TMP_ALLOC(d_labels, sizeof(int) * n);
+  TMP_ALLOC(d_sizes, sizeof(uint32_t) * n);
+  TMP_ALLOC(flags, sizeof(int) * (n + 1));
+  TMP_ALLOC(pos, sizeof(int) * (n + 1));
+  size_t nc = 0;
+  const int rc = cluster_labels_t<P4>(h, in, eps, min_points, d_labels, d_sizes, &nc);
+  if (rc) return rc;
+  cluster_size_flag_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(d_labels, d_sizes, n, (uint32_t)min_cluster_size, flags);  // the labels stay here
+  HIP_TRY(hipGetLastError());
+  return compact_kept_t<P4>(h, in, n, flags, pos, "remove_small_clusters", out, kept_idx, capacity, n_kept);
+}
+}  // namespace
+
+extern "C" {
+
+int o3ds_cluster_dbscan(o3ds_handle h, o3ds_cloud cloud, double eps, int min_points, int32_t* labels, size_t capacity, size_t* n_clusters,
+                        uint32_t* cluster_sizes, size_t size_capacity) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  const int ra = cluster_args(h, "cluster_dbscan", eps, min_points);
+  if (ra) return ra;
+  CloudRec* c = find_cloud(h, cloud);  // (with its exact size; a persistent map as its array)
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cluster_dbscan: unknown cloud id");
+  if (!n_clusters) return fail(h, O3DS_ERR_INVALID_ARG, "cluster_dbscan: n_clusters is required");
+  *n_clusters = 0;
+  if (c->n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_INVALID_ARG, std::string("cluster_dbscan") + kClusterTooLarge);
+  if (c->n == 0) return O3DS_OK;  // an empty cloud has no cluster and is no error
+  if (!labels) return fail(h, O3DS_ERR_INVALID_ARG, "cluster_dbscan: labels is NULL");
+  return DISPATCH(c->precision, cluster_dbscan_t, h, *c, eps, min_points, labels, capacity, n_clusters, cluster_sizes, size_capacity);
+}
+
+int o3ds_remove_small_clusters(o3ds_handle h, o3ds_cloud in, double eps, int min_points, int min_cluster_size, o3ds_cloud* out, uint32_t* kept_idx,
+                               size_t capacity, size_t* n_kept) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  const int ra = cluster_args(h, "remove_small_clusters", eps, min_points);
+  if (ra) return ra;
+  if (min_cluster_size < 1) return fail(h, O3DS_ERR_INVALID_ARG, "remove_small_clusters: min_cluster_size < 1");
+  CloudRec* c = find_cloud(h, in);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "remove_small_clusters: unknown cloud id");
+  if (!out || !n_kept) return fail(h, O3DS_ERR_INVALID_ARG, "remove_small_clusters: out and n_kept are required");
+  if (c->n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_INVALID_ARG, std::string("remove_small_clusters") + kClusterTooLarge);
+  CloudRec o;
+  CloudGuard o_guard(h, o);
+  const int rc = DISPATCH(c->precision, small_cluster_filter_t, h, *c, eps, min_points, min_cluster_size, o, kept_idx, capacity, n_kept);
+  if (rc) return rc;
+  o_guard.release();
+  *out = add_cloud(h, std::move(o));
+  return O3DS_OK;
+}
+
+}  // extern "C"

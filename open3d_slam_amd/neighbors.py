@@ -1,5 +1,5 @@
 """Neighbour queries and outlier filters on device clouds: what callers of the reference reach for next to every cloud operation --
-[O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid, PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers -- and
+[O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid, PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers / ClusterDBSCAN -- and
 o3d_slam::computePointCloudDistance (helpers.hpp:29, helpers.cpp:185-218).  Same names; the search runs in the HIP kernel behind
 o3ds_neighbor_search on the target's grid index, no k-d tree is built and no cloud is downloaded.
 
@@ -56,6 +56,19 @@ def RemoveStatisticalOutliers(cloud: PointCloud, nb_neighbors: int, std_ratio: f
 def RemoveRadiusOutliers(cloud: PointCloud, nb_points: int, search_radius: float):
     """[O3D] PointCloud::RemoveRadiusOutliers: (the kept points as a new cloud -- normals and colours carried --, their indices)"""
     cid, kept = cloud.be.remove_radius_outliers(cloud.id, nb_points, search_radius)
+    return PointCloud(cloud.be, cid), kept
+
+
+def ClusterDBSCAN(cloud: PointCloud, eps: float, min_points: int):
+    """[O3D] PointCloud::ClusterDBSCAN: the label of every point, -1 for noise (int32; defined in include/o3ds_backend.h)"""
+    return cloud.be.cluster_dbscan(cloud.id, eps, min_points)[0]
+
+
+def RemoveSmallClusters(cloud: PointCloud, eps: float, min_points: int, min_cluster_size: int):
+    """ClusterDBSCAN(eps, min_points), then the points of the clusters of at least min_cluster_size points: (the kept points as a new
+    cloud -- normals and colours carried --, their indices).  What the two outlier filters keep by construction -- a compact group of
+    points is locally dense -- this drops; the labels never leave the device."""
+    cid, kept = cloud.be.remove_small_clusters(cloud.id, eps, min_points, min_cluster_size)
     return PointCloud(cloud.be, cid), kept
 
 
