@@ -1253,6 +1253,8 @@ template <typename P4, bool kCrop, int kPassBlock, int kGroup, bool kGicp, bool 
                                   registers instead of 128 + spills */>
 __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const double* Tm, int wg, int nwg, double* s_rec_flat,
                                                 double (*s_red)[kRec], int2* s_seg /* [kPassBlock / kGroup][kSegMax] */,
+                                                int* s_far /* [2 + kPassBlock / kGroup]: [0] count, [1] next, [2..] query slots of the far
+                                                list.  kSingle: the caller has zeroed [0] and [1] in front of a barrier of its own */,
                                                 bool use_cache, const QueryPrefetch<P4>& first_batch,
                                                 unsigned long long* tr = nullptr /* 3 timestamps, development aid */,
                                                 SetMargin sm = SetMargin{-1.0f, 0.0f}, int* s_set = nullptr /* [kQPB][1 + kSetCap] */,
@@ -1286,10 +1288,12 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
   double acc = 0.0;
   const size_t n_batches = (n_live + kQPB - 1) / kQPB;  // (n_live is deal_count: see there)
   static_assert(sizeof(FarItem<P4>) <= kStride * sizeof(double), "a parked far query fits its record slot");
-  static_assert((2 + kQPB) * sizeof(int) <= (kPassBlock / 32) * kRec * sizeof(double), "the far list fits s_red");
-  int* s_far = (int*)&s_red[0][0];  // [0] count, [1] next, [2..] query slots; s_red itself is only used after the loop
-  if (threadIdx.x == 0) s_far[0] = s_far[1] = 0;
-  lds_barrier();
+  // One batch per workgroup (kSingle) meets at three barriers: the far count, the records, the query slices.  The three more of the
+  // batch loop order one batch against the next, or this function against a caller that reuses s_red: there they stay.
+  if constexpr (!kSingle) {
+    if (threadIdx.x == 0) s_far[0] = s_far[1] = 0;
+    lds_barrier();
+  }
   for (size_t b = (size_t)wg; b < n_batches; b += kSingle ? n_batches : (size_t)nwg) {
     // (one batch: first_batch was dealt with this n_live, this order and b = wg)
     const size_t i = kSingle ? (size_t)first_batch.qi : query_index<kQPB, 64 / kGroup>(n_live, b, ql, order);
@@ -1493,7 +1497,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
     }
     lds_barrier();
     if (tr && threadIdx.x == 0) tr[2] = wall_clock64();
-    if (threadIdx.x == 0) s_far[0] = s_far[1] = 0;  // everyone is past the far list (ordered before its next use by the barrier below)
+    if (!kSingle && threadIdx.x == 0) s_far[0] = s_far[1] = 0;  // everyone is past the far list (ordered before its next use by the barrier below)
 #pragma unroll
     for (int qq = 0; qq < kQPB / (kPassBlock / 32); ++qq) {
       const double* rec = s_rec_flat + (qs * (kQPB / (kPassBlock / 32)) + qq) * kStride;
@@ -1502,7 +1506,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
       else
         acc = fma(rec[ta], rec[tb], acc);
     }
-    lds_barrier();  // s_rec is rewritten by the next batch
+    if constexpr (!kSingle) lds_barrier();  // s_rec is rewritten by the next batch
   }
   // query slices -> 1, fixed order => bitwise reproducible for a given launch geometry
   s_red[qs][term] = acc;
@@ -1513,7 +1517,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
     for (int k = 0; k < kPassBlock / 32; ++k) v += s_red[k][threadIdx.x];
     if (threadIdx.x >= 30) v = 0.0;
   }
-  lds_barrier();  // s_red may be reused by the caller
+  if constexpr (!kSingle) lds_barrier();  // s_red may be reused by the caller (the one-batch caller reads s_qhi and its registers, nothing else)
   return v;         // valid in threads 0..31
 }
 
@@ -1527,6 +1531,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   __shared__ double s_rec[kQPB * (kGicp ? kRec : kRecSlots)];
   __shared__ double s_red[kPassBlock / 32][kRec];
   __shared__ int2 s_seg[kQPB * kSegMax];
+  __shared__ int s_far[2 + kQPB];
   if (a.debug == 1) {
     if (threadIdx.x < kRec) a.partials[(size_t)blockIdx.x * kRec + threadIdx.x] = a.state->T[0] * 1e-300;
     return;
@@ -1535,7 +1540,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   const int order = pass_order(a.state->pass);
   const size_t n_live = deal_count(a);
   const QueryPrefetch<P4> qp = prefetch_query<P4, kPassBlock, kGroup>(a, blockIdx.x, use_cache, false, order, n_live);
-  const double v = icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, kKeys>(a, a.state->T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, use_cache, qp, nullptr,
+  const double v = icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, kKeys>(a, a.state->T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, s_far, use_cache, qp, nullptr,
                                                                                 SetMargin{-1.0f, 0.0f}, nullptr, n_live, order);
   if (threadIdx.x < kRec) a.partials[(size_t)blockIdx.x * kRec + threadIdx.x] = v;
 }
@@ -2233,6 +2238,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   __shared__ float s_margin[2];
   __shared__ double s_qhi[kRec];
   __shared__ int s_go;
+  __shared__ int s_far[2 + kQPB];  // the far list of the pass body
   // ---------------- prologue: this pass's state from the previous state and the previous pass's slot records ----------------
   // The loads the serial tail waits for go out FIRST (the memory pipeline returns in order), from preloaded pointers: wavefront 0, lane l
   // holds dword l of the state and slot values l, 64 + l, ..., 448 + l (the hi sums of term l, or the lo sums of term l - 32, of the
@@ -2284,7 +2290,10 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
     const double tl = __shfl_down(t, 32, 64);
     if (threadIdx.x < kRec) s_out[threadIdx.x] = t + tl;  // the one rounding, as in reduce_partials
   }
-  if (threadIdx.x < 2) s_margin[threadIdx.x] = threadIdx.x == 0 ? -1.0f : 0.0f;
+  if (threadIdx.x < 2) {
+    s_margin[threadIdx.x] = threadIdx.x == 0 ? -1.0f : 0.0f;
+    s_far[threadIdx.x] = 0;  // (the one-batch pass body has no barrier of its own in front of the far list: the one below serves)
+  }
   if (threadIdx.x < kRec) s_qhi[threadIdx.x] = q_hi_mine;
   lds_barrier();
   if (s_st.done) {  // loop already terminated: hand the final state on
@@ -2321,9 +2330,9 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   // of the pass body: one test per four candidates is a quarter of the search's instructions)
   const bool collect = fa.pass.set_pos != nullptr && sm.w >= 0.0f && fa.pass.set_gain * sm.t <= fa.pass.set_cap;
   unsigned long long* const trb = fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 13 : nullptr;
-  const double v = collect ? icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, true, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg,
+  const double v = collect ? icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, true, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, s_far,
                                                                                               use_cache, qp, trb, sm, s_set, n_live, order)
-                           : icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, false, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg,
+                           : icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, false, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, s_far,
                                                                                                use_cache, qp, trb, sm, s_set, n_live, order);
   O3DS_STAMP(3);
   // ---------------- epilogue: add the record to this workgroup's slot, exactly ----------------
