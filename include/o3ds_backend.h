@@ -107,7 +107,8 @@ int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
 /* Tagged spans for bench.py's per-call table: while profiling is enabled, o3ds_profile_span(h, tag, 0) / (h, tag, 1) record a pair
  * of hipEvents on the handle's stream around whatever the caller enqueues in between (tags 0..7).  Tags 8 (the two kernels of
  * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
- * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) are marked inside the library.  span_read synchronises, returns the
+ * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) and 14 (the evaluation kernel of o3ds_segment_plane, once per batch of
+ * hypotheses) are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -514,6 +515,60 @@ int o3ds_cluster_dbscan(o3ds_handle h, o3ds_cloud cloud, double eps, int min_poi
  * for o3ds_remove_radius_outliers: points, normals and colours of the kept points in cloud order, FPFH features not carried. */
 int o3ds_remove_small_clusters(o3ds_handle h, o3ds_cloud in, double eps, int min_points, int min_cluster_size, o3ds_cloud* out,
                                uint32_t* kept_idx /* may be NULL */, size_t capacity, size_t* n_kept);
+/* ---- [O3D] PointCloud::SegmentPlane(distance_threshold, ransac_n, num_iterations) on a device cloud, and the split by its plane ---------
+ * The procedure of Open3D v0.15.1 (PointCloudSegmentation.cpp), restated from the upstream sources; like every [O3D] row it is not pinned
+ * against a build of Open3D.  The result is defined here without reference to an implementation (tests/plane_restatement.py is the same
+ * text in numpy):
+ *   - COORDINATES are the stored ones widened to f64; all arithmetic is f64 whatever the storage, every operation rounded on its own (no
+ *     fused multiply-add).  n is the number of points.
+ *   - SUM ORDER.  Every sum over points below -- each hypothesis's error, the centroid, the six moments, the sums over a sample -- is taken
+ *     in ONE order that depends on the number m of terms alone: len = max(1, ceil(m / 256)); chunk c (c = 0 .. 255) is the terms
+ *     [c len, min(m, (c + 1) len)) added one after the other in index order onto +0.0 (an empty chunk is +0.0); then a halving tree over the
+ *     256 chunk sums, v[t] = v[t] + v[t + s] for t < s, with s = 128, 64, ..., 1; the sum is v[0].  A term of a point that is no inlier is +0.0.
+ *   - SAMPLE t (t = 0 .. num_iterations - 1) is the points mix(seed + (ransac_n t + j + 1) 0x9E3779B97F4A7C15) mod n for j = 0 ..
+ *     ransac_n - 1, mix the splitmix64 finaliser and the arithmetic modulo 2^64 (the draw of o3ds_ransac_feature_matching).  It draws with
+ *     replacement.  DEPARTURE: Open3D draws distinct indices from a generator seeded by std::random_device, so it has no sequence to
+ *     reproduce; a repeated index among three gives the zero plane and is skipped like any collinear sample.
+ *   - HYPOTHESIS PLANE.  ransac_n == 3 (ComputeTrianglePlane): (a, b, c) = (p1 - p0) x (p2 - p0), each component one product minus the
+ *     other; norm = sqrt((a a + b b) + c c); norm == 0 gives the zero plane; else a, b, c are each divided by norm and
+ *     d = -((a x0 + b y0) + c z0).  ransac_n > 3: the fit below over the sample's ransac_n points in sample order (m = ransac_n terms).
+ *     A hypothesis is skipped, and counted in n_degenerate, iff all four coefficients are exactly 0; a plane with a NaN is evaluated and
+ *     finds no inliers.
+ *   - EVALUATION.  dist_i = |((a x + b y) + c z) + d|; point i is an inlier iff dist_i < distance_threshold, strictly (never for a NaN or an
+ *     infinite dist_i); count = the number of inliers; error = sum of dist_i over the inliers (the distance, not its square: Open3D's rule);
+ *     fitness = count / n; inlier_rmse = error / sqrt(count), 0 when count is 0.
+ *   - WINNER.  The hypotheses that are not skipped are read in index order, starting from fitness 0 and inlier_rmse 0; hypothesis t replaces
+ *     the best iff its fitness is greater, or its fitness is equal and its inlier_rmse strictly smaller.  All num_iterations hypotheses run
+ *     (v0.15.1 has no early stop).  best_plane, fitness, inlier_rmse and best_t are the winner's.
+ *   - INLIERS.  The points that pass the same test against best_plane, in cloud order; n_inliers of them.
+ *   - FIT (GetPlaneFromPoints) of k points: centroid = (sum x / k, sum y / k, sum z / k); r = p - centroid; xx = sum r.x r.x, and xy, xz, yy,
+ *     yz, zz alike; det_x = yy zz - yz yz, det_y = xx zz - xz xz, det_z = xx yy - xy xy; the largest picks the axis, x if det_x >= det_y and
+ *     det_x >= det_z, else y if det_y >= det_z, else z; the normal is
+ *         x: (det_x, xz yz - xy zz, xy yz - xz yy)    y: (xz yz - xy zz, det_y, xy xz - yz xx)    z: (xy yz - xz yy, xy xz - yz xx, det_z)
+ *     norm = sqrt((a a + b b) + c c); norm == 0 gives the zero plane (a NaN goes through); else a, b, c are each divided by norm and
+ *     d = -((a cx + b cy) + c cz).  `plane` is this fit of the inliers (m = n terms, non-inliers +0.0, k = n_inliers).
+ *   - NO WINNER (num_iterations == 0, distance_threshold <= 0 or NaN, every sample degenerate, no hypothesis with an inlier): plane and
+ *     best_plane are zeros, fitness and inlier_rmse 0, best_t -1, n_inliers 0, the inlier cloud is empty and the rest is a copy of the cloud.
+ *     DEPARTURE: Open3D returns a plane of NaNs here.
+ * inlier_idx (may be NULL) receives the inliers' indices, ascending, at most `capacity` of them; inliers_out (may be NULL) is
+ * SelectByIndex(inliers) and rest_out (may be NULL) SelectByIndex(inliers, invert = true): points, normals and colours in cloud order, as
+ * o3ds_remove_radius_outliers carries them; FPFH features are not carried.  More inliers than `capacity` with inlier_idx given:
+ * O3DS_ERR_CAPACITY, *out is complete (n_inliers holds their number) and no cloud is made.  A cloud in the persistent map form is first
+ * folded into its array; no grid index is built or needed, and an infinite coordinate is no error (such a point is never an inlier).
+ * O3DS_ERR_INVALID_ARG: ransac_n < 3 and n < ransac_n (an empty cloud included) with Open3D's messages, ransac_n > 8, num_iterations < 0 or
+ * > 16 777 216, an unknown id, out NULL, inlier_idx NULL with capacity > 0, 2^31 points or more.  Waits for the result.  While profiling
+ * is enabled the library marks span 14 around every launch of the kernel that evaluates a batch of hypotheses against all points. */
+typedef struct {
+  double plane[4];        /* a x + b y + c z + d = 0, refitted on the inliers; zeros when there is no winner */
+  double best_plane[4];   /* the winning hypothesis before the refit */
+  double fitness, inlier_rmse; /* of the winning hypothesis */
+  uint64_t n_inliers;
+  int64_t best_t;         /* winning hypothesis, -1: none */
+  int64_t n_degenerate;   /* hypotheses skipped because their plane was zero */
+} o3ds_plane_result;
+int o3ds_segment_plane(o3ds_handle h, o3ds_cloud cloud, double distance_threshold, int ransac_n, int64_t num_iterations, uint64_t seed,
+                       o3ds_plane_result* out, uint32_t* inlier_idx /* may be NULL */, size_t capacity,
+                       o3ds_cloud* inliers_out /* may be NULL */, o3ds_cloud* rest_out /* may be NULL */);
 /* mapCloud_ += cloud (Submap.cpp:70; [O3D] PointCloud::operator+=). Appends `add` to `map` in place. */
 int o3ds_cloud_append(o3ds_handle h, o3ds_cloud map, o3ds_cloud add);
 /* A copy of a cloud of handle `src` as a cloud of handle `dst` (same device, same storage precision), device to device: points,

@@ -99,6 +99,12 @@ class PoseGraphResult(C.Structure):  # o3ds_pose_graph_result
     _fields_ = [("valid", C.c_int32), ("n_edges_kept", C.c_int32), ("iterations", C.c_int32 * 2), ("lm_steps", C.c_int32 * 2),
                 ("stop_reason", C.c_int32 * 2), ("residual", C.c_double * 2), ("line_process_weight", C.c_double * 2)]
 
+
+class PlaneResult(C.Structure):  # o3ds_plane_result
+    _fields_ = [("plane", C.c_double * 4), ("best_plane", C.c_double * 4), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("n_inliers", C.c_uint64), ("best_t", C.c_int64), ("n_degenerate", C.c_int64)]
+
+
 SIGNATURES = {
     "o3ds_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
     "o3ds_destroy": (C.c_int, [_H]),
@@ -196,6 +202,8 @@ SIGNATURES = {
                                       C.c_size_t]),
     "o3ds_remove_small_clusters": (C.c_int, [_H, _CL, C.c_double, C.c_int, C.c_int, C.POINTER(_CL), C.POINTER(C.c_uint32), C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
+    "o3ds_segment_plane": (C.c_int, [_H, _CL, C.c_double, C.c_int, C.c_int64, C.c_uint64, C.POINTER(PlaneResult), C.POINTER(C.c_uint32), C.c_size_t,
+                                     C.POINTER(_CL), C.POINTER(_CL)]),
     "o3ds_cloud_append": (C.c_int, [_H, _CL, _CL]),
     "o3ds_cloud_copy_across": (C.c_int, [_H, _H, _CL, C.POINTER(_CL)]),
     "o3ds_voxelize_within_volume": (C.c_int, [_H, _CL, C.c_double, C.POINTER(Crop)]),
@@ -901,6 +909,20 @@ class Backend:
         self._ck(self.lib.o3ds_remove_small_clusters(self.h, cid, float(eps), int(min_points), int(min_cluster_size), C.byref(out),
                                                      kept.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(n_kept)))
         return out.value, kept[: n_kept.value].copy()
+
+    def segment_plane(self, cid: int, distance_threshold: float = 0.01, ransac_n: int = 3, num_iterations: int = 100, seed: int = 0,
+                      split: bool = False):
+        """[O3D] SegmentPlane on the device: (plane (4,) refitted on the inliers, inlier indices ascending, the PlaneResult); with `split`
+        also (.., inlier cloud id, rest cloud id) -- SelectByIndex(inliers) and its inverse, normals and colours carried.  No winner:
+        a zero plane, best_t -1, no inliers, the rest a copy of the cloud."""
+        n = self.size(cid)[0]
+        idx = np.zeros(max(n, 1), np.uint32)
+        res, inl, rest = PlaneResult(), _CL(), _CL()
+        self._ck(self.lib.o3ds_segment_plane(self.h, cid, float(distance_threshold), int(ransac_n), int(num_iterations), int(seed) % (1 << 64),
+                                             C.byref(res), idx.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(inl) if split else None,
+                                             C.byref(rest) if split else None))
+        out = (np.array(res.plane), idx[: res.n_inliers].copy(), res)
+        return out + (inl.value, rest.value) if split else out
 
     def cloud_append(self, map_id: int, add_id: int):
         self._ck(self.lib.o3ds_cloud_append(self.h, map_id, add_id))

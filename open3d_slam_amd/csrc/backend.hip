@@ -30,6 +30,7 @@
 #include "normals_kernel.hpp"
 #include "pose_graph_kernels.hpp"
 #include "cluster_kernels.hpp"  // (last: its kernels follow every other one in the code object, whose layout the registration was measured with)
+#include "plane_kernels.hpp"    // (and these follow the clustering's)
 
 using namespace o3ds;
 
@@ -5590,6 +5591,114 @@ int o3ds_remove_small_clusters(o3ds_handle h, o3ds_cloud in, double eps, int min
   if (rc) return rc;
   o_guard.release();
   *out = add_cloud(h, std::move(o));
+  return O3DS_OK;
+}
+
+}  // extern "C"
+
+// The plane segmentation follows the clustering: its kernels are instantiated last of all.
+namespace {
+// ---- [O3D] SegmentPlane and the split by the plane (plane_kernels.hpp) -----------------------------------------------------------------
+constexpr int64_t kPlaneMaxIterations = 1 << 24;
+constexpr int kSpanPlaneEval = 14;
+
+template <typename P4>
+int segment_plane_t(o3ds_handle h, CloudRec& in, double thr, int ransac_n, int64_t num_iterations, uint64_t seed, o3ds_plane_result* out,
+                    uint32_t* inlier_idx, size_t capacity, CloudRec* inl, CloudRec* rest) {
+  const size_t n = in.n;
+  const P4* pts = (const P4*)in.pts;
+  PlaneState* st = nullptr;
+  double *planes = nullptr, *perr = nullptr, *fit = nullptr, *rmse = nullptr, *partial = nullptr;
+  uint32_t* pcnt = nullptr;
+  int *flags = nullptr, *nflags = nullptr, *pos = nullptr;
+  TMP_ALLOC(st, sizeof(PlaneState));
+  TMP_ALLOC(planes, sizeof(double) * 4 * kPlaneBatch);
+  TMP_ALLOC(perr, sizeof(double) * (size_t)kPlaneChunks * kPlaneBatch);
+  TMP_ALLOC(pcnt, sizeof(uint32_t) * (size_t)kPlaneChunks * kPlaneBatch);
+  TMP_ALLOC(fit, sizeof(double) * kPlaneBatch);
+  TMP_ALLOC(rmse, sizeof(double) * kPlaneBatch);
+  TMP_ALLOC(partial, sizeof(double) * 6 * kPlaneChunks);
+  TMP_ALLOC(flags, sizeof(int) * (n + 1));
+  TMP_ALLOC(nflags, sizeof(int) * (n + 1));
+  TMP_ALLOC(pos, sizeof(int) * (n + 1));
+  plane_init_kernel<><<<1, 1, 0, h->stream>>>(st);
+  for (int64_t t0 = 0; t0 < num_iterations; t0 += kPlaneBatch) {
+    const int count = (int)std::min<int64_t>(kPlaneBatch, num_iterations - t0);
+    const unsigned int groups = (unsigned int)((count + 63) / 64);
+    plane_hypothesis_kernel<P4><<<groups, 64, 0, h->stream>>>(pts, n, ransac_n, seed, (uint64_t)t0, count, planes);
+    span_mark(h, kSpanPlaneEval);
+    plane_eval_kernel<P4><<<dim3(groups, kPlaneChunks), 64, 0, h->stream>>>(pts, n, planes, thr, perr, pcnt);
+    span_mark(h, kSpanPlaneEval);
+    plane_finish_kernel<><<<groups * (64 / kPlaneFinishHyps), kBlock, 0, h->stream>>>(perr, pcnt, n, fit, rmse);
+    plane_fold_kernel<><<<1, kBlock, 0, h->stream>>>(planes, fit, rmse, count, (long long)t0, st);
+  }
+  plane_mask_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>(pts, n, st, thr, flags, nflags);
+  plane_sums_kernel<P4, 0><<<kPlaneChunks, 64, 0, h->stream>>>(pts, n, flags, st, partial);
+  plane_sums_finish_kernel<0><<<1, kBlock, 0, h->stream>>>(partial, st);
+  plane_sums_kernel<P4, 1><<<kPlaneChunks, 64, 0, h->stream>>>(pts, n, flags, st, partial);
+  plane_sums_finish_kernel<1><<<1, kBlock, 0, h->stream>>>(partial, st);
+  HIP_TRY(hipGetLastError());
+  PlaneState s;
+  int rc = read_back(h, {{&s, st, sizeof(s)}});
+  if (rc) return rc;
+  for (int k = 0; k < 4; ++k) out->plane[k] = s.plane[k], out->best_plane[k] = s.best_plane[k];
+  out->fitness = s.fitness;
+  out->inlier_rmse = s.rmse;
+  out->n_inliers = s.n_inliers;
+  out->best_t = s.best_t;
+  out->n_degenerate = s.n_degenerate;
+  if (inlier_idx && s.n_inliers > capacity)
+    return fail(h, O3DS_ERR_CAPACITY, "segment_plane: inlier_idx is too small for the inliers (n_inliers holds their number)");
+  size_t m = 0;
+  if (inl || inlier_idx) {  // SelectByIndex(inliers)
+    CloudRec scratch;
+    CloudGuard scratch_guard(h, scratch);
+    CloudRec& o = inl ? *inl : scratch;
+    o.precision = in.precision;
+    box_copy(o, in);  // a subset
+    rc = compact_kept_t<P4>(h, in, n, flags, pos, "segment_plane", o, inlier_idx, capacity, &m);
+    if (rc) return rc;
+  }
+  if (rest) {  // SelectByIndex(inliers, invert = true)
+    rest->precision = in.precision;
+    box_copy(*rest, in);
+    rc = compact_kept_t<P4>(h, in, n, nflags, pos, "segment_plane", *rest, nullptr, 0, &m);
+  }
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int o3ds_segment_plane(o3ds_handle h, o3ds_cloud cloud, double distance_threshold, int ransac_n, int64_t num_iterations, uint64_t seed,
+                       o3ds_plane_result* out, uint32_t* inlier_idx, size_t capacity, o3ds_cloud* inliers_out, o3ds_cloud* rest_out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!out) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: out is required");
+  *out = o3ds_plane_result{};
+  out->best_t = -1;
+  if (ransac_n < 3) return fail(h, O3DS_ERR_INVALID_ARG, "ransac_n should be set to higher than or equal to 3.");  // [O3D]
+  if (ransac_n > kRansacMaxN) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: ransac_n > 8 unsupported");
+  if (num_iterations < 0 || num_iterations > kPlaneMaxIterations)
+    return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: num_iterations is negative or above 16777216");
+  if (!inlier_idx && capacity > 0) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: inlier_idx is NULL with capacity > 0");
+  CloudRec* c = find_cloud(h, cloud);  // (with its exact size; a persistent map as its array)
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: unknown cloud id");
+  if (c->n < (size_t)ransac_n) return fail(h, O3DS_ERR_INVALID_ARG, "There must be at least 'ransac_n' points.");  // [O3D]
+  if (c->n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: clouds of 2^31 points and more are unsupported (the scan's positions are 32-bit)");
+  CloudRec inl, rest;
+  CloudGuard inl_guard(h, inl), rest_guard(h, rest);
+  const int rc = DISPATCH(c->precision, segment_plane_t, h, *c, distance_threshold, ransac_n, num_iterations, seed, out, inlier_idx, capacity,
+                          inliers_out ? &inl : nullptr, rest_out ? &rest : nullptr);
+  if (rc) return rc;
+  if (inliers_out) {
+    inl_guard.release();
+    *inliers_out = add_cloud(h, std::move(inl));
+  }
+  if (rest_out) {
+    rest_guard.release();
+    *rest_out = add_cloud(h, std::move(rest));
+  }
   return O3DS_OK;
 }
 

@@ -1,5 +1,5 @@
 """Neighbour queries and outlier filters on device clouds: what callers of the reference reach for next to every cloud operation --
-[O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid, PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers / ClusterDBSCAN -- and
+[O3D] KDTreeFlann::SearchKNN / SearchRadius / SearchHybrid, PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers / ClusterDBSCAN / SegmentPlane -- and
 o3d_slam::computePointCloudDistance (helpers.hpp:29, helpers.cpp:185-218).  Same names; the search runs in the HIP kernel behind
 o3ds_neighbor_search on the target's grid index, no k-d tree is built and no cloud is downloaded.
 
@@ -70,6 +70,20 @@ def RemoveSmallClusters(cloud: PointCloud, eps: float, min_points: int, min_clus
     points is locally dense -- this drops; the labels never leave the device."""
     cid, kept = cloud.be.remove_small_clusters(cloud.id, eps, min_points, min_cluster_size)
     return PointCloud(cloud.be, cid), kept
+
+
+def SegmentPlane(cloud: PointCloud, distance_threshold: float = 0.01, ransac_n: int = 3, num_iterations: int = 100, seed: int = 0):
+    """[O3D] PointCloud::SegmentPlane: (plane (a, b, c, d) refitted on the inliers, their indices, the result record with the winning
+    hypothesis, fitness and inlier_rmse).  Seeded: the same seed gives the same bytes (defined in include/o3ds_backend.h).  No plane found:
+    zeros and no inliers, where Open3D returns NaNs."""
+    return cloud.be.segment_plane(cloud.id, distance_threshold, ransac_n, num_iterations, seed)
+
+
+def SplitByPlane(cloud: PointCloud, distance_threshold: float = 0.01, ransac_n: int = 3, num_iterations: int = 100, seed: int = 0):
+    """SegmentPlane, then SelectByIndex(inliers) and SelectByIndex(inliers, invert=True) without the indices leaving the device: (plane,
+    the inliers, the rest) -- normals and colours carried.  What a scan needs before ClusterDBSCAN: with its ground it is one cluster."""
+    plane, _, _, inl, rest = cloud.be.segment_plane(cloud.id, distance_threshold, ransac_n, num_iterations, seed, split=True)
+    return plane, PointCloud(cloud.be, inl), PointCloud(cloud.be, rest)
 
 
 def computePointCloudDistance(reference: PointCloud, cloud: PointCloud, idsInReference):
