@@ -39,7 +39,8 @@ namespace {
 thread_local std::string g_thread_error;
 
 // A/B levers, tuning knobs and debugging aids (O3DS_ICP_MODE, O3DS_ICP_SETS, O3DS_SUM_NO_SPLIT, O3DS_VOXEL_SORT, O3DS_CARVE_SORT, ...) exist
-// only in the library built with -DO3DS_AB_SWITCHES (lib/libo3ds_backend_ab.so: what the A/B tests and the experiment scripts load).  The
+// only in the library built with -DO3DS_AB_SWITCHES (lib/libo3ds_backend_ab.so: what the A/B tests and the experiment scripts load); every one
+// of them is listed in tests/test_abi.py, which fails on a name that is not: a lever is kept while a test, the benchmark or a kernel uses it.  The
 // shipped library reads three environment variables, two of memory sizing and the file name of RCCL: O3DS_POOL_CAP_MB, O3DS_ARENA_MB, O3DS_RCCL_LIB -- a drop-in library's results
 // and code paths must not depend on its host process's environment.
 #ifdef O3DS_AB_SWITCHES
@@ -438,7 +439,7 @@ int d2h_copy(o3ds_handle h, void* h_dst, const void* d_src, size_t bytes) {  // 
 // the runtime's.  Round 1 used hipMallocAsync / hipFreeAsync; under alloc / free churn of blocks of tens to hundreds of MB
 // (estimate_normals with a fine pilot grid: a 150 MB scratch block, 40 MB cell tables per call) ROCm 7.2's pool intermittently
 // handed out memory whose contents were then lost -- cell_start came back zeroed from some cell on, or the GPU faulted on it
-// (scripts/stress_normals.py with O3DS_NRM_DEBUG=1 shows the broken table before the kernel that reads it runs; the scratch arena
+// (scripts/stress_normals.py reproduced it; a host-side check showed the broken table before the kernel that reads it ran; the scratch arena
 // had met the same thing in round 1 and stopped returning its blocks).  Sizes are rounded up to 1/8 of their power of two, so the
 // slowly varying sizes of a lidar stream hit the same classes; blocks go back to the driver only when the handle is destroyed.
 hipError_t dev_alloc(o3ds_handle h, void** out, size_t bytes) {
@@ -525,14 +526,6 @@ struct DevGuard {
 int arena_alloc(o3ds_handle h, void** out, size_t bytes) {
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes == 0) bytes = 256;
-  static const bool no_reuse = ab_getenv("O3DS_NO_ARENA") != nullptr;  // debugging aid: every temporary is its own pool allocation
-  if (no_reuse) {
-    char* p = nullptr;
-    if (dev_alloc(h, (void**)&p, bytes) != hipSuccess) return fail(h, O3DS_ERR_OOM, "arena: out of memory");
-    h->arena_blocks.emplace_back(p, 0);
-    *out = p;
-    return O3DS_OK;
-  }
   for (;;) {
     if (h->arena_cur < h->arena_blocks.size()) {
       auto& b = h->arena_blocks[h->arena_cur];
@@ -552,18 +545,12 @@ int arena_alloc(o3ds_handle h, void** out, size_t bytes) {
     hipError_t e = dev_alloc(h, (void**)&p, want);
     if (e != hipSuccess) return fail(h, O3DS_ERR_OOM, std::string("arena: ") + hipGetErrorString(e));
     h->arena_blocks.emplace_back(p, want);
-    if (ab_getenv("O3DS_ARENA_LOG"))
-      fprintf(stderr, "[arena] new block %zu MB (request %zu B, blocks now %zu, prev off %zu)\n", want >> 20, bytes, h->arena_blocks.size(), h->arena_off);
   }
 }
 struct ArenaScope {
   o3ds_handle h;
   explicit ArenaScope(o3ds_handle hh) : h(hh) {
     if (h && h->arena_depth++ == 0) {
-      if (ab_getenv("O3DS_NO_ARENA")) {
-        for (auto& b : h->arena_blocks) dev_free(h, b.first);
-        h->arena_blocks.clear();
-      }
       // Blocks are never returned or merged while the handle lives: they grow geometrically, so there are at most a
       // handful, and a call simply walks through them.  (Freeing a 32 MB and a 64 MB block and immediately requesting
       // one 96 MB block from the stream-ordered pool corrupted live data on ROCm 7.2 -- timing dependent, reproduced
@@ -576,11 +563,6 @@ struct ArenaScope {
     if (h) --h->arena_depth;
   }
 };
-// debugging aid: O3DS_SYNC_MASK re-inserts a stream synchronisation at the end of selected internal steps
-inline void dbg_sync(o3ds_handle h, int bit) {
-  static const int mask = ab_getenv("O3DS_SYNC_MASK") ? atoi(ab_getenv("O3DS_SYNC_MASK")) : 0;
-  if (mask & bit) (void)hipStreamSynchronize(h->stream);
-}
 // tagged span marks on the handle's stream (only while profiling is enabled): begin and end alternate per tag
 void span_mark(o3ds_handle h, int tag) {
   if (!h->profiling || tag < 0 || tag >= 16) return;
@@ -610,6 +592,18 @@ inline int grid_for(size_t n, int cap = 4096) {
 size_t p4_size(int precision) { return precision == O3DS_PRECISION_F64 ? sizeof(P4d) : sizeof(P4f); }
 // fn<P4> of the storage precision
 #define DISPATCH(prec, fn, ...) ((prec) == O3DS_PRECISION_F64 ? fn<P4d>(__VA_ARGS__) : fn<P4f>(__VA_ARGS__))
+// ... and a launch that is not worth a function of its own: statements that name the type as P4 (not a generic lambda: its kernels would be
+// instantiated behind every other one instead of where they are first used, and the order of the kernels in the code object follows that)
+#define WITH_P4(prec, ...)              \
+  do {                                  \
+    if ((prec) == O3DS_PRECISION_F64) { \
+      using P4 = P4d;                   \
+      __VA_ARGS__;                      \
+    } else {                            \
+      using P4 = P4f;                   \
+      __VA_ARGS__;                      \
+    }                                   \
+  } while (0)
 
 void cloud_ready(o3ds_handle h, CloudRec& c);
 int resolve_count(o3ds_handle h, CloudRec& c, bool block);
@@ -788,6 +782,16 @@ struct CloudGuard {
   }
   void release() { c = nullptr; }
 };
+// ... and an index under construction over points its record only borrows: the index is freed on every early return, kept by release()
+struct IndexGuard {
+  o3ds_handle h;
+  CloudRec* c;
+  IndexGuard(o3ds_handle hh, CloudRec& cc) : h(hh), c(&cc) {}
+  ~IndexGuard() {
+    if (c) free_index(h, *c);
+  }
+  void release() { c = nullptr; }
+};
 
 // exclusive scan of m ints (in -> out) with the hand-written 3-phase scan; in may alias out
 // pub: null, or a device-visible address (the handle's pinned block) that also receives out[m - 1] -- the total, when the input ends in a
@@ -807,7 +811,6 @@ int exclusive_scan_phases(o3ds_handle h, T* out, size_t m, T* pub, L&& local) {
     scan_add_kernel<T><<<nb, kBlock, 0, h->stream>>>(out, sums, m, pub);
   }
   HIP_TRY(hipGetLastError());
-  dbg_sync(h, 1);
   return O3DS_OK;  // results are stream-ordered; callers that need a value on the host copy it back and synchronise
 }
 template <typename T>
@@ -893,11 +896,6 @@ int handle_scratch(o3ds_handle h, T** ptr, size_t* cap, size_t want, size_t new_
   *fresh = true;
   return O3DS_OK;
 }
-// debugging / A/B aid: do not rely on self-cleaning scratch -- every block with a clean flag is cleared before every use
-bool always_clear() {
-  static const bool on = ab_getenv("O3DS_ALWAYS_CLEAR") != nullptr;
-  return on;
-}
 // per-cell counters for a table of ncell cells: the handle's block of zeros (ncell + 1: the scan's sentinel stays zero), counted up by
 // a count kernel, read by the scan, counted back down to zero by the scatter -- after which the caller sets cells_clean again (stream
 // order: whoever counts next runs after that scatter).  h->d_cells is null when the allocation failed.
@@ -906,7 +904,7 @@ int cell_counters(o3ds_handle h, size_t ncell) {
   const int rc = handle_scratch(h, &h->d_cells, &h->cells_cap, ncell + 1, ncell + 1 + ncell / 4, sizeof(int) * (ncell + 1 + ncell / 4), &fresh);
   if (rc || !h->d_cells) return rc;
   if (fresh) h->cells_clean = false;
-  if (!h->cells_clean || always_clear()) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
+  if (!h->cells_clean) HIP_TRY(hipMemsetAsync(h->d_cells, 0, sizeof(int) * h->cells_cap, h->stream));
   h->cells_clean = false;
   return O3DS_OK;
 }
@@ -924,7 +922,7 @@ int vox_scratch(o3ds_handle h, size_t n, const char* what, VoxTable* table, size
   cap = h->voxtab_cap;
   unsigned char* tab = h->d_voxtab;
   *table = VoxTable{(VoxSlot*)tab, (unsigned int*)(tab + kVoxSlotBytes * cap), (unsigned int)(cap - 1)};
-  if (!h->voxtab_clean || always_clear()) HIP_TRY(hipMemsetAsync(tab, 0xff, kVoxSlotBytes * cap + 16, h->stream));
+  if (!h->voxtab_clean) HIP_TRY(hipMemsetAsync(tab, 0xff, kVoxSlotBytes * cap + 16, h->stream));
   h->voxtab_clean = false;
   *n_tiles = (n + kVoxTile - 1) / kVoxTile;
   const size_t tiles = std::max<size_t>(*n_tiles + *n_tiles / 4, 1024);
@@ -998,24 +996,21 @@ inline void cpu_relax() {
 #endif
 }
 hipError_t wait_fused_state(o3ds_handle h, unsigned long long seq) {
-  static const bool watch = !(ab_getenv("O3DS_ICP_WATCH_STATE") && atoi(ab_getenv("O3DS_ICP_WATCH_STATE")) == 0);
-  if (watch) {
-    const volatile unsigned long long* w = (const volatile unsigned long long*)(h->h_pin + kPubOff + 16 * (size_t)kSeqSlot);
-    // spin for ~20 us (a steady pass launch is 10 us: the stamp of a registration that is about to finish shows up inside that), then
-    // give the core away between looks: SlamWrapper runs four to seven threads (SlamWrapper.cpp:227-236) and a GPU box grants its
-    // container a CPU quota -- a core that spins through a whole registration is a core the other worker does not get
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int spins = 1;; ++spins) {
-      if (*w == seq) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return hipSuccess;
-      }
-      cpu_relax();
-      if ((spins & 0x3fu) == 0) {
-        const auto dt = std::chrono::steady_clock::now() - t0;
-        if (dt > std::chrono::milliseconds(50)) break;
-        if (dt > std::chrono::microseconds(kWaitSpinUs)) sched_yield();
-      }
+  const volatile unsigned long long* w = (const volatile unsigned long long*)(h->h_pin + kPubOff + 16 * (size_t)kSeqSlot);
+  // spin for ~20 us (a steady pass launch is 10 us: the stamp of a registration that is about to finish shows up inside that), then
+  // give the core away between looks: SlamWrapper runs four to seven threads (SlamWrapper.cpp:227-236) and a GPU box grants its
+  // container a CPU quota -- a core that spins through a whole registration is a core the other worker does not get
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned int spins = 1;; ++spins) {
+    if (*w == seq) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      return hipSuccess;
+    }
+    cpu_relax();
+    if ((spins & 0x3fu) == 0) {
+      const auto dt = std::chrono::steady_clock::now() - t0;
+      if (dt > std::chrono::milliseconds(50)) break;
+      if (dt > std::chrono::microseconds(kWaitSpinUs)) sched_yield();
     }
   }
   return hipStreamSynchronize(h->stream);
@@ -1054,8 +1049,7 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
     return fail(h, O3DS_ERR_CAPACITY, "build_index: the cell-sorted points exceed 2^32 bytes less the scan loop's slack (the search addresses them by 32-bit byte offsets)");
   double mn[3], mx[3];
   int rc = O3DS_OK;
-  static const bool no_box_cache = ab_getenv("O3DS_NO_BOX_CACHE") != nullptr;  // debugging aid: always reduce
-  if (box && box->has_box && !no_box_cache) {
+  if (box && box->has_box) {
     for (int a = 0; a < 3; ++a) mn[a] = box->bmn[a], mx[a] = box->bmx[a];
   } else {
     if (n_dev) return fail(h, O3DS_ERR_INVALID_ARG, "build_index: a cloud whose size is still in flight must bring its box");
@@ -1108,7 +1102,6 @@ int build_grid_t(o3ds_handle h, const P4* pts, const P4* nrm, size_t n, double c
   span_mark(h, kSpanIndexBuild);
   HIP_TRY(hipGetLastError());
   h->cells_clean = true;  // (stream order: whoever counts next runs after the scatter)
-  dbg_sync(h, 2);
   g.cell_start = cell_start;
   *out_grid = g;
   *out_cell_start = cell_start;
@@ -1132,11 +1125,7 @@ int build_index_t(o3ds_handle h, CloudRec& c, double cell) {
   return O3DS_OK;
 }
 
-// grid cell of a registration target = max_correspondence_distance / this (O3DS_INDEX_CELL_DIV: tuning experiments)
-double index_cell_div() {
-  static const double d = ab_getenv("O3DS_INDEX_CELL_DIV") ? std::max(1.0, atof(ab_getenv("O3DS_INDEX_CELL_DIV"))) : 4.0;
-  return d;
-}
+constexpr double kIndexCellDiv = 4.0;  // grid cell of a registration target = max_correspondence_distance / this
 
 int build_index(o3ds_handle h, CloudRec& c, double cell) { return DISPATCH(c.precision, build_index_t, h, c, cell); }
 
@@ -1236,11 +1225,9 @@ int d2h_copy_widen(o3ds_handle h, double* h_dst, const float* d_src, size_t coun
   }
   return O3DS_OK;
 }
-static const bool kNarrowOnHost = ab_getenv("O3DS_NO_HOST_NARROW") == nullptr;  // A/B switch
-
 template <typename P4>
 int upload_array_t(o3ds_handle h, const double* host, size_t n, P4* d_out) {  // host double[3n] -> device P4[n]
-  if (std::is_same<P4, P4f>::value && kNarrowOnHost && sizeof(double) * 3 * n >= kStageMin) {
+  if (std::is_same<P4, P4f>::value && sizeof(double) * 3 * n >= kStageMin) {
     float* stage = nullptr;
     TMP_ALLOC(stage, sizeof(float) * 3 * n);
     const int rcc = h2d_copy_narrow(h, stage, host, 3 * n);
@@ -1257,7 +1244,7 @@ int upload_array_t(o3ds_handle h, const double* host, size_t n, P4* d_out) {  //
 }
 template <typename P4>
 int download_array_t(o3ds_handle h, const P4* d_in, size_t n, double* host) {  // device P4[n] -> host double[3n]; complete on return
-  if (std::is_same<P4, P4f>::value && kNarrowOnHost && sizeof(double) * 3 * n >= kStageMin) {
+  if (std::is_same<P4, P4f>::value && sizeof(double) * 3 * n >= kStageMin) {
     float* stage = nullptr;
     TMP_ALLOC(stage, sizeof(float) * 3 * n);
     unpack_kernel<P4, float><<<grid_for(n), kBlock, 0, h->stream>>>(d_in, n, stage);
@@ -1308,6 +1295,31 @@ o3ds_cloud add_cloud(o3ds_handle h, CloudRec&& c) {
   if (c.pre_slot >= 0) h->rec_owner[c.pre_slot] = id;
   h->clouds.emplace(id, std::move(c));
   return id;
+}
+// a new cloud as the result of a call: fill(cloud) makes it; freed if that fails, registered under a new id in *out otherwise
+template <typename F>
+int new_cloud(o3ds_handle h, o3ds_cloud* out, F&& fill) {
+  CloudRec c;
+  CloudGuard c_guard(h, c);
+  const int rc = fill(c);
+  if (rc) return rc;
+  if (out) {  // (null: an output the caller did not ask for)
+    c_guard.release();
+    *out = add_cloud(h, std::move(c));
+  }
+  return O3DS_OK;
+}
+// device copies of a cloud's arrays (n elements each; nrm and col may be null) into the arrays of the new cloud `o`, which they are allocated for
+int copy_arrays(o3ds_handle h, CloudRec& o, size_t n, const void* pts, const void* nrm, const void* col) {
+  const size_t bytes = p4_size(o.precision) * n;
+  const void* from[3] = {pts, nrm, col};
+  void** to[3] = {&o.pts, &o.nrm, &o.col};
+  for (int k = 0; k < 3; ++k)
+    if (from[k]) {
+      HIP_TRY(dev_alloc(h, to[k], bytes));
+      HIP_TRY(hipMemcpyAsync(*to[k], from[k], bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
+  return O3DS_OK;
 }
 
 const double kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -1626,9 +1638,8 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   int rc = validate_icp(h, src, tgt, params);
   if (rc) return rc;
   const double r_hint = params->max_correspondence_distance;
-  static const double reuse_max = ab_getenv("O3DS_INDEX_REUSE_MAX") ? atof(ab_getenv("O3DS_INDEX_REUSE_MAX")) : 0.75;  // tuning experiments
-  if (!tgt->has_index || (tgt->nrm && !tgt->snrm) || (tgt->index_byproduct && (tgt->grid.cell < r_hint / 8.0 || tgt->grid.cell > r_hint * reuse_max))) {
-    rc = build_index(h, *tgt, params->max_correspondence_distance / index_cell_div());
+  if (!tgt->has_index || (tgt->nrm && !tgt->snrm) || (tgt->index_byproduct && (tgt->grid.cell < r_hint / 8.0 || tgt->grid.cell > r_hint * 0.75))) {
+    rc = build_index(h, *tgt, params->max_correspondence_distance / kIndexCellDiv);
     if (rc) return rc;
   }
   rc = maybe_build_replica(h, *tgt);
@@ -2012,14 +2023,7 @@ int o3ds_cloud_upload(o3ds_handle h, const double* xyz, const double* normals, s
   if (!out || (n > 0 && !xyz)) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_upload: null argument");
   if (n > 0x7fffffffull) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_upload: more than 2^31-1 points");
   HIP_TRY(hipSetDevice(h->device));
-  CloudRec c;
-  int rc = DISPATCH(h->precision, upload_t, h, xyz, normals, n, c);
-  if (rc) {
-    free_cloud(h, c);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(c));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& c) { return DISPATCH(h->precision, upload_t, h, xyz, normals, n, c); });
 }
 
 int o3ds_cloud_upload_f32(o3ds_handle h, const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y, size_t off_z,
@@ -2030,103 +2034,97 @@ int o3ds_cloud_upload_f32(o3ds_handle h, const void* data, size_t n, size_t poin
   if (point_step < 12 || off_x + 4 > point_step || off_y + 4 > point_step || off_z + 4 > point_step)
     return fail(h, O3DS_ERR_INVALID_ARG, "cloud_upload_f32: x/y/z fields do not fit the point step");
   HIP_TRY(hipSetDevice(h->device));
-  CloudRec c;
-  CloudGuard c_guard(h, c);
-  c.n = n;
-  c.precision = h->precision;
-  if (n > 0) {
-    // The whole ingest runs on the handle's COPY stream -- DMA of the records, unpack, box -- and the call returns with it queued: the
-    // scan crosses PCIe while the frame before it is still being registered and merged on the handle's stream, whose first use of the
-    // cloud waits for an event (cloud_ready), not the host.  The points live in an ingest buffer (free_points).
-    const size_t psz = p4_size(h->precision), bytes = n * point_step;
-    // a buffer nothing on the handle's stream still reads (its "freed" event has passed): the ingest must not queue behind the frame
-    // that used the buffer last -- that frame is exactly what it is meant to overlap with.  Up to four buffers before one is waited for.
-    int bi = -1, idle = -1;
-    for (size_t k = 0; k < h->ingest_bufs.size(); ++k) {
-      o3ds_context::IngestBuf& cand = h->ingest_bufs[k];
-      if (cand.in_use) continue;
-      if (idle < 0) idle = (int)k;
-      if (cand.pts_bytes >= psz * n && (!cand.freed || hipEventQuery(cand.freed) == hipSuccess)) {
-        bi = (int)k;
-        break;
+  return new_cloud(h, out, [&](CloudRec& c) -> int {
+    c.n = n;
+    c.precision = h->precision;
+    if (n > 0) {
+      // The whole ingest runs on the handle's COPY stream -- DMA of the records, unpack, box -- and the call returns with it queued: the
+      // scan crosses PCIe while the frame before it is still being registered and merged on the handle's stream, whose first use of the
+      // cloud waits for an event (cloud_ready), not the host.  The points live in an ingest buffer (free_points).
+      const size_t psz = p4_size(h->precision), bytes = n * point_step;
+      // a buffer nothing on the handle's stream still reads (its "freed" event has passed): the ingest must not queue behind the frame
+      // that used the buffer last -- that frame is exactly what it is meant to overlap with.  Up to four buffers before one is waited for.
+      int bi = -1, idle = -1;
+      for (size_t k = 0; k < h->ingest_bufs.size(); ++k) {
+        o3ds_context::IngestBuf& cand = h->ingest_bufs[k];
+        if (cand.in_use) continue;
+        if (idle < 0) idle = (int)k;
+        if (cand.pts_bytes >= psz * n && (!cand.freed || hipEventQuery(cand.freed) == hipSuccess)) {
+          bi = (int)k;
+          break;
+        }
       }
-    }
-    (void)hipGetLastError();  // (hipErrorNotReady of a pending event is not an error)
-    if (bi < 0) {
-      if (h->ingest_bufs.size() < 4 || idle < 0) {
-        h->ingest_bufs.emplace_back();
-        bi = (int)h->ingest_bufs.size() - 1;
-      } else {
-        bi = idle;  // too small (grown below) or still being read (waited for on the copy stream)
+      (void)hipGetLastError();  // (hipErrorNotReady of a pending event is not an error)
+      if (bi < 0) {
+        if (h->ingest_bufs.size() < 4 || idle < 0) {
+          h->ingest_bufs.emplace_back();
+          bi = (int)h->ingest_bufs.size() - 1;
+        } else {
+          bi = idle;  // too small (grown below) or still being read (waited for on the copy stream)
+        }
       }
-    }
-    o3ds_context::IngestBuf& b = h->ingest_bufs[(size_t)bi];
-    if (b.pts_bytes < psz * n) {
-      if (b.pts) {
-        if (b.freed) HIP_TRY(hipEventSynchronize(b.freed));
+      o3ds_context::IngestBuf& b = h->ingest_bufs[(size_t)bi];
+      if (b.pts_bytes < psz * n) {
+        if (b.pts) {
+          if (b.freed) HIP_TRY(hipEventSynchronize(b.freed));
+          HIP_TRY(hipStreamSynchronize(h->copy_stream));
+          (void)hipFree(b.pts);
+          b.pts = nullptr;
+          b.pts_bytes = 0;
+        }
+        const size_t want = psz * (n + n / 8);
+        if (hipMalloc(&b.pts, want) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: ingest buffer allocation failed");
+        b.pts_bytes = want;
+      }
+      if (!b.box) {
+        if (hipMalloc((void**)&b.box, 64) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: box record allocation failed");
+        unsigned long long arm[8] = {0};
+        for (int a = 0; a < 6; ++a) arm[a] = order_bits(a < 3 ? 1e300 : -1e300);
+        HIP_TRY(hipMemcpy(b.box, arm, sizeof(arm), hipMemcpyHostToDevice));
+      }
+      if (h->raw_cap < bytes) {
         HIP_TRY(hipStreamSynchronize(h->copy_stream));
-        (void)hipFree(b.pts);
-        b.pts = nullptr;
-        b.pts_bytes = 0;
+        if (h->d_raw) (void)hipFree(h->d_raw);
+        h->d_raw = nullptr;
+        h->raw_cap = 0;
+        if (hipMalloc((void**)&h->d_raw, bytes + bytes / 8) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: staging allocation failed");
+        h->raw_cap = bytes + bytes / 8;
       }
-      const size_t want = psz * (n + n / 8);
-      if (hipMalloc(&b.pts, want) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: ingest buffer allocation failed");
-      b.pts_bytes = want;
+      if (b.freed) HIP_TRY(hipStreamWaitEvent(h->copy_stream, b.freed, 0));  // whatever still read the buffer's last cloud on the handle's stream
+      // the records: straight DMA from memory the runtime knows as pinned (o3ds_pinned_alloc, hipHostRegister: read asynchronously, see the
+      // header), through the handle's pinned ring otherwise (the caller's buffer is consumed when this returns)
+      hipPointerAttribute_t attr{};
+      const bool pinned = hipPointerGetAttributes(&attr, data) == hipSuccess && attr.type == hipMemoryTypeHost;
+      (void)hipGetLastError();  // (a pageable pointer makes the query fail: not an error of ours)
+      if (pinned) {
+        HIP_TRY(hipMemcpyAsync(h->d_raw, data, bytes, hipMemcpyHostToDevice, h->copy_stream));
+      } else {
+        const int rcc = h2d_copy(h, h->d_raw, data, bytes, h->copy_stream);
+        if (rcc) return rcc;
+      }
+      b.in_use = true;
+      c.pts = b.pts;
+      c.ingest_buf = bi;
+      // the box of the points inside the volume the handle last cropped with rides on the unpack (pack_strided_f32_box_kernel)
+      const int box_slot = h->pre_crop_valid ? take_rec(h) : -1;  // (-1: every record is held by a map -- the box is reduced when it is asked for)
+      if (box_slot >= 0) {
+        c.pre_slot = box_slot;
+        c.pre_seq = ++h->rec_seq;
+        c.pre_crop = h->pre_crop;
+        o3ds_context::PinRec* rec = h->h_rec_dev + c.pre_slot;
+        WITH_P4(h->precision, pack_strided_f32_box_kernel<P4><<<grid_for(n, 1024), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z,
+                                                                                                                 (P4*)c.pts, c.pre_crop, b.box));
+        box_publish_kernel<<<1, 64, 0, h->copy_stream>>>(b.box, rec->box, &rec->seq, c.pre_seq);
+      } else {
+        WITH_P4(h->precision, pack_strided_f32_kernel<P4><<<grid_for(n), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z, (P4*)c.pts));
+      }
+      HIP_TRY(hipGetLastError());
+      c.ingest_ev = take_event(h);
+      if (!c.ingest_ev) return fail(h, O3DS_ERR_HIP, "cloud_upload_f32: event creation failed");
+      HIP_TRY(hipEventRecord(c.ingest_ev, h->copy_stream));
     }
-    if (!b.box) {
-      if (hipMalloc((void**)&b.box, 64) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: box record allocation failed");
-      unsigned long long arm[8] = {0};
-      for (int a = 0; a < 6; ++a) arm[a] = order_bits(a < 3 ? 1e300 : -1e300);
-      HIP_TRY(hipMemcpy(b.box, arm, sizeof(arm), hipMemcpyHostToDevice));
-    }
-    if (h->raw_cap < bytes) {
-      HIP_TRY(hipStreamSynchronize(h->copy_stream));
-      if (h->d_raw) (void)hipFree(h->d_raw);
-      h->d_raw = nullptr;
-      h->raw_cap = 0;
-      if (hipMalloc((void**)&h->d_raw, bytes + bytes / 8) != hipSuccess) return fail(h, O3DS_ERR_OOM, "cloud_upload_f32: staging allocation failed");
-      h->raw_cap = bytes + bytes / 8;
-    }
-    if (b.freed) HIP_TRY(hipStreamWaitEvent(h->copy_stream, b.freed, 0));  // whatever still read the buffer's last cloud on the handle's stream
-    // the records: straight DMA from memory the runtime knows as pinned (o3ds_pinned_alloc, hipHostRegister: read asynchronously, see the
-    // header), through the handle's pinned ring otherwise (the caller's buffer is consumed when this returns)
-    hipPointerAttribute_t attr{};
-    const bool pinned = hipPointerGetAttributes(&attr, data) == hipSuccess && attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();  // (a pageable pointer makes the query fail: not an error of ours)
-    if (pinned) {
-      HIP_TRY(hipMemcpyAsync(h->d_raw, data, bytes, hipMemcpyHostToDevice, h->copy_stream));
-    } else {
-      const int rcc = h2d_copy(h, h->d_raw, data, bytes, h->copy_stream);
-      if (rcc) return rcc;
-    }
-    b.in_use = true;
-    c.pts = b.pts;
-    c.ingest_buf = bi;
-    // the box of the points inside the volume the handle last cropped with rides on the unpack (pack_strided_f32_box_kernel)
-    const int box_slot = h->pre_crop_valid ? take_rec(h) : -1;  // (-1: every record is held by a map -- the box is reduced when it is asked for)
-    if (box_slot >= 0) {
-      c.pre_slot = box_slot;
-      c.pre_seq = ++h->rec_seq;
-      c.pre_crop = h->pre_crop;
-      o3ds_context::PinRec* rec = h->h_rec_dev + c.pre_slot;
-      if (h->precision == O3DS_PRECISION_F64)
-        pack_strided_f32_box_kernel<P4d><<<grid_for(n, 1024), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z, (P4d*)c.pts, c.pre_crop, b.box);
-      else
-        pack_strided_f32_box_kernel<P4f><<<grid_for(n, 1024), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z, (P4f*)c.pts, c.pre_crop, b.box);
-      box_publish_kernel<<<1, 64, 0, h->copy_stream>>>(b.box, rec->box, &rec->seq, c.pre_seq);
-    } else if (h->precision == O3DS_PRECISION_F64) {
-      pack_strided_f32_kernel<P4d><<<grid_for(n), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z, (P4d*)c.pts);
-    } else {
-      pack_strided_f32_kernel<P4f><<<grid_for(n), kBlock, 0, h->copy_stream>>>(h->d_raw, n, point_step, off_x, off_y, off_z, (P4f*)c.pts);
-    }
-    HIP_TRY(hipGetLastError());
-    c.ingest_ev = take_event(h);
-    if (!c.ingest_ev) return fail(h, O3DS_ERR_HIP, "cloud_upload_f32: event creation failed");
-    HIP_TRY(hipEventRecord(c.ingest_ev, h->copy_stream));
-  }
-  c_guard.release();
-  *out = add_cloud(h, std::move(c));
-  return O3DS_OK;
+    return O3DS_OK;
+  });
 }
 
 int o3ds_pinned_alloc(o3ds_handle h, size_t bytes, void** out) {
@@ -2155,9 +2153,7 @@ int o3ds_cloud_free(o3ds_handle h, o3ds_cloud id) {
   auto it = h->clouds.find(id);
   if (it == h->clouds.end()) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_free: unknown cloud id");
   // no host synchronisation: the buffers go back to the handle's allocator behind whatever still reads them on this stream
-  // (o3ds_set_stream synchronises the stream it leaves).  O3DS_SYNC_ON_FREE=1 restores the wait (six of them per lidar frame).
-  static const bool sync_on_free = ab_getenv("O3DS_SYNC_ON_FREE") != nullptr;
-  if (sync_on_free) (void)hipStreamSynchronize(h->stream);
+  // (o3ds_set_stream synchronises the stream it leaves)
   free_cloud(h, it->second);
   h->clouds.erase(it);
   return O3DS_OK;
@@ -2254,12 +2250,8 @@ int o3ds_cloud_download_f32(o3ds_handle h, o3ds_cloud id, void* data, size_t cap
   HIP_TRY(hipMemsetAsync(d_raw, 0, bytes, h->stream));  // padding and the fields this path does not carry
   const size_t on = off_normal == O3DS_NO_FIELD ? kNoField : off_normal;
   const size_t oc = off_rgb == O3DS_NO_FIELD ? kNoField : off_rgb;
-  if (c->precision == O3DS_PRECISION_F64)
-    unpack_strided_f32_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4d*)c->pts, (const P4d*)c->nrm, (const P4d*)c->col, c->n,
-                                                                            point_step, off_x, off_y, off_z, on, oc, rgb_rounding, d_raw);
-  else
-    unpack_strided_f32_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4f*)c->pts, (const P4f*)c->nrm, (const P4f*)c->col, c->n,
-                                                                            point_step, off_x, off_y, off_z, on, oc, rgb_rounding, d_raw);
+  WITH_P4(c->precision, unpack_strided_f32_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4*)c->pts, (const P4*)c->nrm, (const P4*)c->col, c->n,
+                                                                                                 point_step, off_x, off_y, off_z, on, oc, rgb_rounding, d_raw));
   HIP_TRY(hipGetLastError());
   return d2h_copy(h, data, d_raw, bytes);
 }
@@ -2284,10 +2276,7 @@ int o3ds_cloud_set_colors_from_records(o3ds_handle h, o3ds_cloud id, const void*
     if (rcc) return rcc;
   }
   HIP_TRY(dev_alloc(h, (void**)&c->col, p4_size(c->precision) * c->n));
-  if (c->precision == O3DS_PRECISION_F64)
-    colors_from_records_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>(d_raw, c->n, point_step, off_field, kind, (P4d*)c->col);
-  else
-    colors_from_records_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>(d_raw, c->n, point_step, off_field, kind, (P4f*)c->col);
+  WITH_P4(c->precision, colors_from_records_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>(d_raw, c->n, point_step, off_field, kind, (P4*)c->col));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));  // `data` may be reused by the caller
   return O3DS_OK;
@@ -2309,10 +2298,7 @@ int o3ds_cloud_set_colors(o3ds_handle h, o3ds_cloud id, const double* rgb) {
     if (rcc) return rcc;
   }
   HIP_TRY(dev_alloc(h, (void**)&c->col, p4_size(c->precision) * c->n));
-  if (c->precision == O3DS_PRECISION_F64)
-    pack_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>(stage, c->n, (P4d*)c->col);
-  else
-    pack_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>(stage, c->n, (P4f*)c->col);
+  WITH_P4(c->precision, pack_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>(stage, c->n, (P4*)c->col));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));  // rgb may be released by the caller
   return O3DS_OK;
@@ -2335,10 +2321,7 @@ int o3ds_cloud_get_colors(o3ds_handle h, o3ds_cloud id, double* rgb, size_t capa
   if (capacity < c->n) return fail(h, O3DS_ERR_CAPACITY, "cloud_get_colors: capacity < cloud size");
   double* stage = nullptr;
   TMP_ALLOC(stage, sizeof(double) * 3 * c->n);
-  if (c->precision == O3DS_PRECISION_F64)
-    unpack_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4d*)c->col, c->n, stage);
-  else
-    unpack_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4f*)c->col, c->n, stage);
+  WITH_P4(c->precision, unpack_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4*)c->col, c->n, stage));
   HIP_TRY(hipGetLastError());
   return d2h_copy(h, rgb, stage, sizeof(double) * 3 * c->n);
 }
@@ -2348,7 +2331,7 @@ int o3ds_cloud_build_index(o3ds_handle h, o3ds_cloud id, double max_corr_hint, d
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, id);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "build_index: unknown cloud id");
-  double cell = cell_size > 0.0 ? cell_size : max_corr_hint / index_cell_div();
+  double cell = cell_size > 0.0 ? cell_size : max_corr_hint / kIndexCellDiv;
   if (!(cell > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "build_index: need cell_size > 0 or max_corr_hint > 0");
   int rc = build_index(h, *c, cell);
   return rc;
@@ -2800,7 +2783,6 @@ int crop_t(o3ds_handle h, const CloudRec& in, const CropDev& crop, CloudRec& out
     rc = compact_cloud<P4>(h, in, in.n, flags, pos, 1, out.n, &out.pts, &out.nrm, &out.col);
     if (rc) return rc;
   }
-  dbg_sync(h, 4);
   return O3DS_OK;
 }
 
@@ -2894,7 +2876,6 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
       vox_mean_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)in.col, nullptr, m_ref, order, run_next, run_len, starts, piece, 1, (P4*)out.col,
                                                                nullptr, t);
     HIP_TRY(hipGetLastError());
-    dbg_sync(h, 8);
     return O3DS_OK;
   }
   unsigned long long *k0 = nullptr, *k1 = nullptr, *d_scalar = nullptr;
@@ -3026,7 +3007,6 @@ int voxel_reduce_t(o3ds_handle h, const CloudRec& in, int mode, double voxel, co
       segment_last_kernel<P4><<<grid_for(out.n), kBlock, 0, h->stream>>>((const P4*)in.col, k1, v1, seg_start, out.n, n, n_pass, (P4*)out.col);
   }
   HIP_TRY(hipGetLastError());
-  dbg_sync(h, 8);
   return O3DS_OK;
 }
 
@@ -3070,22 +3050,15 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
   tmp.pts = c.pts;  // borrowed
   tmp.lazy_slot = c.lazy_slot;  // (borrowed as well: build_index_t hands the device word to its kernels)
   box_copy(tmp, c);
+  IndexGuard tmp_guard(h, tmp);
   int rc = O3DS_OK;
   if (reuse) {
     ++h->nrm_age;
     rc = build_index_t<P4>(h, tmp, h->nrm_cell);
-    if (rc) {
-      tmp.pts = nullptr;
-      free_index(h, tmp);
-      return rc;
-    }
+    if (rc) return rc;
   } else {
     rc = build_index_t<P4>(h, tmp, radius / 8.0);
-    if (rc) {
-      tmp.pts = nullptr;
-      free_index(h, tmp);
-      return rc;
-    }
+    if (rc) return rc;
     const size_t ncell = (size_t)tmp.grid.nx * tmp.grid.ny * tmp.grid.nz;
     unsigned long long* d_cnt = nullptr;
     TMP_ALLOC(d_cnt, sizeof(unsigned long long));
@@ -3093,21 +3066,12 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
     count_occupied_kernel<<<grid_for(ncell), kBlock, 0, h->stream>>>(tmp.cell_start, ncell, d_cnt);
     unsigned long long occ = 0;
     rc = read_back(h, {{&occ, d_cnt, sizeof(occ)}});
-    if (rc) {
-      tmp.pts = nullptr;
-      free_index(h, tmp);
-      return rc;
-    }
+    if (rc) return rc;
     const double avg = occ ? (double)c.n / (double)occ : 1.0;
-    static const double cell_scale = ab_getenv("O3DS_NRM_CELL_SCALE") ? atof(ab_getenv("O3DS_NRM_CELL_SCALE")) : 1.0;  // tuning experiments
-    double cell = cell_scale * tmp.grid.cell * std::sqrt(std::max(1.0, (double)max_nn) / (3.14159265358979 * avg));
+    double cell = tmp.grid.cell * std::sqrt(std::max(1.0, (double)max_nn) / (3.14159265358979 * avg));
     cell = std::min(std::max(cell, radius / 64.0), radius);
     rc = build_index_t<P4>(h, tmp, cell);
-    if (rc) {
-      tmp.pts = nullptr;
-      free_index(h, tmp);
-      return rc;
-    }
+    if (rc) return rc;
     h->nrm_cell = tmp.grid.cell;
     h->nrm_radius = radius;
     h->nrm_knn = max_nn;
@@ -3118,38 +3082,12 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
   // o3ds_map_insert_scan writes both arrays behind the last point)
   if (!c.nrm) HIP_TRY(dev_alloc(h, (void**)&c.nrm, sizeof(P4) * std::max(c.n, c.cap)));
   const int rmax = std::max(1, (int)std::ceil(radius / tmp.grid.cell));
-  static const bool nrm_debug = ab_getenv("O3DS_NRM_DEBUG") != nullptr;  // debugging aid: where a fault happens
-  if (nrm_debug) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    fprintf(stderr, "[normals] n %zu radius %g max_nn %d reuse %d grid %d x %d x %d cell %g rmax %d (index built: %s)\n", c.n, radius, max_nn, (int)reuse,
-            tmp.grid.nx, tmp.grid.ny, tmp.grid.nz, tmp.grid.cell, rmax, hipGetErrorString(e));
-    const size_t ncell = (size_t)tmp.grid.nx * tmp.grid.ny * tmp.grid.nz;
-    std::vector<int> hcs(ncell + 1);
-    (void)hipMemcpy(hcs.data(), tmp.cell_start, sizeof(int) * (ncell + 1), hipMemcpyDeviceToHost);
-    size_t bad = 0, first = 0;
-    for (size_t i = 0; i < ncell; ++i)
-      if (hcs[i + 1] < hcs[i]) {
-        if (!bad) first = i;
-        ++bad;
-      }
-    fprintf(stderr, "[normals] cell_start: first %d last %d (n %zu), descents %zu", hcs[0], hcs[ncell], c.n, bad);
-    if (bad) fprintf(stderr, " first at cell %zu (block %zu): %d -> %d", first, (first + 1) / 1024, hcs[first], hcs[first + 1]);
-    fprintf(stderr, "\n");
-  }
   // 16 lanes per point, 16 points per 256-thread workgroup (normals_kernel.hpp), then a thread per point for the eigen-solve; the instantiation is picked by max_nn
   {
     const P4* p_pts = (const P4*)c.pts;
     const P4* p_sp = (const P4*)tmp.spts;
     P4* p_out = (P4*)c.nrm;
     const unsigned int gsz = (unsigned int)((c.n + o3ds::kNrmPointsPerBlock - 1) / o3ds::kNrmPointsPerBlock);
-#ifdef O3DS_NRM_CHECK
-    unsigned long long* d_ws = nullptr;
-    if (ab_getenv("O3DS_NRM_STATS_FILE")) {
-      HIP_TRY(hipMalloc((void**)&d_ws, sizeof(unsigned long long) * o3ds::kNrmStatWords * ((size_t)o3ds::kNrmWaves * gsz)));
-      HIP_TRY(hipMemset(d_ws, 0, sizeof(unsigned long long) * o3ds::kNrmStatWords * ((size_t)o3ds::kNrmWaves * gsz)));
-    }
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(o3ds::g_nrm_wave_stats), &d_ws, sizeof(d_ws)));
-#endif
     double* d_sums = nullptr;
     int* d_cnts = nullptr;
     TMP_ALLOC(d_sums, sizeof(double) * 9 * c.n);
@@ -3164,42 +3102,12 @@ int normals_t(o3ds_handle h, CloudRec& c, double radius, int max_nn, bool knn_ra
       normals_kernel<P4, 128><<<gsz, 64 * o3ds::kNrmWaves, 0, h->stream>>>(p_pts, c.n, tmp.grid, p_sp, radius, max_nn, rmax, d_sums, d_cnts, n_dev);
     // the grid, the cell-ordered points and (written here) the cell-ordered normals are a complete nearest-neighbour index of the cloud:
     // kept, so that a registration against this cloud (scan-to-scan odometry: the previous scan) does not build another one
-    if (dev_alloc(h, (void**)&tmp.snrm, sizeof(P4) * c.n) != hipSuccess) {
-      tmp.pts = nullptr;
-      free_index(h, tmp);
-      return fail(h, O3DS_ERR_OOM, "estimate_normals: out of device memory");
-    }
+    if (dev_alloc(h, (void**)&tmp.snrm, sizeof(P4) * c.n) != hipSuccess) return fail(h, O3DS_ERR_OOM, "estimate_normals: out of device memory");
     normals_finish_kernel<P4><<<(unsigned int)((c.n + 255) / 256), 256, 0, h->stream>>>(p_sp, c.n, d_sums, d_cnts, p_out, knn_raw ? 1 : 0, (P4*)tmp.snrm, n_dev);
     span_mark(h, kSpanNormalsKernels);
   }
   HIP_TRY(hipGetLastError());
-  dbg_sync(h, 16);
-#ifdef O3DS_NRM_CHECK
-  if (const char* sf = ab_getenv("O3DS_NRM_STATS_FILE")) {
-    const unsigned int gsz = (unsigned int)((c.n + o3ds::kNrmPointsPerBlock - 1) / o3ds::kNrmPointsPerBlock);
-    unsigned long long* d_ws = nullptr;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpyFromSymbol(&d_ws, HIP_SYMBOL(o3ds::g_nrm_wave_stats), sizeof(d_ws)));
-    std::vector<unsigned long long> ws((size_t)o3ds::kNrmStatWords * ((size_t)o3ds::kNrmWaves * gsz));
-    HIP_TRY(hipMemcpy(ws.data(), d_ws, sizeof(unsigned long long) * ws.size(), hipMemcpyDeviceToHost));
-    (void)hipFree(d_ws);
-    if (FILE* f = fopen(sf, "wb")) {
-      fwrite(ws.data(), sizeof(unsigned long long), ws.size(), f);
-      fclose(f);
-    }
-  }
-#endif
-  if (nrm_debug) {
-    fprintf(stderr, "[normals] kernel done: %s\n", hipGetErrorString(hipStreamSynchronize(h->stream)));
-#ifdef O3DS_NRM_CHECK
-    unsigned int dbg[8] = {0};
-    (void)hipMemcpyFromSymbol(dbg, HIP_SYMBOL(o3ds::g_nrm_dbg), sizeof(dbg));
-    fprintf(stderr, "[normals] violations: unsorted %u, bad p %u, bad oi %u\n", dbg[0], dbg[1], dbg[2]);
-    const unsigned int zero[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(o3ds::g_nrm_dbg), zero, sizeof(zero));
-#endif
-  }
-  tmp.pts = nullptr;
+  tmp_guard.release();
   box_copy(c, tmp);  // the box an index build reduced is kept for the cloud
   free_index(h, c);  // the cloud's own index (if any) no longer matches its normals
   c.grid = tmp.grid, c.cell_start = tmp.cell_start, c.spts = tmp.spts, c.snrm = tmp.snrm;
@@ -3420,7 +3328,6 @@ int append_t(o3ds_handle h, CloudRec& map, const CloudRec& add) {
     if (keep_col) reindex_copy_kernel<P4><<<grid_for(add.n), kBlock, 0, h->stream>>>((const P4*)add.col, add.n, (P4*)nc, map.n, 0);
   }
   HIP_TRY(hipGetLastError());
-  dbg_sync(h, 32);
   guard.release();
   replace_arrays(h, map, np, nn, nc, n, 0);
   drop_ingest_box(h, map);
@@ -3483,7 +3390,6 @@ int random_down_sample_t(o3ds_handle h, const CloudRec& in, double ratio, unsign
   if (rc) return rc;
   rc = compact_cloud<P4>(h, in, bound, flags, pos, 1, k_bound, &out.pts, &out.nrm, &out.col);
   if (rc) return rc;
-  dbg_sync(h, 4);
   return O3DS_OK;
 }
 
@@ -3604,11 +3510,16 @@ int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const doubl
   return O3DS_OK;
 }
 
-// The tail of every filter that judges point by point: flags[0..n) (flags[n] = 0, the scan's sentinel) -> the croppers' scan and stable
-// compaction into `out` (points, normals and colours in cloud order), the kept indices on request.  pos: n + 1 ints of scratch.
+// The subset of `in` that flags[0..n) keeps (flags[n] = 0, the scan's sentinel), as the new cloud `out`: the croppers' scan and stable
+// compaction (points, normals and colours in cloud order), the kept indices on request.  pos: n + 1 ints of scratch.
 template <typename P4>
 int compact_kept_t(o3ds_handle h, CloudRec& in, size_t n, const int* flags, int* pos, const char* what, CloudRec& out, uint32_t* kept_idx, size_t capacity,
                    size_t* n_kept) {
+  out.precision = in.precision;
+  out.n = 0;
+  box_copy(out, in);  // a subset
+  *n_kept = 0;
+  if (n == 0) return O3DS_OK;
   uint32_t* d_kept = nullptr;
   int rc = exclusive_scan_int(h, flags, pos, n + 1, pub_slot<int>(h, 0));
   if (rc) return rc;
@@ -3632,46 +3543,53 @@ int compact_kept_t(o3ds_handle h, CloudRec& in, size_t n, const int* flags, int*
   }
   return O3DS_OK;
 }
+// A filter that judges point by point states its rule, rule(n, flags) for n > 0 points: flags[0..n) = 1 where a point stays
+template <typename P4, typename Rule>
+int filter_cloud_t(o3ds_handle h, CloudRec& in, const char* what, CloudRec& out, uint32_t* kept_idx, size_t capacity, size_t* n_kept, Rule&& rule) {
+  const size_t n = in.n;
+  int *flags = nullptr, *pos = nullptr;
+  *n_kept = 0;  // (also when the rule fails)
+  if (n) {
+    TMP_ALLOC(flags, sizeof(int) * (n + 1));
+    TMP_ALLOC(pos, sizeof(int) * (n + 1));
+    const int rc = rule(n, flags);
+    if (rc) return rc;
+  }
+  return compact_kept_t<P4>(h, in, n, flags, pos, what, out, kept_idx, capacity, n_kept);
+}
 
 // [O3D] RemoveStatisticalOutliers (mode 0: k = nb_neighbors, v = std_ratio) and RemoveRadiusOutliers (mode 1: k = nb_points, v = radius):
 // the search with the cloud as its own target, the mask, the croppers' stable compaction
 template <typename P4>
 int outlier_filter_t(o3ds_handle h, CloudRec& in, int mode, int k, double v, CloudRec& out, uint32_t* kept_idx, size_t capacity, size_t* n_kept) {
-  out.precision = in.precision;
-  out.n = 0;
-  box_copy(out, in);  // a subset
-  *n_kept = 0;
-  const size_t n = in.n;
-  if (n == 0) return O3DS_OK;
-  int *flags = nullptr, *pos = nullptr;
-  uint32_t *d_cnt = nullptr, *d_tot = nullptr;
-  double *d_avg = nullptr, *partial = nullptr, *stat = nullptr;
-  TMP_ALLOC(flags, sizeof(int) * (n + 1));
-  TMP_ALLOC(pos, sizeof(int) * (n + 1));
-  TMP_ALLOC(d_cnt, sizeof(uint32_t) * n);
-  bool empty = false;
-  int rc;
-  if (mode == 0) {
-    TMP_ALLOC(d_avg, sizeof(double) * n);
-    TMP_ALLOC(partial, sizeof(double) * 2 * kCenterChunks);
-    TMP_ALLOC(stat, sizeof(double) * 4);
-    rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, k, 0.0, nullptr, nullptr, d_cnt, nullptr, d_avg, &empty);
-    if (rc) return rc;
-    if (empty) HIP_TRY(hipMemsetAsync(d_avg, 0, sizeof(double) * n, h->stream));  // no list, no valid point
-    stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, nullptr, partial);
-    stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 0, v, stat);
-    stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, stat, partial);
-    stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 1, v, stat);
-    stat_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_avg, n, stat, flags);
-  } else {
-    TMP_ALLOC(d_tot, sizeof(uint32_t) * n);
-    rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, 0, v, nullptr, nullptr, d_cnt, d_tot, nullptr, &empty);
-    if (rc) return rc;
-    if (empty) HIP_TRY(hipMemsetAsync(d_tot, 0, sizeof(uint32_t) * n, h->stream));
-    radius_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_tot, n, (uint32_t)k, flags);
-  }
-  HIP_TRY(hipGetLastError());
-  return compact_kept_t<P4>(h, in, n, flags, pos, "outlier filter", out, kept_idx, capacity, n_kept);
+  return filter_cloud_t<P4>(h, in, "outlier filter", out, kept_idx, capacity, n_kept, [&](size_t n, int* flags) -> int {
+    uint32_t *d_cnt = nullptr, *d_tot = nullptr;
+    double *d_avg = nullptr, *partial = nullptr, *stat = nullptr;
+    TMP_ALLOC(d_cnt, sizeof(uint32_t) * n);
+    bool empty = false;
+    int rc;
+    if (mode == 0) {
+      TMP_ALLOC(d_avg, sizeof(double) * n);
+      TMP_ALLOC(partial, sizeof(double) * 2 * kCenterChunks);
+      TMP_ALLOC(stat, sizeof(double) * 4);
+      rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, k, 0.0, nullptr, nullptr, d_cnt, nullptr, d_avg, &empty);
+      if (rc) return rc;
+      if (empty) HIP_TRY(hipMemsetAsync(d_avg, 0, sizeof(double) * n, h->stream));  // no list, no valid point
+      stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, nullptr, partial);
+      stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 0, v, stat);
+      stat_partial_kernel<<<kCenterChunks, kBlock, 0, h->stream>>>(d_avg, n, stat, partial);
+      stat_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, 1, v, stat);
+      stat_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_avg, n, stat, flags);
+    } else {
+      TMP_ALLOC(d_tot, sizeof(uint32_t) * n);
+      rc = neighbor_launch_t<P4>(h, in, in, nullptr, nullptr, n, 0, v, nullptr, nullptr, d_cnt, d_tot, nullptr, &empty);
+      if (rc) return rc;
+      if (empty) HIP_TRY(hipMemsetAsync(d_tot, 0, sizeof(uint32_t) * n, h->stream));
+      radius_flag_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(d_tot, n, (uint32_t)k, flags);
+    }
+    HIP_TRY(hipGetLastError());
+    return O3DS_OK;
+  });
 }
 
 int outlier_filter(o3ds_handle h, o3ds_cloud in, int mode, int k, double v, const char* what, o3ds_cloud* out, uint32_t* kept_idx, size_t capacity,
@@ -3679,13 +3597,7 @@ int outlier_filter(o3ds_handle h, o3ds_cloud in, int mode, int k, double v, cons
   CloudRec* c = find_cloud(h, in);  // (with its exact size; a persistent map as its array)
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown cloud id");
   if (!out || !n_kept) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": out and n_kept are required");
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  const int rc = DISPATCH(c->precision, outlier_filter_t, h, *c, mode, k, v, o, kept_idx, capacity, n_kept);
-  if (rc) return rc;
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(c->precision, outlier_filter_t, h, *c, mode, k, v, o, kept_idx, capacity, n_kept); });
 }
 }  // namespace
 
@@ -3696,15 +3608,8 @@ int o3ds_crop_cloud(o3ds_handle h, o3ds_cloud in, const o3ds_crop* crop, o3ds_cl
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, in);
   if (!c || !out) return fail(h, O3DS_ERR_INVALID_ARG, "crop_cloud: bad argument");
-  CloudRec o;
   const CropDev cd = to_dev(crop);
-  int rc = DISPATCH(c->precision, crop_t, h, *c, cd, o);
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(c->precision, crop_t, h, *c, cd, o); });
 }
 
 int o3ds_voxel_down_sample(o3ds_handle h, o3ds_cloud in, double voxel_size, o3ds_cloud* out) {
@@ -3712,21 +3617,14 @@ int o3ds_voxel_down_sample(o3ds_handle h, o3ds_cloud in, double voxel_size, o3ds
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, in);
   if (!c || !out) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_down_sample: bad argument");
-  CloudRec o;
-  int rc;
-  if (voxel_size <= 0.0) {  // o3d_slam::voxelize returns the cloud unchanged (helpers.cpp:108-110)
-    o.precision = c->precision;
-    rc = DISPATCH(c->precision, append_t, h, o, *c);
-  } else {
+  return new_cloud(h, out, [&](CloudRec& o) {
+    if (voxel_size <= 0.0) {  // o3d_slam::voxelize returns the cloud unchanged (helpers.cpp:108-110)
+      o.precision = c->precision;
+      return DISPATCH(c->precision, append_t, h, o, *c);
+    }
     CropDev none{};
-    rc = DISPATCH(c->precision, voxel_reduce_t, h, *c, 0, voxel_size, none, o);
-  }
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+    return DISPATCH(c->precision, voxel_reduce_t, h, *c, 0, voxel_size, none, o);
+  });
 }
 
 int o3ds_crop_voxel_down_sample(o3ds_handle h, o3ds_cloud in, const o3ds_crop* crop, double voxel_size, o3ds_cloud* out) {
@@ -3735,15 +3633,8 @@ int o3ds_crop_voxel_down_sample(o3ds_handle h, o3ds_cloud in, const o3ds_crop* c
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, in);
   if (!c || !out) return fail(h, O3DS_ERR_INVALID_ARG, "crop_voxel_down_sample: bad argument");
-  CloudRec o;
   const CropDev cd = to_dev(crop);
-  const int rc = DISPATCH(c->precision, voxel_reduce_t, h, *c, 0, voxel_size, cd, o, true);
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(c->precision, voxel_reduce_t, h, *c, 0, voxel_size, cd, o, true); });
 }
 
 int o3ds_estimate_normals(o3ds_handle h, o3ds_cloud id, double radius, int max_nn) {
@@ -3769,22 +3660,20 @@ int o3ds_select_by_index(o3ds_handle h, o3ds_cloud in, const uint32_t* keep_idx,
   if (!c || !out || (m && !keep_idx)) return fail(h, O3DS_ERR_INVALID_ARG, "select_by_index: bad argument");
   for (size_t i = 0; i < m; ++i)
     if (keep_idx[i] >= c->n) return fail(h, O3DS_ERR_INVALID_ARG, "select_by_index: index out of range");
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  o.precision = c->precision;
-  o.n = m;
-  box_copy(o, *c);  // a subset
-  if (m) {
-    uint32_t* d_idx = nullptr;
-    TMP_ALLOC(d_idx, sizeof(uint32_t) * m);
-    HIP_TRY(hipMemcpyAsync(d_idx, keep_idx, sizeof(uint32_t) * m, hipMemcpyHostToDevice, h->stream));
-    const int rc = DISPATCH(c->precision, gather_cloud, h, *c, d_idx, m, o);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));  // keep_idx may be released by the caller
-  }
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) -> int {
+    o.precision = c->precision;
+    o.n = m;
+    box_copy(o, *c);  // a subset
+    if (m) {
+      uint32_t* d_idx = nullptr;
+      TMP_ALLOC(d_idx, sizeof(uint32_t) * m);
+      HIP_TRY(hipMemcpyAsync(d_idx, keep_idx, sizeof(uint32_t) * m, hipMemcpyHostToDevice, h->stream));
+      const int rc = DISPATCH(c->precision, gather_cloud, h, *c, d_idx, m, o);
+      if (rc) return rc;
+      HIP_TRY(hipStreamSynchronize(h->stream));  // keep_idx may be released by the caller
+    }
+    return O3DS_OK;
+  });
 }
 
 int o3ds_random_down_sample(o3ds_handle h, o3ds_cloud in, double ratio, uint64_t seed, o3ds_cloud* out) {
@@ -3796,13 +3685,7 @@ int o3ds_random_down_sample(o3ds_handle h, o3ds_cloud in, double ratio, uint64_t
   if (!(ratio >= 0.0 && ratio <= 1.0))
     return fail(h, O3DS_ERR_INVALID_ARG, "[RandomDownSample] Illegal sampling_ratio, sampling_ratio must be between 0 and 1.");  // [O3D]
   HIP_TRY(hipSetDevice(h->device));
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  int rc = DISPATCH(c->precision, random_down_sample_t, h, *c, ratio, (unsigned long long)seed, o);
-  if (rc) return rc;
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(c->precision, random_down_sample_t, h, *c, ratio, (unsigned long long)seed, o); });
 }
 
 int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_cloud* out) {
@@ -3810,14 +3693,7 @@ int o3ds_transform_cloud(o3ds_handle h, o3ds_cloud in, const double T[16], o3ds_
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, in);
   if (!c || !out || !T) return fail(h, O3DS_ERR_INVALID_ARG, "transform_cloud: bad argument");
-  CloudRec o;
-  int rc = DISPATCH(c->precision, transform_t, h, *c, T, o);
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(c->precision, transform_t, h, *c, T, o); });
 }
 
 int o3ds_cloud_center(o3ds_handle h, o3ds_cloud cloud, double center[3]) {
@@ -3837,10 +3713,7 @@ int o3ds_cloud_center(o3ds_handle h, o3ds_cloud cloud, double center[3]) {
   TMP_ALLOC(partial, sizeof(double) * 3 * kCenterChunks);
   TMP_ALLOC(d_out, sizeof(double) * 3);
   const CountRef cnt = count_ref(h, *c);
-  if (c->precision == O3DS_PRECISION_F64)
-    center_partial_kernel<P4d><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4d*)c->pts, cnt, partial);
-  else
-    center_partial_kernel<P4f><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4f*)c->pts, cnt, partial);
+  WITH_P4(c->precision, center_partial_kernel<P4><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4*)c->pts, cnt, partial));
   center_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, cnt, d_out);
   HIP_TRY(hipGetLastError());
   return read_back(h, {{center, d_out, sizeof(double) * 3}});
@@ -3936,12 +3809,11 @@ int o3ds_cloud_copy_across(o3ds_handle dst, o3ds_handle src, o3ds_cloud src_clou
   CloudRec* c = find_cloud(src, src_cloud);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_copy_across: unknown cloud id on the source handle");
   if (c->n && c->precision != dst->precision) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_copy_across: the handles store points in different precisions");
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  o.precision = c->n ? c->precision : dst->precision;
-  o.n = c->n;
-  box_copy(o, *c);
-  if (c->n) {
+  return new_cloud(h, out, [&](CloudRec& o) -> int {
+    o.precision = c->n ? c->precision : dst->precision;
+    o.n = c->n;
+    box_copy(o, *c);
+    if (c->n == 0) return O3DS_OK;
     // what the source handle queued for this cloud must have happened before the copy reads it: the destination stream waits for
     // an event on the source stream (no host wait); the source cloud must stay alive until the destination stream passed the copy,
     // which the synchronisation below guarantees before this returns
@@ -3951,22 +3823,11 @@ int o3ds_cloud_copy_across(o3ds_handle dst, o3ds_handle src, o3ds_cloud src_clou
     if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
     (void)hipEventDestroy(ev);  // released once it has completed
     HIP_TRY(e);
-    const size_t bytes = p4_size(c->precision) * c->n;
-    HIP_TRY(dev_alloc(h, (void**)&o.pts, bytes));
-    HIP_TRY(hipMemcpyAsync(o.pts, c->pts, bytes, hipMemcpyDeviceToDevice, h->stream));
-    if (c->nrm) {
-      HIP_TRY(dev_alloc(h, (void**)&o.nrm, bytes));
-      HIP_TRY(hipMemcpyAsync(o.nrm, c->nrm, bytes, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if (c->col) {
-      HIP_TRY(dev_alloc(h, (void**)&o.col, bytes));
-      HIP_TRY(hipMemcpyAsync(o.col, c->col, bytes, hipMemcpyDeviceToDevice, h->stream));
-    }
+    const int rc = copy_arrays(h, o, c->n, c->pts, c->nrm, c->col);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+    return O3DS_OK;
+  });
 }
 
 int o3ds_cloud_export_view(o3ds_handle h, o3ds_cloud id, o3ds_cloud_view* out) {
@@ -4009,31 +3870,19 @@ int o3ds_cloud_import_view(o3ds_handle h, const o3ds_cloud_view* v, o3ds_cloud* 
   if (v->n && v->precision != h->precision) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_import_view: the view's cloud is stored in another precision");
   if (v->n && (!v->pts || !v->event)) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_import_view: a released or incomplete view");
   HIP_TRY(hipSetDevice(h->device));
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  o.precision = h->precision;
-  o.n = v->n;
-  o.has_box = v->has_box != 0;
-  o.box_padded = v->has_box == 2;
-  for (int a = 0; a < 3; ++a) o.bmn[a] = v->box_min[a], o.bmx[a] = v->box_max[a];
-  if (v->n) {
+  return new_cloud(h, out, [&](CloudRec& o) -> int {
+    o.precision = h->precision;
+    o.n = v->n;
+    o.has_box = v->has_box != 0;
+    o.box_padded = v->has_box == 2;
+    for (int a = 0; a < 3; ++a) o.bmn[a] = v->box_min[a], o.bmx[a] = v->box_max[a];
+    if (v->n == 0) return O3DS_OK;
     HIP_TRY(hipStreamWaitEvent(h->stream, (hipEvent_t)v->event, 0));  // what the owner queued for the cloud before it exported the view
-    const size_t bytes = p4_size(h->precision) * v->n;
-    HIP_TRY(dev_alloc(h, (void**)&o.pts, bytes));
-    HIP_TRY(hipMemcpyAsync(o.pts, v->pts, bytes, hipMemcpyDeviceToDevice, h->stream));
-    if (v->nrm) {
-      HIP_TRY(dev_alloc(h, (void**)&o.nrm, bytes));
-      HIP_TRY(hipMemcpyAsync(o.nrm, v->nrm, bytes, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if (v->col) {
-      HIP_TRY(dev_alloc(h, (void**)&o.col, bytes));
-      HIP_TRY(hipMemcpyAsync(o.col, v->col, bytes, hipMemcpyDeviceToDevice, h->stream));
-    }
+    const int rc = copy_arrays(h, o, v->n, v->pts, v->nrm, v->col);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));  // the owner may free its cloud as soon as this returns
-  }
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+    return O3DS_OK;
+  });
 }
 
 }  // extern "C" (a helper with default arguments follows)
@@ -4044,12 +3893,11 @@ int voxelize_within_volume_impl(o3ds_handle h, o3ds_cloud map, double voxel_size
   if (!m) return fail(h, O3DS_ERR_INVALID_ARG, "voxelize_within_volume: unknown cloud id");
   if (voxel_size <= 0.0 || m->n == 0) return O3DS_OK;  // helpers.cpp:119-123 / Submap.cpp:139: unchanged
   CloudRec o;
+  CloudGuard o_guard(h, o);
   const CropDev cd = to_dev(crop);
-  int rc = DISPATCH(m->precision, voxel_reduce_t, h, *m, 1, voxel_size, cd, o, false, merge_np, merge_nv);
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
+  const int rc = DISPATCH(m->precision, voxel_reduce_t, h, *m, 1, voxel_size, cd, o, false, merge_np, merge_nv);
+  if (rc) return rc;
+  o_guard.release();
   free_cloud(h, *m);
   *m = o;
   return O3DS_OK;
@@ -4069,7 +3917,7 @@ namespace {
 
 // cell edge of the row-paged index in voxels: the classic index uses max_corr / 4; here a whole number of voxels
 int pm_cell_voxels(double max_corr_hint, double voxel) {
-  const double want = max_corr_hint > 0.0 ? max_corr_hint / index_cell_div() : 2.5 * voxel;
+  const double want = max_corr_hint > 0.0 ? max_corr_hint / kIndexCellDiv : 2.5 * voxel;
   return std::max(1, (int)std::floor(want / voxel + 0.5));
 }
 
@@ -4247,10 +4095,6 @@ int pm_poll(o3ds_handle h, PMapRec* pm, bool block) {
   std::atomic_thread_fence(std::memory_order_acquire);
   const size_t slots = (size_t)r->cnt, dead = (size_t)r->box[1];
   if ((int)r->box[2] != 0) return fail(h, O3DS_ERR_CAPACITY, "persistent map: an internal capacity was exceeded (error " + std::to_string((int)r->box[2]) + ")");
-  static const bool stats = ab_getenv("O3DS_PM_STATS") != nullptr;  // development aid: what the insertions left behind
-  if (stats)
-    fprintf(stderr, "[pm] t %d slots %zu dead %zu pool top %.0f of %d; multi %.0f complex %.0f outside the grid %.0f\n", pm->t, slots, dead, r->box[0],
-            pm->dev.pool_cap, r->box[3], r->box[4], r->box[5]);
   pm->n_upper = slots;
   pm->live_lower = slots - dead;
   pm->pool_top = r->box[0];
@@ -4397,12 +4241,8 @@ int o3ds_cloud_undistort(o3ds_handle h, o3ds_cloud cloud, const double linear_ve
   if (c->n == 0) return O3DS_OK;
   const double* v = linear_velocity;
   const double* w = angular_velocity_rpy;
-  if (c->precision == O3DS_PRECISION_F64)
-    undistort_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>((P4d*)c->pts, c->n, v[0], v[1], v[2], w[0], w[1], w[2], scan_duration,
-                                                                  spinning_clockwise);
-  else
-    undistort_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>((P4f*)c->pts, c->n, v[0], v[1], v[2], w[0], w[1], w[2], scan_duration,
-                                                                  spinning_clockwise);
+  WITH_P4(c->precision, undistort_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>((P4*)c->pts, c->n, v[0], v[1], v[2], w[0], w[1], w[2], scan_duration,
+                                                                                        spinning_clockwise));
   HIP_TRY(hipGetLastError());
   c->vox_first = -1;  // the points moved
   if (c->nrm) {
@@ -4491,14 +4331,7 @@ int o3ds_cloud_export_rows_by_owner(o3ds_handle h, o3ds_cloud cloud, const doubl
 int o3ds_cloud_import_rows(o3ds_handle h, const double* d_rows, size_t n, int has_normals, o3ds_cloud* out) {
   CHECK_HANDLE(h);
   if (!out || (n && !d_rows)) return fail(h, O3DS_ERR_INVALID_ARG, "import_rows: null argument");
-  CloudRec c;
-  const int rc = DISPATCH(h->precision, import_rows_t, h, d_rows, n, has_normals, c);
-  if (rc) {
-    free_cloud(h, c);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(c));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& c) { return DISPATCH(h->precision, import_rows_t, h, d_rows, n, has_normals, c); });
 }
 
 int o3ds_dense_map_size(o3ds_handle h, o3ds_dense_map id, size_t* n_voxels) {
@@ -4514,14 +4347,7 @@ int o3ds_dense_map_to_cloud(o3ds_handle h, o3ds_dense_map id, o3ds_cloud* out) {
   ArenaScope arena_scope(h);
   auto it = h->dense_maps.find(id);
   if (it == h->dense_maps.end() || !out) return fail(h, O3DS_ERR_INVALID_ARG, "dense_map_to_cloud: bad argument");
-  CloudRec o;
-  const int rc = DISPATCH(h->precision, dense_to_cloud_t, h, it->second, o);
-  if (rc) {
-    free_cloud(h, o);
-    return rc;
-  }
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) { return DISPATCH(h->precision, dense_to_cloud_t, h, it->second, o); });
 }
 
 int o3ds_dense_map_transform(o3ds_handle h, o3ds_dense_map id, const double T[16]) {
@@ -4563,10 +4389,7 @@ int o3ds_dense_map_count_occupied(o3ds_handle h, o3ds_dense_map id, o3ds_cloud c
   unsigned long long* d_hits = nullptr;
   TMP_ALLOC(d_hits, sizeof(unsigned long long));
   HIP_TRY(hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), h->stream));
-  if (c->precision == O3DS_PRECISION_F64)
-    dense_probe_kernel<P4d><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4d*)c->pts, c->n, M, 1.0 / d.voxel, d.dev, d_hits);
-  else
-    dense_probe_kernel<P4f><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4f*)c->pts, c->n, M, 1.0 / d.voxel, d.dev, d_hits);
+  WITH_P4(c->precision, dense_probe_kernel<P4><<<grid_for(c->n), kBlock, 0, h->stream>>>((const P4*)c->pts, c->n, M, 1.0 / d.voxel, d.dev, d_hits));
   HIP_TRY(hipGetLastError());
   unsigned long long hits = 0;
   {
@@ -4622,15 +4445,11 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
       pm->rec_seq = ++h->rec_seq;
       o3ds_context::PinRec* rec = h->h_rec_dev + pm->rec_slot;
       const CountPub pub{cnt_word(h, pm->rec_slot), &rec->cnt, pm->rec_seq};
-      if (pmc->precision == O3DS_PRECISION_F64) {
-        pm_carve_rays_kernel<P4d><<<(unsigned int)((sc->n + kBlock - 1) / kBlock), kBlock, 0, h->stream>>>(d, (const P4d*)sc->pts, sc->n, M, T[12], T[13], T[14], params->max_raytracing_length,
-                                                                            params->truncation_distance, params->min_dot_product_with_normal, cd, block_bits);
-        pm_carve_apply_kernel<P4d><<<256, kBlock, 0, h->stream>>>(d, pub, rec->box);
-      } else {
-        pm_carve_rays_kernel<P4f><<<(unsigned int)((sc->n + kBlock - 1) / kBlock), kBlock, 0, h->stream>>>(d, (const P4f*)sc->pts, sc->n, M, T[12], T[13], T[14], params->max_raytracing_length,
-                                                                            params->truncation_distance, params->min_dot_product_with_normal, cd, block_bits);
-        pm_carve_apply_kernel<P4f><<<256, kBlock, 0, h->stream>>>(d, pub, rec->box);
-      }
+      WITH_P4(pmc->precision,
+              pm_carve_rays_kernel<P4><<<(unsigned int)((sc->n + kBlock - 1) / kBlock), kBlock, 0, h->stream>>>(
+                  d, (const P4*)sc->pts, sc->n, M, T[12], T[13], T[14], params->max_raytracing_length, params->truncation_distance,
+                  params->min_dot_product_with_normal, cd, block_bits);
+              pm_carve_apply_kernel<P4><<<256, kBlock, 0, h->stream>>>(d, pub, rec->box));
       pm_carve_finish_kernel<<<1, 64, 0, h->stream>>>(d, pub, rec->box);
       HIP_TRY(hipGetLastError());
       if (n_removed) {  // (asking for the count is what waits)
@@ -4649,17 +4468,12 @@ int o3ds_map_carve_removed(o3ds_handle h, o3ds_cloud map, o3ds_cloud raw_scan, c
   if (m->n > 0 && s->n > 0 && m->precision != s->precision) return fail(h, O3DS_ERR_INVALID_ARG, "map_carve: precision mismatch");
   size_t removed = 0;
   const CropDev cd = to_dev(map_builder_crop);
-  CloudRec gone;
-  CloudGuard gone_guard(h, gone);
-  gone.precision = m->precision;
-  const int rc = DISPATCH(m->precision, carve_t, h, *m, *s, map_to_range_sensor, cd, *params, &removed, removed_out ? &gone : nullptr);
+  const int rc = new_cloud(h, removed_out, [&](CloudRec& gone) {  // an empty cloud when nothing was carved
+    gone.precision = m->precision;
+    return DISPATCH(m->precision, carve_t, h, *m, *s, map_to_range_sensor, cd, *params, &removed, removed_out ? &gone : nullptr);
+  });
   if (n_removed) *n_removed = removed;
-  if (rc) return rc;
-  if (removed_out) {
-    gone_guard.release();
-    *removed_out = add_cloud(h, std::move(gone));  // an empty cloud when nothing was carved
-  }
-  return O3DS_OK;
+  return rc;
 }
 
 int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const double T[16], double map_voxel_size,
@@ -4737,12 +4551,8 @@ int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const d
     placed.n = s->n;
     box_union(joined, *m, placed);
     const Mat34 M = mat34(T);
-    if (m->precision == O3DS_PRECISION_F64)
-      transform_kernel<P4d><<<grid_for(s->n), kBlock, 0, h->stream>>>((const P4d*)s->pts, (const P4d*)s->nrm, s->n, M, T[3], T[7], T[11], T[15], (P4d*)m->pts,
-                                                                      (P4d*)m->nrm, m->n);
-    else
-      transform_kernel<P4f><<<grid_for(s->n), kBlock, 0, h->stream>>>((const P4f*)s->pts, (const P4f*)s->nrm, s->n, M, T[3], T[7], T[11], T[15], (P4f*)m->pts,
-                                                                      (P4f*)m->nrm, m->n);
+    WITH_P4(m->precision, transform_kernel<P4><<<grid_for(s->n), kBlock, 0, h->stream>>>((const P4*)s->pts, (const P4*)s->nrm, s->n, M, T[3], T[7], T[11], T[15],
+                                                                                          (P4*)m->pts, (P4*)m->nrm, m->n));
     HIP_TRY(hipGetLastError());
     free_index(h, *m);
     m->n += s->n;
@@ -4758,7 +4568,7 @@ int o3ds_map_insert_scan(o3ds_handle h, o3ds_cloud map, o3ds_cloud scan, const d
   if (rc) return rc;
   m = find_cloud(h, map);
   if (max_corr_hint > 0.0) {
-    rc = build_index(h, *m, max_corr_hint / index_cell_div());
+    rc = build_index(h, *m, max_corr_hint / kIndexCellDiv);
   }
   return rc;
 }
@@ -5535,24 +5345,18 @@ int cluster_dbscan_t(o3ds_handle h, CloudRec& c, double eps, int min_points, int
 template <typename P4>
 int small_cluster_filter_t(o3ds_handle h, CloudRec& in, double eps, int min_points, int min_cluster_size, CloudRec& out, uint32_t* kept_idx, size_t capacity,
                            size_t* n_kept) {
-  out.precision = in.precision;
-  out.n = 0;
-  box_copy(out, in);  // a subset
-  *n_kept = 0;
-  const size_t n = in.n;
-  if (n == 0) return O3DS_OK;
-  int *d_labels = nullptr, *flags = nullptr, *pos = nullptr;
-  uint32_t* d_sizes = nullptr;
-  TMP_ALLOC(d_labels, sizeof(int) * n);
-  TMP_ALLOC(d_sizes, sizeof(uint32_t) * n);
-  TMP_ALLOC(flags, sizeof(int) * (n + 1));
-  TMP_ALLOC(pos, sizeof(int) * (n + 1));
-  size_t nc = 0;
-  const int rc = cluster_labels_t<P4>(h, in, eps, min_points, d_labels, d_sizes, &nc);
-  if (rc) return rc;
-  cluster_size_flag_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(d_labels, d_sizes, n, (uint32_t)min_cluster_size, flags);  // the labels stay here
-  HIP_TRY(hipGetLastError());
-  return compact_kept_t<P4>(h, in, n, flags, pos, "remove_small_clusters", out, kept_idx, capacity, n_kept);
+  return filter_cloud_t<P4>(h, in, "remove_small_clusters", out, kept_idx, capacity, n_kept, [&](size_t n, int* flags) -> int {
+    int* d_labels = nullptr;
+    uint32_t* d_sizes = nullptr;
+    TMP_ALLOC(d_labels, sizeof(int) * n);
+    TMP_ALLOC(d_sizes, sizeof(uint32_t) * n);
+    size_t nc = 0;
+    const int rc = cluster_labels_t<P4>(h, in, eps, min_points, d_labels, d_sizes, &nc);
+    if (rc) return rc;
+    cluster_size_flag_kernel<><<<grid_for(n), kBlock, 0, h->stream>>>(d_labels, d_sizes, n, (uint32_t)min_cluster_size, flags);  // the labels stay here
+    HIP_TRY(hipGetLastError());
+    return O3DS_OK;
+  });
 }
 }  // namespace
 
@@ -5585,13 +5389,9 @@ int o3ds_remove_small_clusters(o3ds_handle h, o3ds_cloud in, double eps, int min
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "remove_small_clusters: unknown cloud id");
   if (!out || !n_kept) return fail(h, O3DS_ERR_INVALID_ARG, "remove_small_clusters: out and n_kept are required");
   if (c->n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_INVALID_ARG, std::string("remove_small_clusters") + kClusterTooLarge);
-  CloudRec o;
-  CloudGuard o_guard(h, o);
-  const int rc = DISPATCH(c->precision, small_cluster_filter_t, h, *c, eps, min_points, min_cluster_size, o, kept_idx, capacity, n_kept);
-  if (rc) return rc;
-  o_guard.release();
-  *out = add_cloud(h, std::move(o));
-  return O3DS_OK;
+  return new_cloud(h, out, [&](CloudRec& o) {
+    return DISPATCH(c->precision, small_cluster_filter_t, h, *c, eps, min_points, min_cluster_size, o, kept_idx, capacity, n_kept);
+  });
 }
 
 }  // extern "C"
@@ -5654,16 +5454,11 @@ int segment_plane_t(o3ds_handle h, CloudRec& in, double thr, int ransac_n, int64
     CloudRec scratch;
     CloudGuard scratch_guard(h, scratch);
     CloudRec& o = inl ? *inl : scratch;
-    o.precision = in.precision;
-    box_copy(o, in);  // a subset
     rc = compact_kept_t<P4>(h, in, n, flags, pos, "segment_plane", o, inlier_idx, capacity, &m);
     if (rc) return rc;
   }
-  if (rest) {  // SelectByIndex(inliers, invert = true)
-    rest->precision = in.precision;
-    box_copy(*rest, in);
+  if (rest)  // SelectByIndex(inliers, invert = true)
     rc = compact_kept_t<P4>(h, in, n, nflags, pos, "segment_plane", *rest, nullptr, 0, &m);
-  }
   return rc;
 }
 }  // namespace
@@ -5686,20 +5481,12 @@ int o3ds_segment_plane(o3ds_handle h, o3ds_cloud cloud, double distance_threshol
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: unknown cloud id");
   if (c->n < (size_t)ransac_n) return fail(h, O3DS_ERR_INVALID_ARG, "There must be at least 'ransac_n' points.");  // [O3D]
   if (c->n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_INVALID_ARG, "segment_plane: clouds of 2^31 points and more are unsupported (the scan's positions are 32-bit)");
-  CloudRec inl, rest;
-  CloudGuard inl_guard(h, inl), rest_guard(h, rest);
-  const int rc = DISPATCH(c->precision, segment_plane_t, h, *c, distance_threshold, ransac_n, num_iterations, seed, out, inlier_idx, capacity,
-                          inliers_out ? &inl : nullptr, rest_out ? &rest : nullptr);
-  if (rc) return rc;
-  if (inliers_out) {
-    inl_guard.release();
-    *inliers_out = add_cloud(h, std::move(inl));
-  }
-  if (rest_out) {
-    rest_guard.release();
-    *rest_out = add_cloud(h, std::move(rest));
-  }
-  return O3DS_OK;
+  return new_cloud(h, rest_out, [&](CloudRec& rest) {  // (the inner cloud gets its id first)
+    return new_cloud(h, inliers_out, [&](CloudRec& inl) {
+      return DISPATCH(c->precision, segment_plane_t, h, *c, distance_threshold, ransac_n, num_iterations, seed, out, inlier_idx, capacity,
+                      inliers_out ? &inl : nullptr, rest_out ? &rest : nullptr);
+    });
+  });
 }
 
 }  // extern "C"

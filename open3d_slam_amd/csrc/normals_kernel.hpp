@@ -25,38 +25,12 @@
 
 namespace o3ds {
 
-#ifdef O3DS_NRM_BARRIER
-#define O3DS_WAVE_SYNC() __syncthreads()
-#else
 #define O3DS_WAVE_SYNC()                                  \
   do {                                                    \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
     __builtin_amdgcn_wave_barrier();                      \
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
   } while (0)
-#endif
-#ifdef O3DS_NRM_PHASES  // development aid: shader-clock cycles per phase of the kernel, per wavefront (implies O3DS_NRM_CHECK)
-#define O3DS_PH(k)                      \
-  do {                                  \
-    const long long _t = clock64();     \
-    st_ph[k] += _t - st_last;           \
-    st_last = _t;                       \
-  } while (0)
-#else
-#define O3DS_PH(k) ((void)0)
-#endif
-#ifdef O3DS_NRM_CHECK  // development aid: invariant violations counted in a device array (o3ds_debug_counters)
-__device__ unsigned int g_nrm_dbg[8];
-#define O3DS_NRM_BAD(k) atomicAdd(&g_nrm_dbg[k], 1u)
-#ifdef O3DS_NRM_PHASES
-constexpr int kNrmStatWords = 16;
-#else
-constexpr int kNrmStatWords = 6;
-#endif
-__device__ unsigned long long* g_nrm_wave_stats;  // per wavefront: {clocks, start, rounds, max ring, chunks, merges} when set
-#else
-#define O3DS_NRM_BAD(k) ((void)0)
-#endif
 
 // inclusive prefix sum over the 16 lanes of a DPP row
 __device__ __forceinline__ int row_incl_scan(int v) {
@@ -158,13 +132,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
     return fmaxf(v * (1.0f - 1e-6f) - 1e-7f, 0.0f);
   };
 
-#ifdef O3DS_NRM_CHECK
-  const unsigned long long st_t0 = wall_clock64();
-  unsigned int st_rounds = 0, st_ring = 0, st_chunks = 0, st_cand = 0;
-#endif
-#ifdef O3DS_NRM_PHASES
-  long long st_ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = clock64();
-#endif
   const int* __restrict__ cs = g.cell_start;
   const float cell2_lo = (float)(g.cell * g.cell * (1.0 - 4e-6));
   const float inv_cell_hi = (float)(g.inv_cell * (1.0 + 2e-6));
@@ -209,7 +176,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
     // when the block holds more than 64 points, is made of the rows least likely to hold anything below the bound the first chunk set
     const int r1_dz = (int)((164373u >> (2 * l)) & 3u) - 1, r1_dy = (int)((139617u >> (2 * l)) & 3u) - 1;  // lanes 0 .. 8; the others take no row
 
-    O3DS_PH(0);  // set-up
     for (;;) {
       int T = 0;
       if (round1) {
@@ -225,11 +191,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
         r1_off = incl - tot;
         r1_base = s0 - r1_off;
         tnext = ntask;  // the nine rows are taken: the general round starts by moving on to ring 2
-#ifdef O3DS_NRM_CHECK
-        ++st_rounds;
-        st_ring = max(st_ring, 1u);
-#endif
-        O3DS_PH(2);
       } else {
       // ---- find work: every lane moves to its next row that the current bound does not rule out (arithmetic only: at ring 5-6 of a
       // sparse neighbourhood nearly all of the 100-200 rows are ruled out); when no lane of the group has one left the ring is done.
@@ -295,12 +256,7 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
           }
         }
       }
-      O3DS_PH(1);  // find work (arithmetic only)
       if (__ballot(found) == 0ull) break;  // no group has anything left
-#ifdef O3DS_NRM_CHECK
-      ++st_rounds;
-      st_ring = max(st_ring, (unsigned int)__builtin_amdgcn_readfirstlane(ring));
-#endif
       if (found) load_row(row, dzf, dyf, left, ss[0], ee[0], ss[1], ee[1]);
 #pragma unroll
       for (int k = 1; k < 4; ++k) {  // further rows of the same ring for this lane
@@ -331,15 +287,11 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
         pb[1] = make_int4(sb[4], sb[5], sb[6], sb[7]);
       }
       O3DS_WAVE_SYNC();
-      O3DS_PH(2);  // row bounds (cell_start loads) + segment table
       }
 
       for (int f0 = 0; __ballot(f0 < T) != 0ull; f0 += 64) {
         // ---- four candidates per lane (fewer when the round has few left: nslot is wavefront-uniform): flat number -> segment by a
         // 7-step search of the table, the searches of a lane in step
-#ifdef O3DS_NRM_CHECK
-        ++st_chunks;
-#endif
         const int nslot = __ballot(T - f0 > 48) != 0ull ? 4 : __ballot(T - f0 > 32) != 0ull ? 3 : __ballot(T - f0 > 16) != 0ull ? 2 : 1;
         int sb[4] = {0, 0, 0, 0};
         if (round1) {  // the last lane m whose first candidate number is <= f (an empty segment shares its successor's number, which wins)
@@ -369,18 +321,11 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
           for (int c = 0; c < 4; ++c)
             if (c < nslot) sb[c] = L.seg_base[pos[c]];
         }
-        O3DS_PH(3);  // flat number -> segment
         P4 cand[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int f = f0 + l + 16 * c;
           int p = f < T ? sb[c] + f : 0;
-#ifdef O3DS_NRM_CHECK
-          if ((size_t)(unsigned)p >= n) {
-            O3DS_NRM_BAD(1);
-            p = 0;
-          }
-#endif
           if (c < nslot)
             cand[c] = sp[p];
           else
@@ -401,7 +346,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
         }
         int sincl = row_incl_scan(ns);
         int stot = row_last(sincl);
-        O3DS_PH(4);  // candidate loads, distances, keys, first test
         if (__ballot(stot > 0) == 0ull) continue;
         // ---- a first chunk usually brings 40-60 candidates inside the radius for max_nn places, and ranking costs (survivors)^2.
         // So the bound is tightened first: a distance t with max_nn <= #{d2 < t} <= max_nn + 8 is found by regula falsi on the COUNT
@@ -446,7 +390,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
             stot = row_last(sincl);
           }
         }
-        O3DS_PH(5);  // regula falsi on the count
         {
           int slot = sincl - ns;
 #pragma unroll
@@ -466,7 +409,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
             if (stot + l + 16 * k < send) L.Sk[stot + l + 16 * k] = kNever;
         }
         O3DS_WAVE_SYNC();
-        O3DS_PH(6);  // compaction
         // ---- rank survivors and kept keys against each other: lane l owns survivors l, l + 16, ... and kept keys l, l + 16, ...
         // Table entries are read four at a time (one wait per four); entries past the end are replaced by a key nothing is
         // smaller than.  The number of owned survivors per lane (1..4) is a wavefront-uniform switch.
@@ -572,17 +514,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
           for (int k = 0; k < KPL; ++k)
             if (cnt + l + 16 * k < cend) L.Kk[cnt + l + 16 * k] = kNever;
         }
-#ifdef O3DS_NRM_CHECK
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) {
-          const int idx = l + 16 * u;
-          if (idx + 1 < cnt) {
-            int i0 = 0, i1 = 0;
-            if constexpr (WIDE) i0 = L.Ki[idx], i1 = L.Ki[idx + 1];
-            if (!nrm_less<WIDE>(L.Kk[idx], i0, L.Kk[idx + 1], i1)) O3DS_NRM_BAD(0);
-          }
-        }
-#endif
         if (cnt == max_nn) {  // list full: the bound becomes the max_nn-th key
           tau_k = L.Kk[max_nn - 1];
           if constexpr (WIDE) {
@@ -596,7 +527,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
             worst_hi *= 1.0f + 1e-6f;
           }
         }
-        O3DS_PH(7);  // ranking + new bound
       }
       O3DS_WAVE_SYNC();  // the segment table is rewritten by the next round
       round1 = false;
@@ -612,12 +542,6 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
           oi = L.Ki[idx];
         else
           oi = (int)(unsigned int)(L.Kk[idx] & 0xffffffffull);
-#ifdef O3DS_NRM_CHECK
-        if ((size_t)(unsigned)oi >= n) {
-          O3DS_NRM_BAD(2);
-          oi = 0;
-        }
-#endif
         const P4 tpt = pts[oi];
         using XT = std::remove_reference_t<decltype(L.X[0][0])>;
         L.X[idx][0] = (XT)tpt.x;
@@ -650,17 +574,7 @@ __device__ __forceinline__ void normals_body(const P4* __restrict__ pts /* origi
       if (l == 0 && have) out_cnt[j] = cnt;
     }
     O3DS_WAVE_SYNC();
-    O3DS_PH(8);  // cumulants
   }
-#ifdef O3DS_NRM_CHECK
-  if (g_nrm_wave_stats && lane == 0) {
-    unsigned long long* o = g_nrm_wave_stats + kNrmStatWords * ((size_t)blockIdx.x * kNrmWaves + wv);
-    o[0] = wall_clock64() - st_t0, o[1] = st_t0, o[2] = st_rounds, o[3] = st_ring, o[4] = st_chunks, o[5] = 0;
-#ifdef O3DS_NRM_PHASES
-    for (int k = 0; k < 10; ++k) o[6 + k] = (unsigned long long)st_ph[k];
-#endif
-  }
-#endif
 }
 
 template <typename P4, int KMAX>

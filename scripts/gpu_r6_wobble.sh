@@ -8,8 +8,6 @@ if [ -n "$WOBBLE_ALL" ]; then
 run O3DS_NO_PERSISTENT_MAP=1
 run O3DS_ICP_SETS=0
 run O3DS_ICP_MODE=launch
-run O3DS_SYNC_MASK=65535
-run O3DS_ALWAYS_CLEAR=1
 else
 run X=2
 fi

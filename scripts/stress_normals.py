@@ -1,5 +1,4 @@
-"""Development aid: repeats estimate_normals configurations around device-pool disturbances and reports hashes; with an instrumented
-library (O3DS_BACKEND_LIB=..., built with -DO3DS_NRM_CHECK) and O3DS_NRM_DEBUG=1 the invariant-violation counters are printed."""
+"""Development aid: repeats estimate_normals configurations around device-pool disturbances and reports hashes."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -168,3 +168,28 @@ def test_the_shipped_library_reads_no_ab_switch_from_the_environment():
     assert shipped <= allowed, shipped - allowed
     assert {"O3DS_ICP_MODE", "O3DS_ICP_SETS", "O3DS_SUM_NO_SPLIT", "O3DS_VOXEL_SORT", "O3DS_CARVE_SORT", "O3DS_MERGE_LIBRARY_SORT"} <= ab
     assert b"A/B switches" in backend.load(ab=True).o3ds_version() and b"A/B switches" not in backend.load().o3ds_version()
+
+
+def test_the_ab_library_reads_the_declared_switches_and_no_other():
+    """The inventory of the A/B library's levers: the O3DS_ names it holds, less the five the shipped library may hold and less the enum
+    and macro spellings of include/o3ds_backend.h that error texts quote, are exactly the list below.  A lever that was removed and
+    comes back, or a new one nobody declared here, fails."""
+    from open3d_slam_amd import build
+
+    def names(text):
+        return set(m.decode() for m in re.findall(rb"O3DS_[A-Z0-9_]+", text))
+
+    shipped_may_hold = {"O3DS_POOL_CAP_MB", "O3DS_ARENA_MB", "O3DS_ICP_PASS_MAX_QUERIES", "O3DS_ICP_SUMS_DOUBLES", "O3DS_RCCL_LIB"}
+    levers = names(open(build.LIB_AB, "rb").read()) - shipped_may_hold - names(open(HEADER, "rb").read())
+    assert levers == {
+        # the registration: form of the loop, candidate sets, launch geometry, instrumentation
+        "O3DS_ICP_MODE", "O3DS_ICP_SETS", "O3DS_SET_GAIN", "O3DS_SET_MIN", "O3DS_SET_CAP", "O3DS_PASS_ROWS", "O3DS_SUM_NO_SPLIT",
+        "O3DS_DEBUG_ACC", "O3DS_DEBUG_UPDATE", "O3DS_ICP_STATS", "O3DS_FUSED_TRACE", "O3DS_FUSED_TRACE_LAUNCH",
+        # the search index: replica, the scan loop's slack
+        "O3DS_NN_REPLICA", "O3DS_NN_REPLICA_AFTER", "O3DS_SCAN_SPACE_BYTES", "O3DS_NO_SCAN_SLACK",
+        # pre-processing and the map: sorting forms, the persistent map, the draw list
+        "O3DS_VOXEL_SORT", "O3DS_CARVE_SORT", "O3DS_MERGE_LIBRARY_SORT", "O3DS_SORT_WAYS", "O3DS_NO_INCREMENTAL_MERGE",
+        "O3DS_NO_PERSISTENT_MAP", "O3DS_DRAW_LIST_CAP",
+        # place recognition
+        "O3DS_RANSAC_BATCH",
+    }, levers

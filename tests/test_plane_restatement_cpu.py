@@ -101,7 +101,7 @@ def test_the_documented_order_sums_agree_with_fsum(storage):
 FIT_CASES = (("tilted-plane", pr.tilted_plane, None), ("ground-x", None, "x"), ("ground-y", None, "y"), ("ground-z", None, "z"))
 
 
-@pytest.mark.parametrize("name,cloud,axis", FIT_CASES, ids=lambda v: str(v))
+@pytest.mark.parametrize("name,cloud,axis", FIT_CASES, ids=lambda v: getattr(v, "__name__", None) or str(v))  # (a function by its name: its repr holds an address)
 def test_the_fit_is_the_plane_of_eighs_smallest_eigenvector(name, cloud, axis):
     """GetPlaneFromPoints regresses along the axis of the largest determinant; eigh's smallest eigenvector is the total least-squares
     normal.  The two differ by about (lambda_min / lambda_mid) * tan(tilt from the axis) -- the share of the spread that the plane leaves
