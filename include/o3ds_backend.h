@@ -108,7 +108,8 @@ int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
  * of hipEvents on the handle's stream around whatever the caller enqueues in between (tags 0..7).  Tags 8 (the two kernels of
  * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
  * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) and 14 (the evaluation kernel of o3ds_segment_plane, once per batch of
- * hypotheses) are marked inside the library.  span_read synchronises, returns the
+ * hypotheses) and 15 (the kernel of o3ds_compute_color_gradients) and 16 (the two kernels of one coloured-ICP step: the block sums and
+ * their fold) are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -178,7 +179,8 @@ int o3ds_cloud_download_f32(o3ds_handle h, o3ds_cloud c, void* data, size_t capa
  * must have been made from the same n records (o3ds_cloud_upload_f32). */
 enum { O3DS_COLOR_FIELD_RGB = 0, O3DS_COLOR_FIELD_INTENSITY = 1 };
 int o3ds_cloud_set_colors_from_records(o3ds_handle h, o3ds_cloud c, const void* data, size_t point_step, size_t off_field, int kind);
-/* PointCloud::colors_ (3n doubles in [0, 1]) of a device cloud.  Registration never reads them; the cloud operations carry them
+/* PointCloud::colors_ (3n doubles in [0, 1]) of a device cloud.  The three geometric registrations never read them (coloured ICP,
+ * o3ds_icp_colored_dev at the end of this header, is the one algorithm that does); the cloud operations carry them
  * the way the reference does: crop / select / carve keep the colours of the kept points, transform copies them, append follows
  * [O3D] PointCloud::operator+= (kept only if the map is empty or coloured AND the added cloud is coloured), o3ds_voxel_down_sample
  * averages them ([O3D] VoxelDownSample), and the map merge o3ds_voxelize_within_volume / o3ds_map_insert_scan gives a voxel the
@@ -810,6 +812,83 @@ typedef struct {
 int o3ds_global_optimization(o3ds_handle h, double* node_poses, size_t n_nodes, o3ds_pose_graph_edge* edges, size_t n_edges,
                              const o3ds_global_optimization_option* opt, const o3ds_global_optimization_criteria* crit, uint8_t* edge_kept,
                              o3ds_pose_graph_result* out);
+
+/* ---- coloured ICP: [O3D] pipelines::registration::RegistrationColoredICP (Park, Zhou, Koltun 2017), the fourth RegistrationICP estimator --
+ * Open3D v0.15.1's procedure (ColoredICP.cpp), restated from the upstream sources; like every [O3D] row it is not pinned against a build of
+ * Open3D.  The reference ships no caller of it (there is no CloudRegistrationType for it): the entry points are OFFERED and are not
+ * switched on in the frame loop.  Everything is defined here without reference to an implementation (tests/colored_icp_restatement.py is
+ * the same text in numpy):
+ *   - ARITHMETIC is f64 on the stored values widened (points, normals and colours are held in the storage type), every operation rounded
+ *     on its own (no fused multiply-add).  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+ *     a.x b.y - a.y b.x); the intensity of a colour is I = ((r + g) + b) / 3.0.
+ *
+ * 1. COLOUR GRADIENTS of a cloud, [O3D] InitializePointCloudForColoredICP with KDTreeSearchParamHybrid(radius, max_nn), 1 <= max_nn <= 128.
+ *    For point k with point p, normal n, intensity I: L is the Hybrid list of o3ds_neighbor_search of point k in its own cloud at (radius,
+ *    max_nn), in that search's order (d2, original index).  Fewer than 4 entries: the gradient is (0, 0, 0).  Otherwise the FIRST entry of L
+ *    is skipped, whichever point it is (Open3D assumes it is the point itself; among exact duplicates it need not be -- the definition
+ *    follows Open3D), and every other entry j, in list order, gives a row
+ *        e = dot(q_j - p, n);   a = (q_j - e n) - p, per component;   b = I_j - I
+ *    followed by a last row a = (|L| - 1) n, b = 0.  M = sum a a^T and v = sum a b, every entry summed in that row order onto +0.0
+ *    (M[r][c] += a[r] a[c], v[r] += a[r] b).  M x = v is solved by an UNPIVOTED LDL^T in this order:
+ *        d0 = M00;  l10 = M10 / d0;  l20 = M20 / d0;  d1 = M11 - l10 M10;  w = M21 - l20 M10;  l21 = w / d1;
+ *        d2 = (M22 - l20 M20) - l21 w;  y0 = v0;  y1 = v1 - l10 y0;  y2 = (v2 - l20 y0) - l21 y1;
+ *        x2 = y2 / d2;  x1 = y1 / d1 - l21 x2;  x0 = (y0 / d0 - l10 x1) - l20 x2.
+ *    DEPARTURE: a pivot d0, d1 or d2 that is not finite or not greater than 0 gives the gradient (0, 0, 0) -- a NaN normal, a non-finite
+ *    neighbourhood, and a zero normal or a collinear neighbourhood wherever the cancellation is exact; Open3D takes whatever Eigen's pivoted
+ *    ldlt() returns.  A point with a non-finite coordinate has an empty list, hence a zero gradient.
+ *    The n x 3 doubles stay on the cloud, remembered with the (radius, max_nn) that made them.  They are DROPPED by every call that changes
+ *    the cloud's points, normals or colours in place (o3ds_cloud_set_colors*, o3ds_estimate_normals, o3ds_cloud_append, the map merges,
+ *    carving, de-skew) and are NOT CARRIED into any cloud another call makes (crop, select, filter, copy; o3ds_transform_cloud would have to
+ *    rotate them and does not).  O3DS_ERR_NO_NORMALS / O3DS_ERR_INVALID_ARG for a non-empty cloud without normals / without colours;
+ *    O3DS_ERR_INVALID_ARG for radius <= 0, max_nn outside 1..128, an unknown id, an infinite coordinate (the index build reports it);
+ *    O3DS_ERR_CAPACITY for 2^31 points or a buffer beyond the pool cap.  A persistent-form map is folded into its array first.
+ *    While profiling is enabled the library marks span 15 around the gradient kernel (its search is span 10).
+ *    download: n x 3 row-major doubles, capacity in points. */
+int o3ds_compute_color_gradients(o3ds_handle h, o3ds_cloud cloud, double radius, int max_nn);
+int o3ds_cloud_has_color_gradients(o3ds_handle h, o3ds_cloud cloud, int* has_gradients);
+int o3ds_cloud_download_color_gradients(o3ds_handle h, o3ds_cloud cloud, double* out, size_t capacity);
+/* 2. ONE COLOURED STEP: [O3D] TransformationEstimationForColoredICP::ComputeTransformation up to its solve, with the L2 loss (weights 1;
+ *    robust kernels are out of scope).  One correspondence pass and one reduction; waits for the record.  The testable unit, as
+ *    o3ds_icp_accumulate is for the other estimators.  The target must have normals, colours and gradients (of any parameters), the
+ *    source colours.
+ *    CORRESPONDENCES are the neighbour search's own: o3ds_neighbor_search(source, target, T, Hybrid, max_nn = 1, radius =
+ *    max_correspondence_distance) -- the query is storage(T s), d2 is taken in the storage type and accepted iff strictly below
+ *    storage(r r), ties go to the lower original target index.
+ *    PER ACCEPTED PAIR, with p the query widened, q, n, g the target's point, normal and gradient, I_s and I_t the two intensities,
+ *    sg = sqrt(lambda_geometric), sp = sqrt(1 - lambda_geometric):
+ *        dn = dot(p - q, n);                      J_G = (sg cross(p, n) ; sg n), per component;   r_G = sg dn;
+ *        p' = p - dn n, per component;            I_0 = dot(g, p' - q) + I_t;      gn = dot(g, n);
+ *        g_M = gn n - g, per component;           J_I = (sp cross(p, g_M) ; sp g_M);              r_I = sp (I_s - I_0).
+ *    RECORD TERMS of the pair (the layout of o3ds_icp_accumulate): [0..20] the upper triangle, row-major, of J_G[r] J_G[c] + J_I[r] J_I[c];
+ *    [21..26] J_G[r] r_G + J_I[r] r_I; [27] r_G r_G + r_I r_I; [28] 1; [29] the search's d2 widened.  [30..31] of the record are 0.
+ *    SUM ORDER, a function of the number of source points alone (never of launch geometry, handle or timing; no floating-point atomics):
+ *    the term of a query without a correspondence is +0.0; the queries are cut into blocks of 256 in index order, the missing queries of
+ *    the last block being +0.0; inside a block a halving tree, v[t] = v[t] + v[t + s] for t < s, s = 128, 64, ..., 1, the block's sum is
+ *    v[0]; the block sums are added in ascending block order onto +0.0.  An empty source, or a target without a finite point, gives the
+ *    zero record.
+ *    While profiling is enabled the library marks span 16 around the two kernels of the step (the search is span 10). */
+int o3ds_colored_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance,
+                          double lambda_geometric, double record[32]);
+/* 3. THE REGISTRATION: [O3D] RegistrationColoredICP(source, target, max_correspondence_distance, init,
+ *    TransformationEstimationForColoredICP(lambda_geometric), criteria).  params is o3ds_icp_params with `method` ignored; Open3D's default
+ *    lambda_geometric is 0.968.  The loop is [O3D] RegistrationICP's: pass j evaluates the step above under the current pose; fitness =
+ *    [28] / |source| and inlier_rmse = sqrt([29] / [28]) (0 without correspondences); from the second pass on the loop ends as converged
+ *    when |fitness - previous| < relative_fitness and |inlier_rmse - previous| < relative_rmse; otherwise, while fewer than max_iteration
+ *    updates have been applied, the 6x6 system [0..20] x = -[21..26] is solved (LDL^T, the solve of o3ds_icp_update, with the point-to-plane
+ *    estimator's treatment of an empty correspondence set: the identity) and T <- (Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5) T.  max_iteration
+ *    solves take max_iteration + 1 passes; fitness, inlier_rmse and n_corr are those of the pass after the last update.  The record of
+ *    every pass is consumed on the device by the kernel behind o3ds_icp_update; the host reads the state it publishes once per pass.
+ *    The result is a function of (clouds, params, lambda_geometric, init) alone: two calls give the same bytes.
+ *    GRADIENTS of the target are those of (2 max_correspondence_distance, 30), as RegistrationColoredICP initialises it: computed if the
+ *    cloud has none or has them from other parameters, and then LEFT on the cloud -- a map registered against repeatedly pays once, where
+ *    Open3D pays per call.  The target's grid index is used if it has one and built and left with the cloud otherwise.
+ *    There is no target_crop: a caller crops the map patch with o3ds_crop_cloud, which keeps colours, as the reference does.  A cloud in
+ *    the persistent map form is folded into its array first.  An o3ds_icp_begin session open on the handle is ended.
+ *    O3DS_ERR_NO_NORMALS: target without normals.  O3DS_ERR_EMPTY: empty target.  O3DS_ERR_INVALID_ARG: source or target without colours
+ *    (Open3D's messages), lambda_geometric outside [0, 1] or NaN, max_correspondence_distance <= 0, clouds of two storage types, an
+ *    unknown id, a negative max_iteration, a null pointer.  An empty source gives fitness 0 and the initial pose. */
+int o3ds_icp_colored_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params,
+                         double lambda_geometric, o3ds_icp_result* out);
 
 #ifdef __cplusplus
 }

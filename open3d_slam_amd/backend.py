@@ -211,6 +211,11 @@ SIGNATURES = {
     "o3ds_compute_fpfh": (C.c_int, [_H, _CL, C.c_double, C.c_int]),
     "o3ds_cloud_has_fpfh": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
     "o3ds_cloud_download_fpfh": (C.c_int, [_H, _CL, _dp, C.c_size_t]),
+    "o3ds_compute_color_gradients": (C.c_int, [_H, _CL, C.c_double, C.c_int]),
+    "o3ds_cloud_has_color_gradients": (C.c_int, [_H, _CL, C.POINTER(C.c_int)]),
+    "o3ds_cloud_download_color_gradients": (C.c_int, [_H, _CL, _dp, C.c_size_t]),
+    "o3ds_colored_icp_step": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.c_double, _dp]),
+    "o3ds_icp_colored_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_double, C.POINTER(IcpResult)]),
     "o3ds_feature_correspondences": (C.c_int, [_H, _CL, _CL, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_int)]),
     "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
@@ -616,6 +621,39 @@ class Backend:
         out = IcpResult()
         self._ck(self.lib.o3ds_icp_register_dev(self.h, source, target, C.byref(target_crop) if target_crop else None, ip, C.byref(p), C.byref(out)))
         return self._result(out)
+
+    # -- coloured ICP ([O3D] RegistrationColoredICP; o3ds_backend.h, the last section)
+    def compute_color_gradients(self, cid: int, radius: float, max_nn: int = 30):
+        """o3ds_compute_color_gradients: the gradients stay on the cloud until its points, normals or colours change"""
+        self._ck(self.lib.o3ds_compute_color_gradients(self.h, cid, float(radius), int(max_nn)))
+
+    def has_color_gradients(self, cid: int) -> bool:
+        v = C.c_int()
+        self._ck(self.lib.o3ds_cloud_has_color_gradients(self.h, cid, C.byref(v)))
+        return bool(v.value)
+
+    def color_gradients(self, cid: int) -> np.ndarray:
+        """(n, 3) float64"""
+        n, _ = self.size(cid)
+        out = np.zeros((n, 3))
+        self._ck(self.lib.o3ds_cloud_download_color_gradients(self.h, cid, out.ctypes.data_as(_dp) if n else None, n))
+        return out
+
+    def colored_icp_step(self, source: int, target: int, max_corr: float, lambda_geometric: float = 0.968, T=None) -> np.ndarray:
+        """o3ds_colored_icp_step: the 32-double record of one correspondence pass under T (None: identity)"""
+        T0, ip = (None, _IDENTITY16) if T is None else _d(colmajor(T))
+        rec = np.zeros(32)
+        self._ck(self.lib.o3ds_colored_icp_step(self.h, source, target, ip, float(max_corr), float(lambda_geometric), rec.ctypes.data_as(_dp)))
+        return rec
+
+    def icp_colored_dev(self, source: int, target: int, max_corr, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                        lambda_geometric: float = 0.968, raw: bool = False):
+        """o3ds_icp_colored_dev; raw=True returns the bytes of o3ds_icp_result instead of the dict"""
+        T0, ip = (None, _IDENTITY16) if init is None else _d(colmajor(init))
+        p = self._params(max_corr, max_iter, rel_fitness, rel_rmse)
+        out = IcpResult()
+        self._ck(self.lib.o3ds_icp_colored_dev(self.h, source, target, ip, C.byref(p), float(lambda_geometric), C.byref(out)))
+        return bytes(out) if raw else self._result(out)
 
     # -- sharded registrations inside the library (RCCL through dlopen; o3ds_backend.h)
     SHARD_SOURCE, SHARD_SUBMAP, SHARD_UNION = 0, 1, 2

@@ -166,6 +166,47 @@ class RegistrationIcpPointToPoint(CloudRegistration):  # CloudRegistration.hpp:3
         return None
 
 
+class RegistrationIcpColored(CloudRegistration):
+    """[O3D] RegistrationColoredICP, the fourth RegistrationICP estimator, on device clouds (o3ds_icp_colored_dev).  The reference has no
+    such class and no CloudRegistrationType for it: it is offered beside the three it has and is not made by cloudRegistrationFactory."""
+
+    def __init__(self):
+        self.maxCorrespondenceDistance_ = 1.0
+        self.knnNormalEstimation_ = 10
+        self.maxRadiusNormalEstimation_ = 2.0
+        self.lambdaGeometric_ = 0.968  # [O3D] TransformationEstimationForColoredICP's default
+        self.icpConvergenceCriteria_ = ICPConvergenceCriteria()
+
+    def registerClouds(self, source: PointCloud, target: PointCloud, init) -> RegistrationResult:
+        """[O3D] RegistrationColoredICP(source, target, maxCorrespondenceDistance_, init,
+        TransformationEstimationForColoredICP(lambdaGeometric_), icpConvergenceCriteria_).  Both clouds need colours, the target normals;
+        the target's colour gradients are computed on the first call and stay on it.  Raises as Open3D's LogError does."""
+        c = self.icpConvergenceCriteria_
+        try:
+            r = source.be.icp_colored_dev(source.id, target.id, self.maxCorrespondenceDistance_, init=init, max_iter=c.max_iteration_,
+                                          rel_fitness=c.relative_fitness_, rel_rmse=c.relative_rmse_, lambda_geometric=self.lambdaGeometric_)
+        except _b.BackendError as e:
+            raise RuntimeError(str(e)) from e
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+    def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:
+        """point-to-plane's normals (CloudRegistration.cpp:49-56)"""
+        if not self.maxRadiusNormalEstimation_ > 0.0:
+            raise RuntimeError("maxRadiusNormalEstimation_")
+        if not self.knnNormalEstimation_ > 0:
+            raise RuntimeError("knnNormalEstimation_")
+        cloud.be.estimate_normals(cloud.id, self.maxRadiusNormalEstimation_, self.knnNormalEstimation_)
+
+
+def createColoredIcp(p: CloudRegistrationParameters) -> RegistrationIcpColored:  # as createPointToPlaneIcp; lambdaGeometric_ keeps its default
+    ret = RegistrationIcpColored()
+    ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_
+    ret.knnNormalEstimation_ = p.icp_.knn_
+    ret.maxRadiusNormalEstimation_ = p.icp_.maxDistanceKnn_
+    ret.icpConvergenceCriteria_.max_iteration_ = p.icp_.maxNumIter_
+    return ret
+
+
 def createPointToPointIcp(p: CloudRegistrationParameters) -> RegistrationIcpPointToPoint:  # CloudRegistration.cpp:76-81
     ret = RegistrationIcpPointToPoint()
     ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_

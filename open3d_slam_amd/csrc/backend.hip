@@ -31,6 +31,7 @@
 #include "pose_graph_kernels.hpp"
 #include "cluster_kernels.hpp"  // (last: its kernels follow every other one in the code object, whose layout the registration was measured with)
 #include "plane_kernels.hpp"    // (and these follow the clustering's)
+#include "colored_icp_kernels.hpp"  // (and these the plane's)
 
 using namespace o3ds;
 
@@ -103,6 +104,13 @@ struct CloudRec {
   double* fpfh = nullptr;
   bool has_fpfh = false;
   size_t fpfh_n = 0;
+  // colour gradients (o3ds_compute_color_gradients): n x 3 doubles, remembered with the (radius, max_nn) that made them; dropped by every
+  // operation that changes the points, normals or colours in place, carried into no other cloud
+  double* cgrad = nullptr;
+  bool has_cgrad = false;
+  size_t cgrad_n = 0;
+  double cgrad_radius = 0.0;
+  int cgrad_max_nn = 0;
 };
 
 void box_inflate(CloudRec& c) {  // stored values are rounded (f32 storage, f64 -> f32 of means / placements): keep the box conservative
@@ -316,8 +324,9 @@ struct o3ds_context {
   size_t ev_used = 0;
   // ... and tagged spans (o3ds_profile_span): pairs of events around whatever the caller -- or, for the internal tags, a kernel
   // sequence inside a call -- encloses
-  std::vector<hipEvent_t> span_ev[16];
-  size_t span_used[16] = {0};
+  static constexpr int kSpanTags = 17;  // 0..7 the caller's (o3ds_profile_span), 8..16 marked inside the library
+  std::vector<hipEvent_t> span_ev[kSpanTags];
+  size_t span_used[kSpanTags] = {0};
 };
 
 namespace {
@@ -565,7 +574,7 @@ struct ArenaScope {
 };
 // tagged span marks on the handle's stream (only while profiling is enabled): begin and end alternate per tag
 void span_mark(o3ds_handle h, int tag) {
-  if (!h->profiling || tag < 0 || tag >= 16) return;
+  if (!h->profiling || tag < 0 || tag >= o3ds_context::kSpanTags) return;
   auto& v = h->span_ev[tag];
   if (h->span_used[tag] >= v.size()) {
     hipEvent_t e;
@@ -753,12 +762,26 @@ void free_fpfh(o3ds_handle h, CloudRec& c) {
   c.has_fpfh = false;
   c.fpfh_n = 0;
 }
-void drop_fpfh(o3ds_handle h, o3ds_cloud id) {  // the entry points that change a cloud in place
+void free_cgrad(o3ds_handle h, CloudRec& c) {
+  if (c.cgrad) dev_free(h, c.cgrad);
+  c.cgrad = nullptr;
+  c.has_cgrad = false;
+  c.cgrad_n = 0;
+}
+void drop_cgrad(o3ds_handle h, o3ds_cloud id) {  // the entry points that change a cloud's colours in place
   auto it = h->clouds.find(id);
-  if (it != h->clouds.end()) free_fpfh(h, it->second);
+  if (it != h->clouds.end()) free_cgrad(h, it->second);
+}
+void drop_fpfh(o3ds_handle h, o3ds_cloud id) {  // the entry points that change a cloud's points or normals in place: the colour gradients go too
+  auto it = h->clouds.find(id);
+  if (it != h->clouds.end()) {
+    free_fpfh(h, it->second);
+    free_cgrad(h, it->second);
+  }
 }
 void free_cloud(o3ds_handle h, CloudRec& c) {
   free_fpfh(h, c);
+  free_cgrad(h, c);
   pm_release(h, c);
   free_index(h, c);
   free_points(h, c);
@@ -1986,7 +2009,7 @@ int o3ds_profile_span(o3ds_handle h, int tag, int end) {
 
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms) {
   CHECK_HANDLE(h);
-  if (tag < 0 || tag >= 16) return fail(h, O3DS_ERR_INVALID_ARG, "profile_span_read: bad tag");
+  if (tag < 0 || tag >= o3ds_context::kSpanTags) return fail(h, O3DS_ERR_INVALID_ARG, "profile_span_read: bad tag");
   HIP_TRY(hipStreamSynchronize(h->stream));
   double tot = 0.0;
   const size_t used = h->span_used[tag] & ~(size_t)1;
@@ -2258,6 +2281,7 @@ int o3ds_cloud_download_f32(o3ds_handle h, o3ds_cloud id, void* data, size_t cap
 
 int o3ds_cloud_set_colors_from_records(o3ds_handle h, o3ds_cloud id, const void* data, size_t point_step, size_t off_field, int kind) {
   CHECK_HANDLE(h);
+  drop_cgrad(h, id);
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, id);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_set_colors_from_records: unknown cloud id");
@@ -2284,6 +2308,7 @@ int o3ds_cloud_set_colors_from_records(o3ds_handle h, o3ds_cloud id, const void*
 
 int o3ds_cloud_set_colors(o3ds_handle h, o3ds_cloud id, const double* rgb) {
   CHECK_HANDLE(h);
+  drop_cgrad(h, id);
   ArenaScope arena_scope(h);
   CloudRec* c = find_cloud(h, id);
   if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_set_colors: unknown cloud id");
@@ -3477,11 +3502,13 @@ int neighbor_index_t(o3ds_handle h, CloudRec& c, double radius, int max_nn) {
 // The search of `nq` queries (points d_qidx[0..nq) of `q`, null: its points in order; moved by T if given) in `t`, results in device arrays:
 // d_idx / d_d2 [nq * max_nn] (either may be null), d_cnt [nq], d_tot [nq] (null: not wanted, and a bounded search may stop at its
 // max_nn-th key), d_avg [nq] (null: not wanted).  *empty: the target has no point with three finite coordinates -- nothing was launched,
-// every list is empty.
+// every list is empty.  It comes in two halves (neighbor_launch_t is both), for a caller that searches one target many times (the coloured
+// registration's passes): neighbor_prepare_t, what the target needs once -- the count of its finite points, read back, and its index --,
+// and neighbor_run_t, the launch.
 template <typename P4>
-int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const double* T, const uint32_t* d_qidx, size_t nq, int max_nn, double radius,
-                      uint32_t* d_idx, double* d_d2, uint32_t* d_cnt, uint32_t* d_tot, double* d_avg, bool* empty) {
+int neighbor_prepare_t(o3ds_handle h, CloudRec& t, size_t nq, int max_nn, double radius, unsigned int** d_fin_out, bool* empty) {
   *empty = true;
+  *d_fin_out = nullptr;
   if (t.n == 0 || nq == 0) return O3DS_OK;
   unsigned int* d_fin = nullptr;
   TMP_ALLOC(d_fin, sizeof(unsigned int));
@@ -3493,7 +3520,13 @@ int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const doubl
   if (n_fin == 0) return O3DS_OK;
   rc = neighbor_index_t<P4>(h, t, radius, max_nn);
   if (rc) return rc;
+  *d_fin_out = d_fin;
   *empty = false;
+  return O3DS_OK;
+}
+template <typename P4>
+int neighbor_run_t(o3ds_handle h, const CloudRec& q, const CloudRec& t, const double* T, const uint32_t* d_qidx, size_t nq, int max_nn, double radius,
+                   const unsigned int* d_fin, uint32_t* d_idx, double* d_d2, uint32_t* d_cnt, uint32_t* d_tot, double* d_avg) {
   const unsigned int gsz = (unsigned int)((nq + kNbrQueriesPerBlock - 1) / kNbrQueriesPerBlock);
   const Mat34 M = mat34(T);
   const P4* qp = (const P4*)q.pts;  // (q may be t: its points did not move)
@@ -3508,6 +3541,14 @@ int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const doubl
   span_mark(h, kSpanNeighborKernel);
   HIP_TRY(hipGetLastError());
   return O3DS_OK;
+}
+template <typename P4>
+int neighbor_launch_t(o3ds_handle h, const CloudRec& q, CloudRec& t, const double* T, const uint32_t* d_qidx, size_t nq, int max_nn, double radius,
+                      uint32_t* d_idx, double* d_d2, uint32_t* d_cnt, uint32_t* d_tot, double* d_avg, bool* empty) {
+  unsigned int* d_fin = nullptr;
+  const int rc = neighbor_prepare_t<P4>(h, t, nq, max_nn, radius, &d_fin, empty);
+  if (rc || *empty) return rc;
+  return neighbor_run_t<P4>(h, q, t, T, d_qidx, nq, max_nn, radius, d_fin, d_idx, d_d2, d_cnt, d_tot, d_avg);
 }
 
 // The subset of `in` that flags[0..n) keeps (flags[n] = 0, the scan's sentinel), as the new cloud `out`: the croppers' scan and stable
@@ -5487,6 +5528,214 @@ int o3ds_segment_plane(o3ds_handle h, o3ds_cloud cloud, double distance_threshol
                       inliers_out ? &inl : nullptr, rest_out ? &rest : nullptr);
     });
   });
+}
+
+}  // extern "C"
+
+namespace {
+// ---- [O3D] coloured ICP (colored_icp_kernels.hpp) ------------------------------------------------------------------------------------
+constexpr int kSpanColorGradient = 15, kSpanColoredStep = 16;
+constexpr int kColoredGradMaxNN = 30;  // [O3D] RegistrationColoredICP initialises its target with KDTreeSearchParamHybrid(2 r, 30)
+
+bool cgrad_valid(const CloudRec& c) { return c.has_cgrad && c.cgrad && c.cgrad_n == c.n && !c.pm; }
+
+// InitializePointCloudForColoredICP: the Hybrid lists of the cloud in itself stay in device arrays, one thread per point reads its own
+template <typename P4>
+int color_gradients_t(o3ds_handle h, CloudRec& c, double radius, int max_nn) {
+  const size_t n = c.n;
+  free_cgrad(h, c);
+  if (n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_CAPACITY, "compute_color_gradients: clouds of 2^31 points and more are unsupported");
+  const size_t grad_bytes = n * 3 * sizeof(double), list_bytes = n * (size_t)max_nn * sizeof(uint32_t);
+  if (grad_bytes > pool_cap_bytes() || list_bytes > pool_cap_bytes())
+    return fail(h, O3DS_ERR_CAPACITY, "compute_color_gradients: a buffer exceeds the pool cap (O3DS_POOL_CAP_MB)");
+  uint32_t *d_idx = nullptr, *d_cnt = nullptr;
+  bool empty = true;
+  if (n) {
+    TMP_ALLOC(d_idx, list_bytes);
+    TMP_ALLOC(d_cnt, n * sizeof(uint32_t));
+    const int rc = neighbor_launch_t<P4>(h, c, c, nullptr, nullptr, n, max_nn, radius, d_idx, nullptr, d_cnt, nullptr, nullptr, &empty);
+    if (rc) return rc;
+  }
+  double* out = nullptr;
+  HIP_TRY(dev_alloc(h, (void**)&out, std::max<size_t>(grad_bytes, 8)));
+  c.cgrad = out;
+  if (n && empty) {  // no point with three finite coordinates: every list is empty
+    HIP_TRY(hipMemsetAsync(out, 0, grad_bytes, h->stream));
+  } else if (n) {
+    span_mark(h, kSpanColorGradient);
+    color_gradient_kernel<P4><<<(unsigned int)((n + kBlock - 1) / kBlock), kBlock, 0, h->stream>>>((const P4*)c.pts, (const P4*)c.nrm, (const P4*)c.col, n, d_idx,
+                                                                                                  d_cnt, max_nn, out);
+    span_mark(h, kSpanColorGradient);
+    HIP_TRY(hipGetLastError());
+  }
+  c.has_cgrad = true;
+  c.cgrad_n = n;
+  c.cgrad_radius = radius;
+  c.cgrad_max_nn = max_nn;
+  return O3DS_OK;
+}
+
+// what the passes of one call share: the search's arrays, the block sums, the record, and what the target needed once
+struct ColoredPass {
+  unsigned int* d_fin = nullptr;
+  bool empty = true;  // no query or no finite target point: the record is zero
+  uint32_t *d_idx = nullptr, *d_cnt = nullptr;
+  double *d_d2 = nullptr, *d_partial = nullptr, *d_record = nullptr;
+  size_t nblocks = 0;
+};
+template <typename P4>
+int colored_prepare_t(o3ds_handle h, const CloudRec& s, CloudRec& t, double r, ColoredPass& cp) {
+  cp.nblocks = (s.n + kColStepBlock - 1) / kColStepBlock;
+  TMP_ALLOC(cp.d_record, sizeof(double) * kRec);
+  if (s.n == 0) return O3DS_OK;
+  TMP_ALLOC(cp.d_idx, sizeof(uint32_t) * s.n);
+  TMP_ALLOC(cp.d_cnt, sizeof(uint32_t) * s.n);
+  TMP_ALLOC(cp.d_d2, sizeof(double) * s.n);
+  TMP_ALLOC(cp.d_partial, sizeof(double) * kRec * cp.nblocks);
+  return neighbor_prepare_t<P4>(h, t, s.n, 1, r, &cp.d_fin, &cp.empty);
+}
+// one correspondence pass under T and its reduction into cp.d_record; nothing waits
+template <typename P4>
+int colored_pass_t(o3ds_handle h, const CloudRec& s, const CloudRec& t, const double T[16], double r, double sg, double sp, const ColoredPass& cp) {
+  if (cp.empty) {
+    HIP_TRY(hipMemsetAsync(cp.d_record, 0, sizeof(double) * kRec, h->stream));
+    return O3DS_OK;
+  }
+  const int rc = neighbor_run_t<P4>(h, s, t, T, nullptr, s.n, 1, r, cp.d_fin, cp.d_idx, cp.d_d2, cp.d_cnt, nullptr, nullptr);
+  if (rc) return rc;
+  span_mark(h, kSpanColoredStep);
+  colored_step_kernel<P4><<<(unsigned int)cp.nblocks, kColStepBlock, 0, h->stream>>>((const P4*)s.pts, (const P4*)s.col, s.n, mat34(T), (const P4*)t.pts,
+                                                                                     (const P4*)t.nrm, (const P4*)t.col, t.cgrad, t.n, cp.d_idx, cp.d_cnt,
+                                                                                     cp.d_d2, sg, sp, cp.d_partial);
+  colored_finish_kernel<<<1, 64, 0, h->stream>>>(cp.d_partial, cp.nblocks, cp.d_record);
+  span_mark(h, kSpanColoredStep);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+template <typename P4>
+int colored_step_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T[16], double r, double lambda, double record[32]) {
+  ColoredPass cp;
+  int rc = colored_prepare_t<P4>(h, s, t, r, cp);
+  if (rc) return rc;
+  rc = colored_pass_t<P4>(h, s, t, T, r, std::sqrt(lambda), std::sqrt(1.0 - lambda), cp);
+  if (rc) return rc;
+  return read_back(h, {{record, cp.d_record, sizeof(double) * kRec}});
+}
+
+// [O3D] RegistrationICP's loop around the joint step: the record of every pass goes to the tail the sharded path runs (icp_update_kernel:
+// convergence test, 6x6 LDL^T, T <- U T), and the host reads the state it publishes -- the next pose and whether the loop has ended
+template <typename P4>
+int colored_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, double lambda, o3ds_icp_result* out) {
+  const double r = p.max_correspondence_distance;
+  int rc = O3DS_OK;
+  if (!cgrad_valid(t) || t.cgrad_radius != 2.0 * r || t.cgrad_max_nn != kColoredGradMaxNN) {
+    rc = color_gradients_t<P4>(h, t, 2.0 * r, kColoredGradMaxNN);
+    if (rc) return rc;
+  }
+  ColoredPass cp;
+  rc = colored_prepare_t<P4>(h, s, t, r, cp);  // the finite count's read-back and the index check: once, not per pass
+  if (rc) return rc;
+  h->session = false;  // (the handle's one state is taken: a step-wise session that was open is over)
+  IcpStateDev st{};
+  memcpy(st.T, init, sizeof(double) * 16);
+  *h->h_state = st;
+  if (s.n == 0) {  // [O3D]: no correspondence, fitness 0, the initial pose
+    copy_result(h, out);
+    return O3DS_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_state, h->h_state, sizeof(IcpStateDev), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // (h_state is read back into below)
+  const double sg = std::sqrt(lambda), sp = std::sqrt(1.0 - lambda);
+  for (int pass = 0; pass <= p.max_iteration; ++pass) {
+    double T[16];
+    memcpy(T, h->h_state->T, sizeof(T));
+    rc = colored_pass_t<P4>(h, s, t, T, r, sg, sp, cp);
+    if (rc) return rc;
+    icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
+                                               O3DS_ICP_POINT_TO_PLANE);
+    HIP_TRY(hipGetLastError());
+    rc = read_state(h, out);
+    if (rc) return rc;
+    if (h->h_state->done) break;
+  }
+  return O3DS_OK;
+}
+
+// the checks the step and the registration share; *src / *tgt with their exact sizes, a persistent map folded into its array
+int validate_colored(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cloud target, double r, double lambda, CloudRec** src, CloudRec** tgt) {
+  CloudRec* s = find_cloud(h, source);
+  CloudRec* t = s ? find_cloud(h, target) : nullptr;
+  if (!s || !t) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown cloud id");
+  if (!(r > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");  // [O3D] RegistrationICP
+  if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": lambda_geometric must be in [0, 1]");
+  if (t->n == 0) return fail(h, O3DS_ERR_EMPTY, std::string(what) + ": empty target");
+  if (s->precision != t->precision) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": source/target precision mismatch");
+  if (!t->nrm) return fail(h, O3DS_ERR_NO_NORMALS, "ColoredICP requires target pointcloud to have normals.");  // [O3D]
+  if (!t->col) return fail(h, O3DS_ERR_INVALID_ARG, "ColoredICP requires target pointcloud to have colors.");  // [O3D]
+  if (s->n > 0 && !s->col) return fail(h, O3DS_ERR_INVALID_ARG, "ColoredICP requires source pointcloud to have colors.");  // [O3D]
+  *src = s;
+  *tgt = t;
+  return O3DS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int o3ds_compute_color_gradients(o3ds_handle h, o3ds_cloud cloud, double radius, int max_nn) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  CloudRec* c = find_cloud(h, cloud);  // (with its exact size; a persistent map as its array)
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "compute_color_gradients: unknown cloud id");
+  if (!(radius > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "compute_color_gradients: radius must be > 0");
+  if (max_nn < 1 || max_nn > 128) return fail(h, O3DS_ERR_INVALID_ARG, "compute_color_gradients: max_nn outside 1..128");
+  if (c->n > 0 && !c->nrm) return fail(h, O3DS_ERR_NO_NORMALS, "compute_color_gradients: the cloud has no normals");
+  if (c->n > 0 && !c->col) return fail(h, O3DS_ERR_INVALID_ARG, "compute_color_gradients: the cloud has no colours");
+  return DISPATCH(c->precision, color_gradients_t, h, *c, radius, max_nn);
+}
+
+int o3ds_cloud_has_color_gradients(o3ds_handle h, o3ds_cloud cloud, int* has_gradients) {
+  CHECK_HANDLE(h);
+  if (!has_gradients) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_has_color_gradients: null argument");
+  CloudRec* c = find_cloud(h, cloud);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_has_color_gradients: unknown cloud id");
+  *has_gradients = cgrad_valid(*c) ? 1 : 0;
+  return O3DS_OK;
+}
+
+int o3ds_cloud_download_color_gradients(o3ds_handle h, o3ds_cloud cloud, double* out, size_t capacity) {
+  CHECK_HANDLE(h);
+  CloudRec* c = find_cloud(h, cloud);
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_color_gradients: unknown cloud id");
+  if (!cgrad_valid(*c)) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_color_gradients: the cloud has no colour gradients");
+  if (capacity < c->n) return fail(h, O3DS_ERR_CAPACITY, "cloud_download_color_gradients: buffer too small");
+  if (c->n == 0) return O3DS_OK;
+  if (!out) return fail(h, O3DS_ERR_INVALID_ARG, "cloud_download_color_gradients: null buffer");
+  return d2h_copy(h, out, c->cgrad, c->n * 3 * sizeof(double));
+}
+
+int o3ds_colored_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance,
+                          double lambda_geometric, double record[32]) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!T || !record) return fail(h, O3DS_ERR_INVALID_ARG, "colored_icp_step: null argument");
+  CloudRec *s = nullptr, *t = nullptr;
+  const int rc = validate_colored(h, "colored_icp_step", source, target, max_correspondence_distance, lambda_geometric, &s, &t);
+  if (rc) return rc;
+  if (!cgrad_valid(*t)) return fail(h, O3DS_ERR_INVALID_ARG, "colored_icp_step: the target has no colour gradients (o3ds_compute_color_gradients)");
+  return DISPATCH(t->precision, colored_step_t, h, *s, *t, T, max_correspondence_distance, lambda_geometric, record);
+}
+
+int o3ds_icp_colored_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params,
+                         double lambda_geometric, o3ds_icp_result* out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!init || !params || !out) return fail(h, O3DS_ERR_INVALID_ARG, "icp_colored: null argument");
+  if (params->max_iteration < 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp_colored: negative max_iteration");
+  CloudRec *s = nullptr, *t = nullptr;
+  const int rc = validate_colored(h, "icp_colored", source, target, params->max_correspondence_distance, lambda_geometric, &s, &t);
+  if (rc) return rc;
+  return DISPATCH(t->precision, colored_register_t, h, *s, *t, init, *params, lambda_geometric, out);
 }
 
 }  // extern "C"
