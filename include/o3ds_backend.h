@@ -109,7 +109,7 @@ int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
  * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
  * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) and 14 (the evaluation kernel of o3ds_segment_plane, once per batch of
  * hypotheses) and 15 (the kernel of o3ds_compute_color_gradients) and 16 (the two kernels of one coloured-ICP step: the block sums and
- * their fold) are marked inside the library.  span_read synchronises, returns the
+ * their fold) and 17 (the same two of one robust-loss step, o3ds_robust_icp_step) are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -848,7 +848,7 @@ int o3ds_compute_color_gradients(o3ds_handle h, o3ds_cloud cloud, double radius,
 int o3ds_cloud_has_color_gradients(o3ds_handle h, o3ds_cloud cloud, int* has_gradients);
 int o3ds_cloud_download_color_gradients(o3ds_handle h, o3ds_cloud cloud, double* out, size_t capacity);
 /* 2. ONE COLOURED STEP: [O3D] TransformationEstimationForColoredICP::ComputeTransformation up to its solve, with the L2 loss (weights 1;
- *    robust kernels are out of scope).  One correspondence pass and one reduction; waits for the record.  The testable unit, as
+ *    the robust losses are o3ds_robust_icp_step's, below).  One correspondence pass and one reduction; waits for the record.  The testable unit, as
  *    o3ds_icp_accumulate is for the other estimators.  The target must have normals, colours and gradients (of any parameters), the
  *    source colours.
  *    CORRESPONDENCES are the neighbour search's own: o3ds_neighbor_search(source, target, T, Hybrid, max_nn = 1, radius =
@@ -889,6 +889,59 @@ int o3ds_colored_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
  *    unknown id, a negative max_iteration, a null pointer.  An empty source gives fitness 0 and the initial pose. */
 int o3ds_icp_colored_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params,
                          double lambda_geometric, o3ds_icp_result* out);
+
+/* ---- robust loss kernels: [O3D] pipelines::registration::RobustKernel (Open3D v0.15.1, RobustKernel.cpp) on two estimators of the coloured
+ * section above -- TransformationEstimationPointToPlane(kernel) and TransformationEstimationForColoredICP(lambda_geometric, kernel).  A
+ * registration whose correspondences all weigh 1 is pulled by everything inside max_correspondence_distance that is not in the map (a moved
+ * object, a person, the rim of a partial overlap); a robust loss weighs each residual by how plausible it is.  OFFERED like the coloured
+ * section and switched on nowhere; the tuned geometric passes (o3ds_icp_register_dev and its kin) take no loss, and GICP is not covered.
+ * ARITHMETIC, CORRESPONDENCES, SUM ORDER and the LOOP are those of the coloured section: f64 on stored values widened, every operation
+ * rounded on its own (no fused multiply-add); the neighbour search's pairs under the query storage(T s); blocks of 256 queries in index order,
+ * the halving tree inside a block, the block sums in ascending order onto +0.0.  tests/robust_icp_restatement.py is this text in numpy.
+ *
+ * WEIGHT of a residual r under a loss, with e = |r| ([O3D] <Loss>::Weight; the comparisons are as written, so a NaN residual takes
+ * whatever they give):
+ *     L2      1
+ *     L1      1 / e                                      DEPARTURE: r == 0 gives 1 (Open3D gives inf, and NaN from inf * 0 in the sums)
+ *     HUBER   e > k ? k / e : 1
+ *     CAUCHY  1 / (1 + (r / k) (r / k))
+ *     GM      k / ((k + r r) (k + r r))
+ *     TUKEY   u = (e / k < 1) ? e / k : 1;   v = 1 - u u;   w = v v
+ * k must be finite and > 0 for HUBER, CAUCHY, GM and TUKEY and is ignored for L2 and L1.  `reserved` must be 0. */
+typedef enum { O3DS_LOSS_L2 = 0, O3DS_LOSS_L1 = 1, O3DS_LOSS_HUBER = 2, O3DS_LOSS_CAUCHY = 3, O3DS_LOSS_GM = 4, O3DS_LOSS_TUKEY = 5 } o3ds_loss_kind;
+typedef struct {
+  int32_t kind; /* o3ds_loss_kind */
+  int32_t reserved;
+  double k;
+} o3ds_robust_loss; /* 16 bytes */
+typedef enum { O3DS_ROBUST_POINT_TO_PLANE = 0, O3DS_ROBUST_COLORED = 1 } o3ds_robust_estimator;
+/* 1. ONE ROBUST STEP.  Correspondences, the query p, and q, n, g, J_G, r_G, J_I, r_I of an accepted pair are exactly those of
+ *    o3ds_colored_icp_step.  RECORD TERMS of the pair:
+ *    COLORED, with w_G = Weight(r_G) and w_I = Weight(r_I) (Open3D's weighted form: each residual is weighted after its multiplication by
+ *    sqrt(lambda) or sqrt(1 - lambda)): [0..20] the upper triangle, row-major, of w_G (J_G[r] J_G[c]) + w_I (J_I[r] J_I[c]); [21..26]
+ *    w_G (J_G[r] r_G) + w_I (J_I[r] r_I); [27] r_G r_G + r_I r_I, UNWEIGHTED as in [O3D] ComputeJTJandJTr; [28] 1; [29] the search's d2
+ *    widened; [30..31] of the record are 0.  The target must have normals, colours and gradients, the source colours, as for
+ *    o3ds_colored_icp_step.  With the L2 loss the record is that of o3ds_colored_icp_step, bit for bit.
+ *    POINT_TO_PLANE: J = (cross(p, n) ; n), r = dot(p - q, n), w = Weight(r): [0..20] w (J[r] J[c]); [21..26] w (J[r] r); [27] r r; the rest
+ *    as above.  lambda_geometric is ignored (any value, NaN included).  The target needs normals only; colours and gradients are read on
+ *    neither cloud.
+ *    Empty cases and error codes are the coloured step's (an empty source, a target without a finite point, or no accepted pair: the zero
+ *    record; O3DS_ERR_EMPTY for an empty target; O3DS_ERR_NO_NORMALS); in addition O3DS_ERR_INVALID_ARG for a null loss, an unknown kind, a
+ *    non-zero `reserved`, a k that is not finite or not > 0 where the loss uses it, and an unknown estimator.
+ *    While profiling is enabled the library marks span 17 around the two kernels of the step (the search is span 10). */
+int o3ds_robust_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance,
+                         int estimator, double lambda_geometric, const o3ds_robust_loss* loss, double record[32]);
+/* 2. THE REGISTRATION: [O3D] RegistrationICP(source, target, max_correspondence_distance, init, estimation(kernel), criteria): the loop of
+ *    o3ds_icp_colored_dev around the step above -- the same convergence rule, the same solve and update.  fitness and inlier_rmse come
+ *    from [28] and [29], which carry no weight: as in Open3D they do not depend on the loss.  A system whose weights are all zero
+ *    ([0..26] all zero with [28] > 0: every pair at or beyond Tukey's k) gives the IDENTITY update: the solve follows Eigen's LDLT, which
+ *    zeroes the components of pivots not above the smallest normal double.  For COLORED the target's gradients of
+ *    (2 max_correspondence_distance, 30) are computed if absent and left on the target; POINT_TO_PLANE neither needs nor makes them.
+ *    The result is a function of (clouds, params, estimator, lambda_geometric, loss, init) alone: two calls give the same bytes; with
+ *    COLORED and the L2 loss they are the bytes of o3ds_icp_colored_dev.  Errors: those of o3ds_icp_colored_dev (for POINT_TO_PLANE
+ *    without the colour requirements) and of the step above. */
+int o3ds_icp_robust_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params,
+                        int estimator, double lambda_geometric, const o3ds_robust_loss* loss, o3ds_icp_result* out);
 
 #ifdef __cplusplus
 }

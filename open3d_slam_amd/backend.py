@@ -43,6 +43,14 @@ class IcpParams(C.Structure):
                 ("relative_fitness", C.c_double), ("relative_rmse", C.c_double)]
 
 
+LOSS_L2, LOSS_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_GM, LOSS_TUKEY = range(6)  # o3ds_loss_kind
+ROBUST_POINT_TO_PLANE, ROBUST_COLORED = 0, 1  # o3ds_robust_estimator
+
+
+class RobustLoss(C.Structure):  # o3ds_robust_loss
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("k", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _H = C.c_void_p
 _CL = C.c_uint64
@@ -216,6 +224,8 @@ SIGNATURES = {
     "o3ds_cloud_download_color_gradients": (C.c_int, [_H, _CL, _dp, C.c_size_t]),
     "o3ds_colored_icp_step": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.c_double, _dp]),
     "o3ds_icp_colored_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_double, C.POINTER(IcpResult)]),
+    "o3ds_robust_icp_step": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.c_int, C.c_double, C.POINTER(RobustLoss), _dp]),
+    "o3ds_icp_robust_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_int, C.c_double, C.POINTER(RobustLoss), C.POINTER(IcpResult)]),
     "o3ds_feature_correspondences": (C.c_int, [_H, _CL, _CL, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_int)]),
     "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
@@ -653,6 +663,36 @@ class Backend:
         p = self._params(max_corr, max_iter, rel_fitness, rel_rmse)
         out = IcpResult()
         self._ck(self.lib.o3ds_icp_colored_dev(self.h, source, target, ip, C.byref(p), float(lambda_geometric), C.byref(out)))
+        return bytes(out) if raw else self._result(out)
+
+    # -- robust losses on the point-to-plane and the coloured estimator ([O3D] RobustKernel; o3ds_backend.h, the last section)
+    @staticmethod
+    def _loss(loss) -> RobustLoss:
+        """a RobustLoss, a (kind, k) pair, or None for L2"""
+        if isinstance(loss, RobustLoss):
+            return loss
+        kind, k = (LOSS_L2, 0.0) if loss is None else loss
+        return RobustLoss(int(kind), 0, float(k))
+
+    def robust_icp_step(self, source: int, target: int, max_corr: float, estimator: int = ROBUST_POINT_TO_PLANE, loss=None,
+                        lambda_geometric: float = 0.968, T=None) -> np.ndarray:
+        """o3ds_robust_icp_step: the 32-double weighted record of one correspondence pass under T (None: identity)"""
+        T0, ip = (None, _IDENTITY16) if T is None else _d(colmajor(T))
+        rec = np.zeros(32)
+        ls = self._loss(loss)
+        self._ck(self.lib.o3ds_robust_icp_step(self.h, source, target, ip, float(max_corr), int(estimator), float(lambda_geometric), C.byref(ls),
+                                               rec.ctypes.data_as(_dp)))
+        return rec
+
+    def icp_robust_dev(self, source: int, target: int, max_corr, estimator: int = ROBUST_POINT_TO_PLANE, loss=None, init=None, max_iter=30,
+                       rel_fitness=1e-6, rel_rmse=1e-6, lambda_geometric: float = 0.968, raw: bool = False):
+        """o3ds_icp_robust_dev; raw=True returns the bytes of o3ds_icp_result instead of the dict"""
+        T0, ip = (None, _IDENTITY16) if init is None else _d(colmajor(init))
+        p = self._params(max_corr, max_iter, rel_fitness, rel_rmse)
+        out = IcpResult()
+        ls = self._loss(loss)
+        self._ck(self.lib.o3ds_icp_robust_dev(self.h, source, target, ip, C.byref(p), int(estimator), float(lambda_geometric), C.byref(ls),
+                                              C.byref(out)))
         return bytes(out) if raw else self._result(out)
 
     # -- sharded registrations inside the library (RCCL through dlopen; o3ds_backend.h)

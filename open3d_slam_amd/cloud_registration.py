@@ -207,6 +207,92 @@ def createColoredIcp(p: CloudRegistrationParameters) -> RegistrationIcpColored: 
     return ret
 
 
+# [O3D] pipelines::registration::RobustKernel and its six losses (RobustKernel.h), by Open3D's names; `k_` is Open3D's scaling parameter
+@dataclasses.dataclass(frozen=True)
+class RobustKernel:
+    kind_ = _b.LOSS_L2
+
+    def toBackend(self) -> _b.RobustLoss:
+        return _b.RobustLoss(self.kind_, 0, float(getattr(self, "k_", 0.0)))
+
+
+@dataclasses.dataclass(frozen=True)
+class L2Loss(RobustKernel):
+    kind_ = _b.LOSS_L2
+
+
+@dataclasses.dataclass(frozen=True)
+class L1Loss(RobustKernel):
+    kind_ = _b.LOSS_L1
+
+
+@dataclasses.dataclass(frozen=True)
+class HuberLoss(RobustKernel):
+    k_: float
+    kind_ = _b.LOSS_HUBER
+
+
+@dataclasses.dataclass(frozen=True)
+class CauchyLoss(RobustKernel):
+    k_: float
+    kind_ = _b.LOSS_CAUCHY
+
+
+@dataclasses.dataclass(frozen=True)
+class GMLoss(RobustKernel):
+    k_: float
+    kind_ = _b.LOSS_GM
+
+
+@dataclasses.dataclass(frozen=True)
+class TukeyLoss(RobustKernel):
+    k_: float
+    kind_ = _b.LOSS_TUKEY
+
+
+ROBUST_ESTIMATORS = {"point_to_plane": _b.ROBUST_POINT_TO_PLANE, "colored": _b.ROBUST_COLORED}
+
+
+class RegistrationIcpRobust(CloudRegistration):
+    """[O3D] RegistrationICP with TransformationEstimationPointToPlane(kernel) or TransformationEstimationForColoredICP(lambda, kernel) on
+    device clouds (o3ds_icp_robust_dev).  Like RegistrationIcpColored it is offered beside the reference's three and is not made by
+    cloudRegistrationFactory."""
+
+    def __init__(self):
+        self.maxCorrespondenceDistance_ = 1.0
+        self.knnNormalEstimation_ = 10
+        self.maxRadiusNormalEstimation_ = 2.0
+        self.estimator_ = "point_to_plane"  # or "colored"
+        self.kernel_: RobustKernel = L2Loss()
+        self.lambdaGeometric_ = 0.968  # "colored" only
+        self.icpConvergenceCriteria_ = ICPConvergenceCriteria()
+
+    def registerClouds(self, source: PointCloud, target: PointCloud, init) -> RegistrationResult:
+        """The target needs normals; "colored" needs colours on both clouds as well, and leaves its gradients on the target."""
+        if self.estimator_ not in ROBUST_ESTIMATORS:
+            raise RuntimeError(f"estimator_ {self.estimator_!r}: one of {sorted(ROBUST_ESTIMATORS)}")
+        c = self.icpConvergenceCriteria_
+        try:
+            r = source.be.icp_robust_dev(source.id, target.id, self.maxCorrespondenceDistance_, ROBUST_ESTIMATORS[self.estimator_],
+                                         self.kernel_.toBackend(), init=init, max_iter=c.max_iteration_, rel_fitness=c.relative_fitness_,
+                                         rel_rmse=c.relative_rmse_, lambda_geometric=self.lambdaGeometric_)
+        except _b.BackendError as e:
+            raise RuntimeError(str(e)) from e
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+    estimateNormalsOrCovariancesIfNeeded = RegistrationIcpColored.estimateNormalsOrCovariancesIfNeeded  # point-to-plane's normals
+
+
+def createRobustIcp(p: CloudRegistrationParameters, kernel: RobustKernel, estimator: str = "point_to_plane") -> RegistrationIcpRobust:
+    ret = RegistrationIcpRobust()  # as createColoredIcp; lambdaGeometric_ keeps its default
+    ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_
+    ret.knnNormalEstimation_ = p.icp_.knn_
+    ret.maxRadiusNormalEstimation_ = p.icp_.maxDistanceKnn_
+    ret.icpConvergenceCriteria_.max_iteration_ = p.icp_.maxNumIter_
+    ret.kernel_, ret.estimator_ = kernel, estimator
+    return ret
+
+
 def createPointToPointIcp(p: CloudRegistrationParameters) -> RegistrationIcpPointToPoint:  # CloudRegistration.cpp:76-81
     ret = RegistrationIcpPointToPoint()
     ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_

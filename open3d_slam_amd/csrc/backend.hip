@@ -32,6 +32,7 @@
 #include "cluster_kernels.hpp"  // (last: its kernels follow every other one in the code object, whose layout the registration was measured with)
 #include "plane_kernels.hpp"    // (and these follow the clustering's)
 #include "colored_icp_kernels.hpp"  // (and these the plane's)
+#include "robust_icp_kernels.hpp"   // (and this one the coloured step's)
 
 using namespace o3ds;
 
@@ -324,7 +325,7 @@ struct o3ds_context {
   size_t ev_used = 0;
   // ... and tagged spans (o3ds_profile_span): pairs of events around whatever the caller -- or, for the internal tags, a kernel
   // sequence inside a call -- encloses
-  static constexpr int kSpanTags = 17;  // 0..7 the caller's (o3ds_profile_span), 8..16 marked inside the library
+  static constexpr int kSpanTags = 18;  // 0..7 the caller's (o3ds_profile_span), 8..17 marked inside the library
   std::vector<hipEvent_t> span_ev[kSpanTags];
   size_t span_used[kSpanTags] = {0};
 };
@@ -5625,16 +5626,12 @@ int colored_step_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T
 
 // [O3D] RegistrationICP's loop around the joint step: the record of every pass goes to the tail the sharded path runs (icp_update_kernel:
 // convergence test, 6x6 LDL^T, T <- U T), and the host reads the state it publishes -- the next pose and whether the loop has ended
-template <typename P4>
-int colored_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, double lambda, o3ds_icp_result* out) {
+// `pass(T, cp)` enqueues one correspondence pass under T and leaves its record in cp.d_record (colored_pass_t, robust_pass_t)
+template <typename P4, typename Pass>
+int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass) {
   const double r = p.max_correspondence_distance;
-  int rc = O3DS_OK;
-  if (!cgrad_valid(t) || t.cgrad_radius != 2.0 * r || t.cgrad_max_nn != kColoredGradMaxNN) {
-    rc = color_gradients_t<P4>(h, t, 2.0 * r, kColoredGradMaxNN);
-    if (rc) return rc;
-  }
   ColoredPass cp;
-  rc = colored_prepare_t<P4>(h, s, t, r, cp);  // the finite count's read-back and the index check: once, not per pass
+  int rc = colored_prepare_t<P4>(h, s, t, r, cp);  // the finite count's read-back and the index check: once, not per pass
   if (rc) return rc;
   h->session = false;  // (the handle's one state is taken: a step-wise session that was open is over)
   IcpStateDev st{};
@@ -5646,11 +5643,10 @@ int colored_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const doub
   }
   HIP_TRY(hipMemcpyAsync(h->d_state, h->h_state, sizeof(IcpStateDev), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));  // (h_state is read back into below)
-  const double sg = std::sqrt(lambda), sp = std::sqrt(1.0 - lambda);
-  for (int pass = 0; pass <= p.max_iteration; ++pass) {
+  for (int j = 0; j <= p.max_iteration; ++j) {
     double T[16];
     memcpy(T, h->h_state->T, sizeof(T));
-    rc = colored_pass_t<P4>(h, s, t, T, r, sg, sp, cp);
+    rc = pass(T, cp);
     if (rc) return rc;
     icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
                                                O3DS_ICP_POINT_TO_PLANE);
@@ -5660,6 +5656,76 @@ int colored_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const doub
     if (h->h_state->done) break;
   }
   return O3DS_OK;
+}
+
+// the target's gradients of (2 r, 30), as [O3D] RegistrationColoredICP initialises it: made if absent or of other parameters, and left
+template <typename P4>
+int ensure_registration_gradients_t(o3ds_handle h, CloudRec& t, double r) {
+  if (cgrad_valid(t) && t.cgrad_radius == 2.0 * r && t.cgrad_max_nn == kColoredGradMaxNN) return O3DS_OK;
+  return color_gradients_t<P4>(h, t, 2.0 * r, kColoredGradMaxNN);
+}
+
+template <typename P4>
+int colored_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, double lambda, o3ds_icp_result* out) {
+  const double r = p.max_correspondence_distance;
+  const int rc = ensure_registration_gradients_t<P4>(h, t, r);
+  if (rc) return rc;
+  const double sg = std::sqrt(lambda), sp = std::sqrt(1.0 - lambda);
+  return step_loop_t<P4>(h, s, t, init, p, out, [&](const double* T, const ColoredPass& cp) { return colored_pass_t<P4>(h, s, t, T, r, sg, sp, cp); });
+}
+
+// ---- [O3D] robust loss kernels on the point-to-plane and the coloured estimator (robust_icp_kernels.hpp) ------------------------------
+constexpr int kSpanRobustStep = 17;
+
+struct RobustSpec {
+  bool colored = false;
+  double sg = 1.0, sp = 0.0;  // sqrt(lambda), sqrt(1 - lambda); COLORED only
+  RobustLossDev loss{O3DS_LOSS_L2, 0.0};
+};
+
+// one correspondence pass under T and its weighted reduction into cp.d_record; nothing waits
+template <typename P4>
+int robust_pass_t(o3ds_handle h, const CloudRec& s, const CloudRec& t, const double T[16], double r, const RobustSpec& spec, const ColoredPass& cp) {
+  if (cp.empty) {
+    HIP_TRY(hipMemsetAsync(cp.d_record, 0, sizeof(double) * kRec, h->stream));
+    return O3DS_OK;
+  }
+  const int rc = neighbor_run_t<P4>(h, s, t, T, nullptr, s.n, 1, r, cp.d_fin, cp.d_idx, cp.d_d2, cp.d_cnt, nullptr, nullptr);
+  if (rc) return rc;
+  const unsigned int grid = (unsigned int)cp.nblocks;
+  span_mark(h, kSpanRobustStep);
+  if (spec.colored)
+    robust_step_kernel<P4, true><<<grid, kColStepBlock, 0, h->stream>>>((const P4*)s.pts, (const P4*)s.col, s.n, mat34(T), (const P4*)t.pts, (const P4*)t.nrm,
+                                                                       (const P4*)t.col, t.cgrad, t.n, cp.d_idx, cp.d_cnt, cp.d_d2, spec.sg, spec.sp, spec.loss,
+                                                                       cp.d_partial);
+  else
+    robust_step_kernel<P4, false><<<grid, kColStepBlock, 0, h->stream>>>((const P4*)s.pts, nullptr, s.n, mat34(T), (const P4*)t.pts, (const P4*)t.nrm, nullptr,
+                                                                        nullptr, t.n, cp.d_idx, cp.d_cnt, cp.d_d2, 1.0, 0.0, spec.loss, cp.d_partial);
+  colored_finish_kernel<<<1, 64, 0, h->stream>>>(cp.d_partial, cp.nblocks, cp.d_record);
+  span_mark(h, kSpanRobustStep);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+template <typename P4>
+int robust_step_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T[16], double r, const RobustSpec& spec, double record[32]) {
+  ColoredPass cp;
+  int rc = colored_prepare_t<P4>(h, s, t, r, cp);
+  if (rc) return rc;
+  rc = robust_pass_t<P4>(h, s, t, T, r, spec, cp);
+  if (rc) return rc;
+  return read_back(h, {{record, cp.d_record, sizeof(double) * kRec}});
+}
+
+template <typename P4>
+int robust_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, const RobustSpec& spec,
+                      o3ds_icp_result* out) {
+  const double r = p.max_correspondence_distance;
+  if (spec.colored) {
+    const int rc = ensure_registration_gradients_t<P4>(h, t, r);
+    if (rc) return rc;
+  }
+  return step_loop_t<P4>(h, s, t, init, p, out, [&](const double* T, const ColoredPass& cp) { return robust_pass_t<P4>(h, s, t, T, r, spec, cp); });
 }
 
 // the checks the step and the registration share; *src / *tgt with their exact sizes, a persistent map folded into its array
@@ -5674,6 +5740,35 @@ int validate_colored(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cl
   if (!t->nrm) return fail(h, O3DS_ERR_NO_NORMALS, "ColoredICP requires target pointcloud to have normals.");  // [O3D]
   if (!t->col) return fail(h, O3DS_ERR_INVALID_ARG, "ColoredICP requires target pointcloud to have colors.");  // [O3D]
   if (s->n > 0 && !s->col) return fail(h, O3DS_ERR_INVALID_ARG, "ColoredICP requires source pointcloud to have colors.");  // [O3D]
+  *src = s;
+  *tgt = t;
+  return O3DS_OK;
+}
+
+// the loss and the estimator, then the clouds: COLORED is held to validate_colored, POINT_TO_PLANE to its checks without the colours
+int validate_robust(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cloud target, double r, int estimator, double lambda,
+                    const o3ds_robust_loss* loss, RobustSpec* spec, CloudRec** src, CloudRec** tgt) {
+  if (!loss) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": null loss");
+  if (loss->kind < O3DS_LOSS_L2 || loss->kind > O3DS_LOSS_TUKEY) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown loss kind");
+  if (loss->reserved != 0) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": o3ds_robust_loss.reserved must be 0");
+  const bool uses_k = loss->kind != O3DS_LOSS_L2 && loss->kind != O3DS_LOSS_L1;
+  if (uses_k && !(std::isfinite(loss->k) && loss->k > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": the loss's k must be finite and > 0");
+  if (estimator != O3DS_ROBUST_POINT_TO_PLANE && estimator != O3DS_ROBUST_COLORED)
+    return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown estimator");
+  spec->colored = estimator == O3DS_ROBUST_COLORED;
+  spec->loss = RobustLossDev{loss->kind, uses_k ? loss->k : 1.0};
+  if (spec->colored) {
+    spec->sg = std::sqrt(lambda);
+    spec->sp = std::sqrt(1.0 - lambda);
+    return validate_colored(h, what, source, target, r, lambda, src, tgt);
+  }
+  CloudRec* s = find_cloud(h, source);
+  CloudRec* t = s ? find_cloud(h, target) : nullptr;
+  if (!s || !t) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown cloud id");
+  if (!(r > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");  // [O3D] RegistrationICP
+  if (t->n == 0) return fail(h, O3DS_ERR_EMPTY, std::string(what) + ": empty target");
+  if (s->precision != t->precision) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": source/target precision mismatch");
+  if (!t->nrm) return fail(h, O3DS_ERR_NO_NORMALS, "TransformationEstimationPointToPlane requires pre-computed normal vectors for target PointCloud.");  // [O3D]
   *src = s;
   *tgt = t;
   return O3DS_OK;
@@ -5736,6 +5831,33 @@ int o3ds_icp_colored_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, co
   const int rc = validate_colored(h, "icp_colored", source, target, params->max_correspondence_distance, lambda_geometric, &s, &t);
   if (rc) return rc;
   return DISPATCH(t->precision, colored_register_t, h, *s, *t, init, *params, lambda_geometric, out);
+}
+
+int o3ds_robust_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance, int estimator,
+                         double lambda_geometric, const o3ds_robust_loss* loss, double record[32]) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!T || !record) return fail(h, O3DS_ERR_INVALID_ARG, "robust_icp_step: null argument");
+  CloudRec *s = nullptr, *t = nullptr;
+  RobustSpec spec;
+  const int rc = validate_robust(h, "robust_icp_step", source, target, max_correspondence_distance, estimator, lambda_geometric, loss, &spec, &s, &t);
+  if (rc) return rc;
+  if (spec.colored && !cgrad_valid(*t))
+    return fail(h, O3DS_ERR_INVALID_ARG, "robust_icp_step: the target has no colour gradients (o3ds_compute_color_gradients)");
+  return DISPATCH(t->precision, robust_step_t, h, *s, *t, T, max_correspondence_distance, spec, record);
+}
+
+int o3ds_icp_robust_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params, int estimator,
+                        double lambda_geometric, const o3ds_robust_loss* loss, o3ds_icp_result* out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!init || !params || !out) return fail(h, O3DS_ERR_INVALID_ARG, "icp_robust: null argument");
+  if (params->max_iteration < 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp_robust: negative max_iteration");
+  CloudRec *s = nullptr, *t = nullptr;
+  RobustSpec spec;
+  const int rc = validate_robust(h, "icp_robust", source, target, params->max_correspondence_distance, estimator, lambda_geometric, loss, &spec, &s, &t);
+  if (rc) return rc;
+  return DISPATCH(t->precision, robust_register_t, h, *s, *t, init, *params, spec, out);
 }
 
 }  // extern "C"
