@@ -244,8 +244,13 @@ int o3ds_icp_generalized_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target
 /* RegistrationIcpPointToPoint::registerClouds (CloudRegistration.cpp:69-74) = [O3D] RegistrationICP with
  * TransformationEstimationPointToPoint: the update of every iteration is the closed-form Eigen::umeyama (no scaling) of the
  * matched pairs; same loop and convergence test.  No normals are needed on either cloud.
- * Step-wise record in this method: [0..8] sum q_a p_b (row-major, q = matched target point, p = transformed source point),
- * [9..11] sum p, [12..14] sum q, [28] #corr, [29] sum d^2, the rest 0. */
+ * Step-wise record in this method: [0..8] sum q'_a p'_b (row-major, q = matched target point, p = transformed source point),
+ * [9..11] sum p', [12..14] sum q', [28] #corr, [29] sum d^2 (of p - q), the rest 0, where p' = p - c and q' = q - c are taken relative to
+ * the session's pivot c: per axis the multiple of 1024 m nearest (rint) to T s_0, the pose of the pass applied to point 0 of the source
+ * CLOUD (not of the range a call covers), and 0 on an axis where that is not finite or beyond 2^30 m.  o3ds_icp_accumulate forms the record about c and
+ * o3ds_icp_update derives the same c from the same pose and point, so records of ranks that hold the same source cloud and pose add up;
+ * a caller that writes a record itself forms it about that c.  Within 512 m of the origin c = 0 and the record is the sums of the
+ * coordinates themselves.  (Sigma = E[q p^T] - E[q] E[p]^T does not depend on c; about a far origin its subtraction cancels.) */
 int o3ds_icp_point_to_point(o3ds_handle h, const double* src_xyz, size_t n_src, const double* tgt_xyz, size_t n_tgt,
                             const double init[16], const o3ds_icp_params* params, o3ds_icp_result* out);
 int o3ds_icp_point_to_point_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3ds_crop* target_crop, const double init[16],

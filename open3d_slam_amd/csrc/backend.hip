@@ -1695,6 +1695,7 @@ int begin_session(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const o3d
   if (upload_state) HIP_TRY(hipMemcpyAsync(h->d_state, h->h_state, sizeof(IcpStateDev), hipMemcpyHostToDevice, h->stream));
   IcpPassArgs a{};
   a.src = src->pts;
+  a.src_f64 = src->precision == O3DS_PRECISION_F64 ? 1 : 0;
   a.first = 0;
   a.count = src->n;
   a.tpts = tgt->spts;
@@ -2409,7 +2410,7 @@ int o3ds_icp_update(o3ds_handle h, const double* d_record, uint64_t n_src_total)
   if (!h->session) return fail(h, O3DS_ERR_INVALID_ARG, "icp_update: no session");
   if (!d_record) return fail(h, O3DS_ERR_INVALID_ARG, "icp_update: null record");
   icp_update_kernel<<<1, 128, 0, h->stream>>>(d_record, h->d_state, (unsigned long long)n_src_total, h->params.max_iteration,
-                                             h->params.relative_fitness, h->params.relative_rmse, h->session_method);
+                                             h->params.relative_fitness, h->params.relative_rmse, h->session_method, h->pass.src, h->pass.src_f64);
   HIP_TRY(hipGetLastError());
   return O3DS_OK;
 }
@@ -2736,7 +2737,7 @@ int o3ds_icp_register_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, c
     launch_accumulate(h, a, nb);
     icp_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(h->d_partials, nb, h->d_state, (unsigned long long)a.count,
                                                           params->max_iteration, params->relative_fitness, params->relative_rmse,
-                                                          h->debug_update, h->session_method, quantum_table(a));
+                                                          h->debug_update, h->session_method, quantum_table(a), a.src, a.src_f64);
   });
 }
 
@@ -5649,7 +5650,7 @@ int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init
     rc = pass(T, cp);
     if (rc) return rc;
     icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
-                                               O3DS_ICP_POINT_TO_PLANE);
+                                               O3DS_ICP_POINT_TO_PLANE, nullptr, 0);
     HIP_TRY(hipGetLastError());
     rc = read_state(h, out);
     if (rc) return rc;

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kUpdBlock) void icp_batch_reduce_update_kernel(IcpB
   IcpStateDev* state = const_cast<IcpStateDev*>(a.state);
   if (state->done) return;
   list_reduce_update(a.partials, ba.start[blockIdx.x + 1] - ba.start[blockIdx.x], a.q_hi, state, (unsigned long long)deal_count(a), max_iter, rel_fitness,
-                     rel_rmse, method);
+                     rel_rmse, method, a.src, a.src_f64);
 }
 
 }  // namespace o3ds

@@ -289,12 +289,21 @@ __global__ __launch_bounds__(256) void ransac_hypothesis_kernel(const P4* __rest
   double rec[kRec];
 #pragma unroll
   for (int k = 0; k < kRec; ++k) rec[k] = 0.0;
+  // the sums are of coordinates relative to the multiples of 1024 m nearest to the first drawn pair (pivot_round; source and target each
+  // about its own: Sigma does not depend on either shift, and formed from far absolute coordinates its subtraction cancels;
+  // umeyama_from_record puts the two pivots back into t).  Clouds within 512 m of the origin: both zero, the sums of the coordinates.
+  double cp[3] = {0.0, 0.0, 0.0}, cq[3] = {0.0, 0.0, 0.0};
   for (int j = 0; j < a.n; ++j) {
     const uint32_t c = ransac_draw(a.seed, a.n, t, j, a.m);
     if (a.samples) a.samples[(size_t)slot * kRansacMaxN + j] = c;
     double px, py, pz, qx, qy, qz;
     load_xyz(src, a.corr[2 * (size_t)c], &px, &py, &pz);
     load_xyz(tgt, a.corr[2 * (size_t)c + 1], &qx, &qy, &qz);
+    if (j == 0) {
+      cp[0] = pivot_round(px), cp[1] = pivot_round(py), cp[2] = pivot_round(pz);
+      cq[0] = pivot_round(qx), cq[1] = pivot_round(qy), cq[2] = pivot_round(qz);
+    }
+    px -= cp[0], py -= cp[1], pz -= cp[2], qx -= cq[0], qy -= cq[1], qz -= cq[2];
     rec[0] += qx * px, rec[1] += qx * py, rec[2] += qx * pz;
     rec[3] += qy * px, rec[4] += qy * py, rec[5] += qy * pz;
     rec[6] += qz * px, rec[7] += qz * py, rec[8] += qz * pz;
@@ -303,7 +312,7 @@ __global__ __launch_bounds__(256) void ransac_hypothesis_kernel(const P4* __rest
     rec[kRecCount] += 1.0;
   }
   double U[16];
-  umeyama_from_record(rec, U);
+  umeyama_from_record(rec, U, cp, cq);
   bool edge_ok = true, dist_ok = true;
   if (a.edge > 0.0) {  // CorrespondenceCheckerBasedOnEdgeLength::Check
     for (int i = 0; i < a.n && edge_ok; ++i) {

@@ -972,6 +972,7 @@ struct IcpPassArgs {
   // common.hpp, CountPub).  Queries are dealt out over `count` as always; the ones at or beyond the exact number are dropped where a query
   // past the end is dropped, and the fitness is taken over the exact number.
   const int* count_dev;
+  int src_f64;  // 1: src holds P4d (what a kernel that is not instantiated per storage type needs to read source point 0: p2p_pivot)
 };
 
 // Per-query record staged in LDS: {J0..J5, r, one, d2, 0}.  Every entry of the 32-double normal-equation record is a
@@ -1202,6 +1203,46 @@ struct SetMargin {
   float w, t;  // |R - I|_F and |t| of the last update U; w < 0: no sets this pass
 };
 
+// The frame of the point-to-point record.  Sigma = E[q p^T] - E[q] E[p]^T from sums of ABSOLUTE coordinates cancels (|mu| / extent)^2 of
+// the products' digits: at (1e5, -2e5, 50) a 0.6 m patch of 20 pairs came out 3e-5 rad off Eigen's demeaned form.  So p and q enter the
+// record relative to a pivot near them: per axis the multiple of 1024 m nearest to T s_0, the pass's pose applied to point 0 of the
+// source cloud (of the CLOUD, not of a rank's range: every rank of a sharded session holds the whole source or the same pose, and the
+// records are summed).  The pass that writes the record and the step that reads it both call this function on the same T and the same
+// point (contraction is off in this file: the same roundings); the shift p - c is one f64 subtraction, exact for a
+// point nearer to c than to the origin (every point of a scene that lies beyond 1024 m and spans less than 512 m) and otherwise rounded
+// once, by at most half an ulp of |p - c|; scenes within 512 m of the origin have
+// c = 0 and keep their bits; a non-finite point or pose, or one beyond 2^30 m, gives 0.
+constexpr double kPivotStep = 1024.0;
+__device__ __forceinline__ double pivot_round(double x) {
+  const double k = rint(x * (1.0 / kPivotStep));
+  return fabs(k) < 0x1p20 ? k * kPivotStep : 0.0;  // (NaN and inf fail the comparison)
+}
+// (s0: source point 0 widened to f64.  The fused kernel fetches it with its first loads and hands it on through LDS, so that neither the
+// step nor the pass waits for a load of its own on the chain of the iteration.)
+__device__ __forceinline__ void p2p_pivot_at(const double* Tm /* 4x4 column-major */, const double* s0, double c[3]) {
+  const double sx = s0[0], sy = s0[1], sz = s0[2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    c[r] = pivot_round(Tm[r] * sx + Tm[4 + r] * sy + Tm[8 + r] * sz + Tm[12 + r]);
+  }
+}
+__device__ __forceinline__ void p2p_pivot(const double* Tm /* 4x4 column-major */, const void* src, int src_f64, double c[3]) {
+  // (x, y, z lead a point of either storage type)
+  const double s0[3] = {src_f64 ? ((const double*)src)[0] : (double)((const float*)src)[0],
+                        src_f64 ? ((const double*)src)[1] : (double)((const float*)src)[1],
+                        src_f64 ? ((const double*)src)[2] : (double)((const float*)src)[2]};
+  p2p_pivot_at(Tm, s0, c);
+}
+// A pass looks at the pivot only AFTER its search: thread 0 leaves it in LDS when the pass starts, and the sum over the queries' slots
+// takes it off there -- slot - c * one in one fma (exact where the comment of p2p_pivot says so), and nothing for a query without a match (one = 0) -- so the search carries no register for
+// it and the slots are written as for every other estimator.  One array per kernel (a function-scope static).
+__device__ __forceinline__ double* p2p_pivot_lds() {
+  __shared__ double s_pivot[4];
+  return s_pivot;
+}
+// this thread's share: the pivot's component for record slot `slot` (0..2 p, 3..5 q; nothing for the others)
+__device__ __forceinline__ double p2p_pivot_of_slot(const double* s_pivot, int slot) { return slot < 6 ? s_pivot[slot < 3 ? slot : slot - 3] : 0.0; }
+
 // The record of ONE correspondence (query at p, matched target point q with normal nq) into its 10 (or, generalized ICP, 32) LDS slots.
 template <typename P4, bool kGicp>
 __device__ __forceinline__ void write_record(const IcpPassArgs& a, double* rec, bool p2p, double px, double py, double pz, const P4& q,
@@ -1259,7 +1300,8 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
                                                 unsigned long long* tr = nullptr /* 3 timestamps, development aid */,
                                                 SetMargin sm = SetMargin{-1.0f, 0.0f}, int* s_set = nullptr /* [kQPB][1 + kSetCap] */,
                                                 size_t n_live = ~(size_t)0 /* queries at or beyond it are dropped (IcpPassArgs::count_dev) */,
-                                                int order = 0 /* how the queries are dealt out (pass_order) */) {
+                                                int order = 0 /* how the queries are dealt out (pass_order) */,
+                                                const double* s_p0 = nullptr /* null, or source point 0 in LDS (p2p_pivot_at) */) {
   constexpr int kQPB = kPassBlock / kGroup;
   n_live = min(n_live, a.count);
   constexpr int kStride = kGicp ? kRec : kRecSlots;  // doubles per query record
@@ -1279,6 +1321,15 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
   // be a load whose latency the verified-match path has nothing to hide behind)
   const int ta = term_slot(inf ? kPackA_inf.lo : (p2p ? kPackA_p2p.lo : kPackA.lo), inf ? kPackA_inf.hi : (p2p ? kPackA_p2p.hi : kPackA.hi), term);
   const int tb = term_slot(inf ? kPackB_inf.lo : (p2p ? kPackB_p2p.lo : kPackB.lo), inf ? kPackB_inf.hi : (p2p ? kPackB_p2p.hi : kPackB.hi), term);
+  double* s_pivot = p2p_pivot_lds();  // read behind the barrier that follows the records
+  if (!kGicp && a.method == O3DS_ICP_POINT_TO_POINT && threadIdx.x == 0) {
+    double c[3] = {0.0, 0.0, 0.0};
+    if (s_p0)
+      p2p_pivot_at(Tm, s_p0, c);
+    else if (n_live > 0)
+      p2p_pivot(Tm, a.src, (int)(sizeof(R) == 8), c);
+    s_pivot[0] = c[0], s_pivot[1] = c[1], s_pivot[2] = c[2];
+  }
   // candidate sets: read (verified matches) whenever the previous pass left them, written whenever this pass has a margin
   const bool sets = !kKeys && a.set_pos != nullptr && s_set != nullptr;
   const bool sets_in = sets && use_cache;
@@ -1498,6 +1549,15 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
     lds_barrier();
     if (tr && threadIdx.x == 0) tr[2] = wall_clock64();
     if (!kSingle && threadIdx.x == 0) s_far[0] = s_far[1] = 0;  // everyone is past the far list (ordered before its next use by the barrier below)
+    if (!kGicp && a.method == O3DS_ICP_POINT_TO_POINT) {  // uniform: the slots relative to the pivot (see p2p_pivot)
+      const double pa = p2p_pivot_of_slot(s_pivot, ta), pb = p2p_pivot_of_slot(s_pivot, tb);
+#pragma unroll
+      for (int qq = 0; qq < kQPB / (kPassBlock / 32); ++qq) {
+        const double* rec = s_rec_flat + (qs * (kQPB / (kPassBlock / 32)) + qq) * kStride;
+        const double one = rec[7];
+        acc = fma(fma(-pa, one, rec[ta]), fma(-pb, one, rec[tb]), acc);
+      }
+    } else {
 #pragma unroll
     for (int qq = 0; qq < kQPB / (kPassBlock / 32); ++qq) {
       const double* rec = s_rec_flat + (qs * (kQPB / (kPassBlock / 32)) + qq) * kStride;
@@ -1505,6 +1565,7 @@ __device__ __forceinline__ double icp_pass_body(const IcpPassArgs& a, const doub
         acc += rec[term];  // the record already holds the 32 terms of this correspondence
       else
         acc = fma(rec[ta], rec[tb], acc);
+    }
     }
     if constexpr (!kSingle) lds_barrier();  // s_rec is rewritten by the next batch
   }
@@ -1958,8 +2019,10 @@ __device__ inline double det3_rm(const double A[9]) {
 }
 
 // [O3D] TransformationEstimationPointToPoint::ComputeTransformation = Eigen::umeyama(source, target, with_scaling = false) from the
-// point-to-point record (sums instead of demeaned matrices: Sigma = E[q p^T] - E[q] E[p]^T).  Ucm: 4x4 column-major.
-__device__ inline void umeyama_from_record(const double* rec, double Ucm[16]) {
+// point-to-point record (sums instead of demeaned matrices: Sigma = E[q p^T] - E[q] E[p]^T).  Ucm: 4x4 column-major.  The record's
+// sums are of p - cp and q - cq (Sigma does not depend on the two pivots; they are what keeps its subtraction from cancelling), so
+// t = mu_q - R mu_p + (cq - R cp); with both pivots zero nothing is added and the bits are those of the unshifted form.
+__device__ inline void umeyama_from_record(const double* rec, double Ucm[16], const double cp[3], const double cq[3]) {
   const double m = rec[kRecCount], inv = 1.0 / m;
   const double ms[3] = {rec[9] * inv, rec[10] * inv, rec[11] * inv}, mt[3] = {rec[12] * inv, rec[13] * inv, rec[14] * inv};
   double S[9];
@@ -1980,7 +2043,9 @@ __device__ inline void umeyama_from_record(const double* rec, double Ucm[16]) {
       Ra[b] = Um[a * 3] * Vm[b * 3] + Um[a * 3 + 1] * Vm[b * 3 + 1] + sgn * Um[a * 3 + 2] * Vm[b * 3 + 2];
       Ucm[b * 4 + a] = Ra[b];
     }
-    Ucm[12 + a] = mt[a] - (Ra[0] * ms[0] + Ra[1] * ms[1] + Ra[2] * ms[2]);
+    const double t = mt[a] - (Ra[0] * ms[0] + Ra[1] * ms[1] + Ra[2] * ms[2]);
+    const double back = cq[a] - (Ra[0] * cp[0] + Ra[1] * cp[1] + Ra[2] * cp[2]);
+    Ucm[12 + a] = back != 0.0 ? t + back : t;
   }
   Ucm[15] = 1.0;
 }
@@ -1999,7 +2064,10 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
                                                int method = O3DS_ICP_POINT_TO_PLANE,
                                                float* s_margin = nullptr /* [2]: |R - I|_F and |t| of the update (candidate-set margin) */,
                                                bool fold_only = false /* uniform; the caller has seen iterations >= max_iter in the state: no
-                                               update can be applied (go = 0 below), so wavefront 0 skips the solve whose result nobody reads */) {
+                                               update can be applied (go = 0 below), so wavefront 0 skips the solve whose result nobody reads */,
+                                               const void* src = nullptr, int src_f64 = 0 /* point-to-point: the source cloud, for the
+                                               pivot of the record (p2p_pivot on the pose the pass ran under, which is still in *st) */,
+                                               const double* s_p0 = nullptr /* or its point 0, already in LDS */) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #define O3DS_TSTAMP(k)                                       \
   do {                                                       \
@@ -2017,7 +2085,14 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
     if (method == O3DS_ICP_POINT_TO_POINT) {  // closed form: U straight from the record, no 6-vector (uniform branch)
       if (lane == 0) {
         double Ucm[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        if (count > 0.0) umeyama_from_record(s_rec, Ucm);  // [O3D] corres.empty() -> Identity
+        if (count > 0.0) {  // [O3D] corres.empty() -> Identity
+          double c[3] = {0.0, 0.0, 0.0};
+          if (s_p0)
+            p2p_pivot_at(st->T, s_p0, c);
+          else if (src)
+            p2p_pivot(st->T, src, src_f64, c);
+          umeyama_from_record(s_rec, Ucm, c, c);
+        }
 #pragma unroll
         for (int k = 0; k < 16; ++k) s_U[k] = Ucm[k];
       }
@@ -2128,7 +2203,8 @@ __device__ __forceinline__ void icp_step_block(const double* s_rec, IcpStateDev*
 // single-GPU path: reduce the partials and step, one workgroup
 __global__ __launch_bounds__(kUpdBlock) void icp_reduce_update_kernel(const double* __restrict__ partials, int nrows, IcpStateDev* state,
                                                                       unsigned long long n_src_total, int max_iter, double rel_fitness,
-                                                                      double rel_rmse, int debug_mode, int method, QuantumTable qt) {
+                                                                      double rel_rmse, int debug_mode, int method, QuantumTable qt,
+                                                                      const void* src, int src_f64) {
   if (state->done) return;
   if (debug_mode == 1) {  // timing experiment: launch + done check only
     if (threadIdx.x == 0) { state->pass += 1; state->iterations += 1; if (state->iterations > max_iter) state->done = 1; }
@@ -2143,19 +2219,20 @@ __global__ __launch_bounds__(kUpdBlock) void icp_reduce_update_kernel(const doub
     if (threadIdx.x == 0) { state->pass += 1; state->iterations += 1; state->fitness = s_out[28]; if (state->iterations > max_iter) state->done = 1; }
     return;
   }
-  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
+  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method, nullptr, false, src, src_f64);
 }
 
 // sharded path: the record was all-reduced by the caller
 __global__ __launch_bounds__(128) void icp_update_kernel(const double* __restrict__ record, IcpStateDev* state, unsigned long long n_src_total,
-                                                        int max_iter, double rel_fitness, double rel_rmse, int method) {
+                                                        int max_iter, double rel_fitness, double rel_rmse, int method, const void* src,
+                                                        int src_f64) {
   if (state->done) return;
   __shared__ double s_out[kRec];
   __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ int s_go;
   if (threadIdx.x < kRec) s_out[threadIdx.x] = record[threadIdx.x];
   __syncthreads();
-  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
+  icp_step_block(s_out, state, n_src_total, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method, nullptr, false, src, src_f64);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2271,6 +2348,16 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   // (the quanta of the epilogue: a per-lane load of a kernel argument, fetched now and parked in LDS -- loaded at the very end it is a
   // memory round trip on the tail of every pass, kept in a register it is live through the whole kernel)
   const double q_hi_mine = threadIdx.x < kRec ? fa.pass.q_hi[threadIdx.x] : 0.0;
+  // (point-to-point: source point 0, for the pivot of the record -- asked for here, parked in LDS in front of the barrier below)
+  __shared__ double s_p0[4];
+  const bool pivoted = !kGicp && fa.pass.method == O3DS_ICP_POINT_TO_POINT;
+  double p0x = 0.0, p0y = 0.0, p0z = 0.0;
+  // (whenever the session's source holds a point, not only when this launch's range does: the tail launch of o3ds_icp_pass_finish and
+  // a rank with an empty share still step on a record that the other launches formed about the pivot of point 0)
+  if (pivoted && threadIdx.x == 0 && fa.pass.src != nullptr && fa.n_src_total > 0) {
+    const P4 s = *(const P4*)fa.pass.src;
+    p0x = (double)s.x, p0y = (double)s.y, p0z = (double)s.z;
+  }
   __builtin_amdgcn_sched_barrier(0);
   // pose-independent loads of this workgroup's queries: source point, cached match or candidate set (points AND normals); they land
   // while the tail of the previous pass is computed
@@ -2295,6 +2382,7 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
     s_far[threadIdx.x] = 0;  // (the one-batch pass body has no barrier of its own in front of the far list: the one below serves)
   }
   if (threadIdx.x < kRec) s_qhi[threadIdx.x] = q_hi_mine;
+  if (pivoted && threadIdx.x == 0) s_p0[0] = p0x, s_p0[1] = p0y, s_p0[2] = p0z;
   lds_barrier();
   if (s_st.done) {  // loop already terminated: hand the final state on
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2310,7 +2398,8 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   if (!first) {
     icp_step_block(s_out, &s_st, n_src_total, fa.max_iter, fa.rel_fitness, fa.rel_rmse, s_x, s_sc, s_U, &s_go,
                    fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 8 : nullptr, fa.pass.method, s_margin,
-                   /* fold_only: the last launch of a registration that ran out of iterations */ s_st.iterations >= fa.max_iter);
+                   /* fold_only: the last launch of a registration that ran out of iterations */ s_st.iterations >= fa.max_iter,
+                   nullptr, 0, pivoted ? s_p0 : nullptr);
     lds_barrier();
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2331,9 +2420,9 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
   const bool collect = fa.pass.set_pos != nullptr && sm.w >= 0.0f && fa.pass.set_gain * sm.t <= fa.pass.set_cap;
   unsigned long long* const trb = fa.trace ? fa.trace + (size_t)blockIdx.x * 16 + 13 : nullptr;
   const double v = collect ? icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, true, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, s_far,
-                                                                                              use_cache, qp, trb, sm, s_set, n_live, order)
+                                                                                              use_cache, qp, trb, sm, s_set, n_live, order, pivoted ? s_p0 : nullptr)
                            : icp_pass_body<P4, kCrop, kPassBlock, kGroup, kGicp, false, false, true>(fa.pass, s_st.T, blockIdx.x, gridDim.x, s_rec, s_red, s_seg, s_far,
-                                                                                               use_cache, qp, trb, sm, s_set, n_live, order);
+                                                                                               use_cache, qp, trb, sm, s_set, n_live, order, pivoted ? s_p0 : nullptr);
   O3DS_STAMP(3);
   // ---------------- epilogue: add the record to this workgroup's slot, exactly ----------------
   if (threadIdx.x < kRec) {

@@ -34,6 +34,12 @@ __device__ __forceinline__ ListQuery<typename Scalar<P4>::type> list_place_query
   q.t21 = to_sgpr(Tm[6]), q.t02 = to_sgpr(Tm[8]), q.t12 = to_sgpr(Tm[9]), q.t22 = to_sgpr(Tm[10]), q.t03 = to_sgpr(Tm[12]),
   q.t13 = to_sgpr(Tm[13]), q.t23 = to_sgpr(Tm[14]);
   q.px = 0, q.py = 0, q.pz = 0;
+  if (a.method == O3DS_ICP_POINT_TO_POINT && threadIdx.x == 0) {  // the record's pivot, for list_sum_row (behind the callers' barriers)
+    double c[3] = {0.0, 0.0, 0.0};
+    if (deal_count(a) > 0) p2p_pivot(Tm, a.src, (int)(sizeof(R) == 8), c);
+    double* s_pivot = p2p_pivot_lds();
+    s_pivot[0] = c[0], s_pivot[1] = c[1], s_pivot[2] = c[2];
+  }
   if (live) {
     const P4 s = ((const P4*)a.src)[a.first + i];
     q.px = q.t00 * (double)s.x + q.t01 * (double)s.y + q.t02 * (double)s.z + q.t03;  // [O3D] PointCloud::Transform, as icp_pass_body
@@ -140,13 +146,24 @@ __device__ __forceinline__ void list_sum_row(const double* s_rec, double (*s_red
   const int ta = term_slot(p2p ? kPackA_p2p.lo : kPackA.lo, p2p ? kPackA_p2p.hi : kPackA.hi, term);
   const int tb = term_slot(p2p ? kPackB_p2p.lo : kPackB.lo, p2p ? kPackB_p2p.hi : kPackB.hi, term);
   double acc = 0.0;
+  if (!kGicp && p2p) {  // uniform: the slots relative to the pivot list_place_query left (as icp_pass_body)
+    const double* s_pivot = p2p_pivot_lds();
+    const double pa = p2p_pivot_of_slot(s_pivot, ta), pb = p2p_pivot_of_slot(s_pivot, tb);
 #pragma unroll
-  for (int qq = 0; qq < kQPB / kSlices; ++qq) {
-    const double* rec = s_rec + (qs * (kQPB / kSlices) + qq) * kStride;
-    if (kGicp)
-      acc += rec[term];
-    else
-      acc = fma(rec[ta], rec[tb], acc);
+    for (int qq = 0; qq < kQPB / kSlices; ++qq) {
+      const double* rec = s_rec + (qs * (kQPB / kSlices) + qq) * kStride;
+      const double one = rec[7];
+      acc = fma(fma(-pa, one, rec[ta]), fma(-pb, one, rec[tb]), acc);
+    }
+  } else {
+#pragma unroll
+    for (int qq = 0; qq < kQPB / kSlices; ++qq) {
+      const double* rec = s_rec + (qs * (kQPB / kSlices) + qq) * kStride;
+      if (kGicp)
+        acc += rec[term];
+      else
+        acc = fma(rec[ta], rec[tb], acc);
+    }
   }
   s_red[qs][term] = acc;
   lds_barrier();
@@ -167,13 +184,14 @@ __device__ __forceinline__ void list_sum_row(const double* s_rec, double (*s_red
 // quanta q_hi), convergence test, solve, T <- U * T (icp_step_block) -- what icp_reduce_update_kernel does for one pair.  `den` is the
 // fitness denominator.
 __device__ __forceinline__ void list_reduce_update(const double* __restrict__ partials, int nrows, const double* q_hi, IcpStateDev* state,
-                                                   unsigned long long den, int max_iter, double rel_fitness, double rel_rmse, int method) {
+                                                   unsigned long long den, int max_iter, double rel_fitness, double rel_rmse, int method,
+                                                   const void* src, int src_f64) {
   __shared__ double s_part[2 * (kUpdBlock / 32) * kRec];
   __shared__ double s_out[kRec];
   __shared__ double s_x[8], s_sc[8], s_U[16];
   __shared__ int s_go;
   reduce_partials(partials, nrows, q_hi, s_part, s_out);
-  icp_step_block(s_out, state, den, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method);
+  icp_step_block(s_out, state, den, max_iter, rel_fitness, rel_rmse, s_x, s_sc, s_U, &s_go, nullptr, method, nullptr, false, src, src_f64);
 }
 
 }  // namespace o3ds

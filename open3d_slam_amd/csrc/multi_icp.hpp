@@ -88,6 +88,7 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
   }
   src = find_cloud_lazy(h, source);  // (a persistent-form source was folded by the first session)
   ma.pass.src = h->pass.src;
+  ma.pass.src_f64 = h->pass.src_f64;
   ma.pass.count = h->pass.count;
   ma.pass.count_dev = h->pass.count_dev;
   ma.pass.snrm = h->pass.snrm;
@@ -114,7 +115,8 @@ int o3ds_icp_register_multi(o3ds_handle h, int form, o3ds_cloud source, const o3
   return two_launch_loop(h, total_passes, look_at_session_state(h, out), [&] {  // the host loop of o3ds_icp_register_dev's two-launch form
     launch_multi_accumulate(h, ma, nb);
     icp_multi_reduce_update_kernel<<<1, kUpdBlock, 0, h->stream>>>(d_rows, nrows, h->d_state, n_upper, ma.pass.count_dev, den_mult, params->max_iteration,
-                                                                params->relative_fitness, params->relative_rmse, params->method, quantum_table(ma.pass));
+                                                                params->relative_fitness, params->relative_rmse, params->method, quantum_table(ma.pass), ma.pass.src,
+                                                                ma.pass.src_f64);
   });
 }
 

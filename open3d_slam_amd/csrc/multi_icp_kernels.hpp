@@ -155,10 +155,10 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
 __global__ __launch_bounds__(kUpdBlock) void icp_multi_reduce_update_kernel(const double* __restrict__ partials, int nrows, IcpStateDev* state,
                                                                             size_t count, const int* count_dev, unsigned long long den_mult,
                                                                             int max_iter, double rel_fitness, double rel_rmse, int method,
-                                                                            QuantumTable qt) {
+                                                                            QuantumTable qt, const void* src, int src_f64) {
   if (state->done) return;
   const size_t n = count_dev ? min((size_t)*count_dev, count) : count;
-  list_reduce_update(partials, nrows, qt.q, state, (unsigned long long)n * den_mult, max_iter, rel_fitness, rel_rmse, method);
+  list_reduce_update(partials, nrows, qt.q, state, (unsigned long long)n * den_mult, max_iter, rel_fitness, rel_rmse, method, src, src_f64);
 }
 
 }  // namespace o3ds

@@ -68,7 +68,10 @@ def icp_point_to_plane(src, tgt, nrm, max_corr, init=None, max_iter=30, rel_fitn
 
 
 def umeyama_update(P, Q, corr):
-    """Eigen::umeyama(source, target, with_scaling=False) on the matched pairs ([O3D] TransformationEstimationPointToPoint)."""
+    """Eigen::umeyama(source, target, with_scaling=False) on the matched pairs ([O3D] TransformationEstimationPointToPoint): means
+    first, covariance of the DEMEANED points.  The device sums coordinates instead (the point-to-point record of
+    include/o3ds_backend.h) and keeps the subtraction Sigma = E[q p^T] - E[q] E[p]^T from cancelling by taking them relative to a pivot
+    near the pairs (a multiple of 1024 m); tests/point_to_point_restatement.py holds it to this form in longdouble."""
     m = corr >= 0
     if not m.any():
         return np.eye(4)

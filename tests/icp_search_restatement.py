@@ -95,11 +95,23 @@ def nearest_within(src, tgt, T, r, storage, keep=None, chunk=64) -> Matches:
     return Matches(idx, np.where(idx >= 0, best, np.inf), gap, best, p, q)
 
 
+PIVOT_STEP = 1024.0
+
+
+def record_pivot(x) -> np.ndarray:
+    """o3ds_backend.h, the point-to-point record: per axis the multiple of 1024 m nearest to x (rint), 0 where x is not finite or beyond
+    2^30 m.  Zero for every point within 512 m of the origin."""
+    with np.errstate(invalid="ignore"):
+        k = np.rint(np.asarray(x, dtype=np.float64) / PIVOT_STEP)
+        return np.where(np.abs(k) < 2.0 ** 20, k * PIVOT_STEP, 0.0)
+
+
 def record(p, tgt, nrm, idx, storage, method=METHOD_POINT_TO_PLANE, src_nrm=None, T=None, eps=GICP_EPSILON):
     """(record[32], scale[32]): the step record of o3ds_backend.h over the matches idx (-1 = none) of the transformed, unrounded source
     points p, and per term the sum of |addends|.  Point-to-plane: [0..20] upper triangle of JtJ row-major, [21..26] Jtr, [27] sum r^2,
     [28] count, [29] sum d^2, J = [p x n ; n], r = (p - t) . n.  Point-to-point: [0..8] sum t_a p_b row-major, [9..11] sum p,
-    [12..14] sum t, [28], [29].  Generalized (needs src_nrm and the pose T): record_gicp, whose scale is its own."""
+    [12..14] sum t, [28], [29], with p and t taken relative to the pivot of the pass (record_pivot of p[0]: p is the WHOLE transformed
+    source, so p[0] is the pose applied to point 0 of the source cloud); d^2 is of the points themselves.  Generalized (needs src_nrm and the pose T): record_gicp, whose scale is its own."""
     if method == METHOD_GENERALIZED:
         return record_gicp(p, tgt, nrm, src_nrm, idx, T, eps, storage)
     t_all = to_storage(np.asarray(tgt, dtype=np.float64).reshape(-1, 3), storage)
@@ -110,6 +122,8 @@ def record(p, tgt, nrm, idx, storage, method=METHOD_POINT_TO_PLANE, src_nrm=None
     d2 = D[:, 0] * D[:, 0] + D[:, 1] * D[:, 1] + D[:, 2] * D[:, 2]
     terms = [None] * 32
     if method == METHOD_POINT_TO_POINT:
+        c = record_pivot(np.asarray(p, dtype=np.float64)[0])
+        P, Q = P - c, Q - c  # (one subtraction, as the device's fma(-c, 1, slot): exact for a point nearer to c than to the origin)
         for a in range(3):
             for b in range(3):
                 terms[3 * a + b] = Q[:, a] * P[:, b]
