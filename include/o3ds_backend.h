@@ -948,6 +948,75 @@ int o3ds_robust_icp_step(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, co
 int o3ds_icp_robust_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* params,
                         int estimator, double lambda_geometric, const o3ds_robust_loss* loss, o3ds_icp_result* out);
 
+/* ---- degeneracy-aware ICP: which directions the normal equations of a pass leave unconstrained, and the update solved in the others only
+ * (Zhang, Kaess, Singh, "On degeneracy of optimization-based state estimation", ICRA 2016: solution remapping; Tuna et al., X-ICP, 2022:
+ * rotation and translation analysed apart, so that radians and metres are never compared).  In a corridor, on an open floor or facing one
+ * wall the 6x6 system of the geometric estimators is near-singular: the solve makes something of a pivot that is noise, the pose slides
+ * along the unobservable direction, and fitness and inlier_rmse stay excellent.  OFFERED like the two sections above and switched on nowhere;
+ * with both thresholds 0 the registration below is o3ds_icp_robust_dev to the byte.  tests/degeneracy_restatement.py is this text in numpy.
+ *
+ * INPUT of the analysis: the 32-double record of a pass under the pose T (o3ds_robust_icp_step's: H = the symmetric matrix of [0..20],
+ * g = -[21..26], n_corr = [28]) and c0, the centre of the source as stored, as o3ds_cloud_center forms it, taken once per call.
+ * ARITHMETIC: f64, every operation rounded on its own (no fused multiply-add).  Every product of 6x6 matrices and of a matrix and a vector
+ * is the dense one: entry (i, j) = P[i][0] Q[0][j], then + P[i][k] Q[k][j] for k = 1 .. 5, zeros included.
+ *  1. RE-CENTRE.  c[i] = ((T[i][0] c0.x + T[i][1] c0.y) + T[i][2] c0.z) + T[i][3].  With x = (omega, t) the parameters of the update about
+ *     the map origin and x_c those of the same motion as a rotation about c, x = M x_c, M = [[I, 0], [[c]x, I]], [c]x = ((0, -c.z, c.y),
+ *     (c.z, 0, -c.x), (-c.y, c.x, 0)).  W = H M;  H_c = M^T W;  g_c = M^T g.  Of H_c the UPPER triangle is what is read below.  Without this the
+ *     rotation block of a scan far from the origin is dominated by |p|^2 and says nothing about the scan.
+ *  2. EIGEN-DECOMPOSE H_rr = H_c[0:3, 0:3] and, apart from it, H_tt = H_c[3:6, 3:6]: cyclic Jacobi, EIGHT sweeps over the pairs (0,1),
+ *     (0,2), (1,2), from V = I.  One rotation on (p, q), r the third index: nothing if a_pq == 0; else theta = (a_qq - a_pp) / (2 a_pq);
+ *     t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta theta + 1));  c = 1 / sqrt(t t + 1);  s = t c;  h = t a_pq;  a_pp = a_pp - h;
+ *     a_qq = a_qq + h;  a_pq = 0;  (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq);  for each row k of V: (V_kp, V_kq) = (c V_kp - s V_kq,
+ *     s V_kp + c V_kq).  The values are the diagonal, the vectors the columns of V.  ORDER: ascending, by exchanging the pairs (0,1), (1,2),
+ *     (0,1) in turn where the first value is > the second.  SIGN: a vector is negated if its component of largest magnitude (the first of
+ *     equals) is < 0.
+ *  3. NORMALISE: lambda^ = lambda / n_corr, the mean information per correspondence (point-to-plane: the three translation values sum to 1;
+ *     the rotation values are in m^2).  There is no other form and no threshold on raw eigenvalues.
+ *  4. DEGENERATE: rotation direction i iff lambda^_i < min_eigenvalue_rotation, translation direction iff lambda^ < min_eigenvalue_translation,
+ *     the comparison as written.  n_corr == 0 (not > 0): all six are degenerate and every lambda^ is +0.0.
+ *  5. THE SOLVE.  No direction degenerate: the ordinary solve of the ORIGINAL record, the very tail o3ds_icp_robust_dev runs (the LDL^T with
+ *     symmetric pivoting of every step loop here), bit for bit.  Otherwise, with V = blockdiag(V_r, V_t): W = H_c V (H_c symmetric from its upper
+ *     triangle), A = V^T W, b = V^T g_c; for every degenerate index i row and column i of A become those of the unit matrix and b_i = +0.0;
+ *     y = the same LDL^T solve of (upper triangle of A, b);  x_c = V y;  x = M x_c;  x = x + 0.0.  That x minimises the pass's quadratic among
+ *     the updates without motion along the dropped directions.
+ *  6. APPLY: T <- (Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5) T, convergence rule and loop exactly those of o3ds_icp_robust_dev.
+ * Thresholds: both finite and >= 0; (0, 0) switches the feature off (no lambda^ of a pass with correspondences is < 0 -- unless it is NaN or
+ * rounding made a vanishing value negative, which 0 then rightly drops).  No default is offered: DESIGN.md 7.11 quotes the values measured on
+ * the test scenes. */
+typedef struct {
+  double min_eigenvalue_rotation, min_eigenvalue_translation;
+} o3ds_degeneracy_params; /* 16 bytes */
+typedef struct {
+  double record[32];       /* the pass's record */
+  double centre[3];        /* c = T c0 */
+  double eigenvalues[6];   /* normalised; [0..2] rotation ascending, [3..5] translation ascending */
+  double eigenvectors[36]; /* V, row-major, in the re-centred parameters: column i belongs to eigenvalues[i] */
+  int32_t degenerate[6];
+  int32_t n_degenerate;
+  int32_t reserved;
+  double x[6]; /* the update this pass would apply */
+} o3ds_localizability; /* 696 bytes */
+typedef struct {
+  double centre[3], eigenvalues[6], eigenvectors[36]; /* of the last pass evaluated, whether or not its update was applied */
+  int32_t degenerate[6];
+  int32_t n_degenerate;
+  int32_t ever_degenerate[6];   /* OR of `degenerate` over the passes whose update was applied */
+  int32_t n_passes_constrained; /* how many of those dropped at least one direction */
+} o3ds_degeneracy_report; /* 416 bytes */
+/* 1. ONE STEP AND ITS ANALYSIS, the testable unit: the record of o3ds_robust_icp_step(source, target, T, ...), steps 1 to 5 on it, and x.
+ *    estimator, lambda_geometric and loss are o3ds_robust_icp_step's (the L2 loss gives the plain estimator).  Errors: those of
+ *    o3ds_robust_icp_step; O3DS_ERR_INVALID_ARG for a null params or out and for a threshold that is negative, NaN or infinite.  An empty
+ *    source or a pass without a pair gives the zero record, hence n_corr == 0: six degenerate directions, V = I, x = 0. */
+int o3ds_icp_localizability(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance,
+                            int estimator, double lambda_geometric, const o3ds_robust_loss* loss, const o3ds_degeneracy_params* params,
+                            o3ds_localizability* out);
+/* 2. THE REGISTRATION: o3ds_icp_robust_dev with step 5 in the place of its solve.  `report` may be NULL.  Errors: those of
+ *    o3ds_icp_robust_dev and of the step above.  An empty source: fitness 0, the initial pose, an all-zero report.  The result and the
+ *    report are functions of the arguments alone: two calls give the same bytes. */
+int o3ds_icp_degeneracy_aware_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* icp_params,
+                                  int estimator, double lambda_geometric, const o3ds_robust_loss* loss, const o3ds_degeneracy_params* params,
+                                  o3ds_icp_result* out, o3ds_degeneracy_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,20 @@ class RobustLoss(C.Structure):  # o3ds_robust_loss
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("k", C.c_double)]
 
 
+class DegeneracyParams(C.Structure):  # o3ds_degeneracy_params
+    _fields_ = [("min_eigenvalue_rotation", C.c_double), ("min_eigenvalue_translation", C.c_double)]
+
+
+class Localizability(C.Structure):  # o3ds_localizability
+    _fields_ = [("record", C.c_double * 32), ("centre", C.c_double * 3), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36),
+                ("degenerate", C.c_int32 * 6), ("n_degenerate", C.c_int32), ("reserved", C.c_int32), ("x", C.c_double * 6)]
+
+
+class DegeneracyReport(C.Structure):  # o3ds_degeneracy_report
+    _fields_ = [("centre", C.c_double * 3), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36), ("degenerate", C.c_int32 * 6),
+                ("n_degenerate", C.c_int32), ("ever_degenerate", C.c_int32 * 6), ("n_passes_constrained", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _H = C.c_void_p
 _CL = C.c_uint64
@@ -226,6 +240,10 @@ SIGNATURES = {
     "o3ds_icp_colored_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_double, C.POINTER(IcpResult)]),
     "o3ds_robust_icp_step": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.c_int, C.c_double, C.POINTER(RobustLoss), _dp]),
     "o3ds_icp_robust_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_int, C.c_double, C.POINTER(RobustLoss), C.POINTER(IcpResult)]),
+    "o3ds_icp_localizability": (C.c_int, [_H, _CL, _CL, _dp, C.c_double, C.c_int, C.c_double, C.POINTER(RobustLoss), C.POINTER(DegeneracyParams),
+                                          C.POINTER(Localizability)]),
+    "o3ds_icp_degeneracy_aware_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_int, C.c_double, C.POINTER(RobustLoss),
+                                                C.POINTER(DegeneracyParams), C.POINTER(IcpResult), C.POINTER(DegeneracyReport)]),
     "o3ds_feature_correspondences": (C.c_int, [_H, _CL, _CL, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_int)]),
     "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
@@ -694,6 +712,38 @@ class Backend:
         self._ck(self.lib.o3ds_icp_robust_dev(self.h, source, target, ip, C.byref(p), int(estimator), float(lambda_geometric), C.byref(ls),
                                               C.byref(out)))
         return bytes(out) if raw else self._result(out)
+
+    # -- degeneracy-aware ICP: the localizability of a step and the constrained update (o3ds_backend.h, the last section)
+    @staticmethod
+    def _analysis(a) -> dict:
+        """the fields a Localizability and a DegeneracyReport share"""
+        return dict(centre=np.array(a.centre), eigenvalues=np.array(a.eigenvalues), eigenvectors=np.array(a.eigenvectors).reshape(6, 6),
+                    degenerate=np.array(a.degenerate, dtype=np.int32), n_degenerate=int(a.n_degenerate))
+
+    def icp_localizability(self, source: int, target: int, max_corr: float, min_eigenvalue_rotation: float = 0.0,
+                           min_eigenvalue_translation: float = 0.0, estimator: int = ROBUST_POINT_TO_PLANE, loss=None,
+                           lambda_geometric: float = 0.968, T=None, raw: bool = False):
+        """o3ds_icp_localizability: the record of one pass under T (None: identity), its analysis and the update it would apply"""
+        T0, ip = (None, _IDENTITY16) if T is None else _d(colmajor(T))
+        ls, dp, out = self._loss(loss), DegeneracyParams(float(min_eigenvalue_rotation), float(min_eigenvalue_translation)), Localizability()
+        self._ck(self.lib.o3ds_icp_localizability(self.h, source, target, ip, float(max_corr), int(estimator), float(lambda_geometric), C.byref(ls),
+                                                  C.byref(dp), C.byref(out)))
+        return bytes(out) if raw else dict(self._analysis(out), record=np.array(out.record), x=np.array(out.x))
+
+    def icp_degeneracy_aware(self, source: int, target: int, max_corr, min_eigenvalue_rotation: float = 0.0, min_eigenvalue_translation: float = 0.0,
+                             estimator: int = ROBUST_POINT_TO_PLANE, loss=None, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                             lambda_geometric: float = 0.968, raw: bool = False):
+        """o3ds_icp_degeneracy_aware_dev: (result, report); raw=True returns the bytes of the two structs instead of the dicts"""
+        T0, ip = (None, _IDENTITY16) if init is None else _d(colmajor(init))
+        p = self._params(max_corr, max_iter, rel_fitness, rel_rmse)
+        ls, dp = self._loss(loss), DegeneracyParams(float(min_eigenvalue_rotation), float(min_eigenvalue_translation))
+        out, rep = IcpResult(), DegeneracyReport()
+        self._ck(self.lib.o3ds_icp_degeneracy_aware_dev(self.h, source, target, ip, C.byref(p), int(estimator), float(lambda_geometric), C.byref(ls),
+                                                        C.byref(dp), C.byref(out), C.byref(rep)))
+        if raw:
+            return bytes(out), bytes(rep)
+        return self._result(out), dict(self._analysis(rep), ever_degenerate=np.array(rep.ever_degenerate, dtype=np.int32),
+                                       n_passes_constrained=int(rep.n_passes_constrained))
 
     # -- sharded registrations inside the library (RCCL through dlopen; o3ds_backend.h)
     SHARD_SOURCE, SHARD_SUBMAP, SHARD_UNION = 0, 1, 2

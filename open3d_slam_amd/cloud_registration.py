@@ -293,6 +293,43 @@ def createRobustIcp(p: CloudRegistrationParameters, kernel: RobustKernel, estima
     return ret
 
 
+class RegistrationIcpDegeneracyAware(RegistrationIcpRobust):
+    """RegistrationIcpRobust whose update is solved only in the directions the pass constrains (o3ds_icp_degeneracy_aware_dev): a direction
+    of the rotation or of the translation whose normalised eigenvalue lies below its minimum is left where the initial guess put it.  With
+    both minima 0 -- the only default -- it is RegistrationIcpRobust to the byte.  `lastReport` holds the report of the last call."""
+
+    def __init__(self):
+        super().__init__()
+        self.minEigenvalueRotation_ = 0.0     # m^2 per correspondence
+        self.minEigenvalueTranslation_ = 0.0  # the point-to-plane values of a pass sum to 1
+        self.lastReport = None
+
+    def registerClouds(self, source: PointCloud, target: PointCloud, init) -> RegistrationResult:
+        if self.estimator_ not in ROBUST_ESTIMATORS:
+            raise RuntimeError(f"estimator_ {self.estimator_!r}: one of {sorted(ROBUST_ESTIMATORS)}")
+        c = self.icpConvergenceCriteria_
+        try:
+            r, self.lastReport = source.be.icp_degeneracy_aware(
+                source.id, target.id, self.maxCorrespondenceDistance_, self.minEigenvalueRotation_, self.minEigenvalueTranslation_,
+                ROBUST_ESTIMATORS[self.estimator_], self.kernel_.toBackend(), init=init, max_iter=c.max_iteration_,
+                rel_fitness=c.relative_fitness_, rel_rmse=c.relative_rmse_, lambda_geometric=self.lambdaGeometric_)
+        except _b.BackendError as e:
+            raise RuntimeError(str(e)) from e
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+
+def createDegeneracyAwareIcp(p: CloudRegistrationParameters, estimator: str = "point_to_plane", kernel: RobustKernel = L2Loss(),
+                             minEigenvalueRotation: float = 0.0, minEigenvalueTranslation: float = 0.0) -> RegistrationIcpDegeneracyAware:
+    ret = RegistrationIcpDegeneracyAware()  # as createRobustIcp
+    ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_
+    ret.knnNormalEstimation_ = p.icp_.knn_
+    ret.maxRadiusNormalEstimation_ = p.icp_.maxDistanceKnn_
+    ret.icpConvergenceCriteria_.max_iteration_ = p.icp_.maxNumIter_
+    ret.kernel_, ret.estimator_ = kernel, estimator
+    ret.minEigenvalueRotation_, ret.minEigenvalueTranslation_ = float(minEigenvalueRotation), float(minEigenvalueTranslation)
+    return ret
+
+
 def createPointToPointIcp(p: CloudRegistrationParameters) -> RegistrationIcpPointToPoint:  # CloudRegistration.cpp:76-81
     ret = RegistrationIcpPointToPoint()
     ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_

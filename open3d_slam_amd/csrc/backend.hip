@@ -33,6 +33,7 @@
 #include "plane_kernels.hpp"    // (and these follow the clustering's)
 #include "colored_icp_kernels.hpp"  // (and these the plane's)
 #include "robust_icp_kernels.hpp"   // (and this one the coloured step's)
+#include "degeneracy_kernels.hpp"   // (and this one the robust step's)
 
 using namespace o3ds;
 
@@ -5628,8 +5629,9 @@ int colored_step_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T
 // [O3D] RegistrationICP's loop around the joint step: the record of every pass goes to the tail the sharded path runs (icp_update_kernel:
 // convergence test, 6x6 LDL^T, T <- U T), and the host reads the state it publishes -- the next pose and whether the loop has ended
 // `pass(T, cp)` enqueues one correspondence pass under T and leaves its record in cp.d_record (colored_pass_t, robust_pass_t)
-template <typename P4, typename Pass>
-int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass) {
+// `tail(cp)` enqueues the one-workgroup kernel that turns the record into the next state (icp_update_kernel, or the degeneracy-aware one)
+template <typename P4, typename Pass, typename Tail>
+int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass, Tail tail) {
   const double r = p.max_correspondence_distance;
   ColoredPass cp;
   int rc = colored_prepare_t<P4>(h, s, t, r, cp);  // the finite count's read-back and the index check: once, not per pass
@@ -5649,14 +5651,20 @@ int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init
     memcpy(T, h->h_state->T, sizeof(T));
     rc = pass(T, cp);
     if (rc) return rc;
-    icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
-                                               O3DS_ICP_POINT_TO_PLANE, nullptr, 0);
+    tail(cp);
     HIP_TRY(hipGetLastError());
     rc = read_state(h, out);
     if (rc) return rc;
     if (h->h_state->done) break;
   }
   return O3DS_OK;
+}
+template <typename P4, typename Pass>
+int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass) {
+  return step_loop_t<P4>(h, s, t, init, p, out, pass, [&](const ColoredPass& cp) {
+    icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
+                                               O3DS_ICP_POINT_TO_PLANE, nullptr, 0);
+  });
 }
 
 // the target's gradients of (2 r, 30), as [O3D] RegistrationColoredICP initialises it: made if absent or of other parameters, and left
@@ -5774,6 +5782,105 @@ int validate_robust(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_clo
   *tgt = t;
   return O3DS_OK;
 }
+
+// ---- degeneracy-aware ICP (degeneracy_kernels.hpp): the analysis of a pass's 6x6 system and the update constrained to what it observes ----
+struct DegeneracyRun {
+  DegeneracyDev* d_dg = nullptr;
+  double* d_c0 = nullptr;
+};
+
+// the device struct next to the state, zeroed, and c0 = the source's centre as o3ds_cloud_center forms it: once per call, nothing waits
+template <typename P4>
+int degeneracy_prepare_t(o3ds_handle h, const CloudRec& s, DegeneracyRun& run) {
+  TMP_ALLOC(run.d_dg, sizeof(DegeneracyDev));
+  TMP_ALLOC(run.d_c0, sizeof(double) * 3);
+  HIP_TRY(hipMemsetAsync(run.d_dg, 0, sizeof(DegeneracyDev), h->stream));
+  HIP_TRY(hipMemsetAsync(run.d_c0, 0, sizeof(double) * 3, h->stream));
+  if (s.n == 0) return O3DS_OK;
+  double* partial = nullptr;
+  TMP_ALLOC(partial, sizeof(double) * 3 * kCenterChunks);
+  const CountRef cnt = count_ref(h, s);
+  center_partial_kernel<P4><<<kCenterChunks, kBlock, 0, h->stream>>>((const P4*)s.pts, cnt, partial);
+  center_finish_kernel<<<1, kBlock, 0, h->stream>>>(partial, cnt, run.d_c0);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+void degeneracy_tail(o3ds_handle h, const ColoredPass& cp, const DegeneracyRun& run, const o3ds_degeneracy_params& dp, size_t n_src, int max_iter,
+                     double rel_fitness, double rel_rmse) {
+  icp_degeneracy_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, run.d_dg, run.d_c0, dp.min_eigenvalue_rotation,
+                                                         dp.min_eigenvalue_translation, (unsigned long long)n_src, max_iter, rel_fitness, rel_rmse);
+}
+
+template <typename P4>
+int degeneracy_register_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, const RobustSpec& spec,
+                          const o3ds_degeneracy_params& dp, o3ds_icp_result* out, o3ds_degeneracy_report* report) {
+  const double r = p.max_correspondence_distance;
+  if (report) memset(report, 0, sizeof(*report));
+  if (spec.colored) {
+    const int rc = ensure_registration_gradients_t<P4>(h, t, r);
+    if (rc) return rc;
+  }
+  DegeneracyRun run;
+  int rc = degeneracy_prepare_t<P4>(h, s, run);
+  if (rc) return rc;
+  rc = step_loop_t<P4>(
+      h, s, t, init, p, out, [&](const double* T, const ColoredPass& cp) { return robust_pass_t<P4>(h, s, t, T, r, spec, cp); },
+      [&](const ColoredPass& cp) { degeneracy_tail(h, cp, run, dp, s.n, p.max_iteration, p.relative_fitness, p.relative_rmse); });
+  if (rc || !report || s.n == 0) return rc;
+  DegeneracyDev dg;
+  rc = read_back(h, {{&dg, run.d_dg, sizeof(dg)}});
+  if (rc) return rc;
+  memcpy(report->centre, dg.centre, sizeof(dg.centre));
+  memcpy(report->eigenvalues, dg.eigenvalues, sizeof(dg.eigenvalues));
+  memcpy(report->eigenvectors, dg.eigenvectors, sizeof(dg.eigenvectors));
+  for (int k = 0; k < 6; ++k) {
+    report->degenerate[k] = dg.degenerate[k];
+    report->ever_degenerate[k] = dg.ever_degenerate[k];
+  }
+  report->n_degenerate = dg.n_degenerate;
+  report->n_passes_constrained = dg.n_passes_constrained;
+  return O3DS_OK;
+}
+
+// one pass under T and the tail on a fresh state that may apply one update: the record, the analysis and the x of that pass
+template <typename P4>
+int localizability_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T[16], double r, const RobustSpec& spec, const o3ds_degeneracy_params& dp,
+                     o3ds_localizability* out) {
+  memset(out, 0, sizeof(*out));
+  ColoredPass cp;
+  int rc = colored_prepare_t<P4>(h, s, t, r, cp);
+  if (rc) return rc;
+  DegeneracyRun run;
+  rc = degeneracy_prepare_t<P4>(h, s, run);
+  if (rc) return rc;
+  h->session = false;  // (the handle's one state is taken, as by a registration)
+  IcpStateDev st{};
+  memcpy(st.T, T, sizeof(double) * 16);
+  *h->h_state = st;
+  HIP_TRY(hipMemcpyAsync(h->d_state, h->h_state, sizeof(IcpStateDev), hipMemcpyHostToDevice, h->stream));
+  rc = robust_pass_t<P4>(h, s, t, T, r, spec, cp);
+  if (rc) return rc;
+  degeneracy_tail(h, cp, run, dp, std::max<size_t>(s.n, 1), 1, 0.0, 0.0);
+  HIP_TRY(hipGetLastError());
+  DegeneracyDev dg;
+  rc = read_back(h, {{out->record, cp.d_record, sizeof(double) * kRec}, {&dg, run.d_dg, sizeof(dg)}});
+  if (rc) return rc;
+  memcpy(out->centre, dg.centre, sizeof(dg.centre));
+  memcpy(out->eigenvalues, dg.eigenvalues, sizeof(dg.eigenvalues));
+  memcpy(out->eigenvectors, dg.eigenvectors, sizeof(dg.eigenvectors));
+  for (int k = 0; k < 6; ++k) out->degenerate[k] = dg.degenerate[k];
+  out->n_degenerate = dg.n_degenerate;
+  memcpy(out->x, dg.x, sizeof(dg.x));
+  return O3DS_OK;
+}
+
+int validate_degeneracy(o3ds_handle h, const char* what, const o3ds_degeneracy_params* dp) {
+  if (!dp) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": null degeneracy params");
+  for (const double v : {dp->min_eigenvalue_rotation, dp->min_eigenvalue_translation})
+    if (!(std::isfinite(v) && v >= 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": a minimum eigenvalue must be finite and >= 0");
+  return O3DS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -5859,6 +5966,39 @@ int o3ds_icp_robust_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, con
   const int rc = validate_robust(h, "icp_robust", source, target, params->max_correspondence_distance, estimator, lambda_geometric, loss, &spec, &s, &t);
   if (rc) return rc;
   return DISPATCH(t->precision, robust_register_t, h, *s, *t, init, *params, spec, out);
+}
+
+int o3ds_icp_localizability(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double T[16], double max_correspondence_distance, int estimator,
+                            double lambda_geometric, const o3ds_robust_loss* loss, const o3ds_degeneracy_params* params, o3ds_localizability* out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!T || !out) return fail(h, O3DS_ERR_INVALID_ARG, "icp_localizability: null argument");
+  int rc = validate_degeneracy(h, "icp_localizability", params);
+  if (rc) return rc;
+  CloudRec *s = nullptr, *t = nullptr;
+  RobustSpec spec;
+  rc = validate_robust(h, "icp_localizability", source, target, max_correspondence_distance, estimator, lambda_geometric, loss, &spec, &s, &t);
+  if (rc) return rc;
+  if (spec.colored && !cgrad_valid(*t))
+    return fail(h, O3DS_ERR_INVALID_ARG, "icp_localizability: the target has no colour gradients (o3ds_compute_color_gradients)");
+  return DISPATCH(t->precision, localizability_t, h, *s, *t, T, max_correspondence_distance, spec, *params, out);
+}
+
+int o3ds_icp_degeneracy_aware_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* icp_params,
+                                  int estimator, double lambda_geometric, const o3ds_robust_loss* loss, const o3ds_degeneracy_params* params,
+                                  o3ds_icp_result* out, o3ds_degeneracy_report* report) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!init || !icp_params || !out) return fail(h, O3DS_ERR_INVALID_ARG, "icp_degeneracy_aware: null argument");
+  if (icp_params->max_iteration < 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp_degeneracy_aware: negative max_iteration");
+  int rc = validate_degeneracy(h, "icp_degeneracy_aware", params);
+  if (rc) return rc;
+  CloudRec *s = nullptr, *t = nullptr;
+  RobustSpec spec;
+  rc = validate_robust(h, "icp_degeneracy_aware", source, target, icp_params->max_correspondence_distance, estimator, lambda_geometric, loss, &spec, &s,
+                       &t);
+  if (rc) return rc;
+  return DISPATCH(t->precision, degeneracy_register_t, h, *s, *t, init, *icp_params, spec, *params, out, report);
 }
 
 }  // extern "C"
