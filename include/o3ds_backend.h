@@ -109,7 +109,8 @@ int o3ds_profile_read(o3ds_handle h, uint64_t* n_launches, double* total_ms);
  * normal estimation), 9 (the kernels of an index build) and 10 (the kernel of o3ds_neighbor_search and of the outlier filters' search)
  * and 11 to 13 (the steps of o3ds_cluster_dbscan, see there) and 14 (the evaluation kernel of o3ds_segment_plane, once per batch of
  * hypotheses) and 15 (the kernel of o3ds_compute_color_gradients) and 16 (the two kernels of one coloured-ICP step: the block sums and
- * their fold) and 17 (the same two of one robust-loss step, o3ds_robust_icp_step) are marked inside the library.  span_read synchronises, returns the
+ * their fold) and 17 (the same two of one robust-loss step, o3ds_robust_icp_step) and 18 (the kernels of o3ds_voxel_gaussians_create) and 19
+ * (the two kernels of one o3ds_ndt_step) are marked inside the library.  span_read synchronises, returns the
  * number of complete spans of a tag and their summed duration (ms) and resets that tag. */
 int o3ds_profile_span(o3ds_handle h, int tag, int end);
 int o3ds_profile_span_read(o3ds_handle h, int tag, uint64_t* n_spans, double* total_ms);
@@ -1016,6 +1017,79 @@ int o3ds_icp_localizability(o3ds_handle h, o3ds_cloud source, o3ds_cloud target,
 int o3ds_icp_degeneracy_aware_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud target, const double init[16], const o3ds_icp_params* icp_params,
                                   int estimator, double lambda_geometric, const o3ds_robust_loss* loss, const o3ds_degeneracy_params* params,
                                   o3ds_icp_result* out, o3ds_degeneracy_report* report);
+
+/* ---- search-free registration against voxel Gaussians: the normal-distributions transform (Biber and Strasser 2003; Magnusson 2009) in the
+ * voxelised form of Koide et al. (VGICP, 2021).  Every registration above pays for an exact nearest-neighbour search per pass; here the
+ * target is summarised ONCE as one Gaussian per voxel of a world-anchored grid, and a pass costs per source point a voxel key, a lookup and
+ * one or seven 3x3 quadratic forms.  OFFERED like the three sections above and switched on nowhere; there is no Open3D 0.15.1 counterpart,
+ * so this text and tests/ndt_restatement.py (the same text in numpy) are the definition.
+ * ARITHMETIC: f64 on the stored values widened, every operation rounded on its own (no fused multiply-add).
+ * dot3(a, b) = (a0 b0 + a1 b1) + a2 b2.
+ *
+ * 1. THE VOXEL GAUSSIANS OF A CLOUD: a snapshot -- the cloud may be changed or freed afterwards; a map in its persistent form is folded first.
+ *    KEY: inv = 1.0 / voxel_size; k_a = floor(x_a * inv) per axis (the map merge's rounding).  A point with a non-finite coordinate, or with
+ *    some |k_a| >= 2^20, belongs to no voxel and is counted in n_skipped_points.
+ *    MEMBERS of a voxel: its points in ascending original index, n_v of them.  The voxels are stored and downloaded in ascending packed-key
+ *    order: kz major, then ky, then kx.
+ *    MEAN: per axis the members' coordinates added one after the other in index order onto +0.0, then divided by n_v.
+ *    COVARIANCE: r = p - mean per component; the six sums r_a r_b (a <= b) taken in the same order onto +0.0; C = S / (n_v - 1).  n_v == 1:
+ *    C = S (six times +0.0; nothing is divided).
+ *    VALID iff n_v >= min_points and, with (lambda, V) the eigen-decomposition of C by step 2 of the degeneracy section (eight cyclic Jacobi
+ *    sweeps, ascending order, the sign rule), lambda_2 is finite and lambda_2 > 0.  A voxel with n_v >= min_points that fails on lambda_2
+ *    is counted in n_flat (coincident points).  The decomposition of a voxel with fewer members is not taken.
+ *    INFORMATION of a valid voxel: f = min_eigenvalue_ratio * lambda_2; l_i = lambda_i < f ? f : lambda_i;
+ *    B[a][b] = ((V[a][0] V[b][0]) / l_0 + (V[a][1] V[b][1]) / l_1) + (V[a][2] V[b][2]) / l_2 for a <= b, mirrored.  An invalid voxel downloads
+ *    zeros for `information` and valid = 0.
+ *    Errors: O3DS_ERR_INVALID_ARG for null params or out, a voxel_size that is not finite or not > 0, min_points < 2, a
+ *    min_eigenvalue_ratio outside (0, 1] or NaN, reserved != 0, an unknown id; O3DS_ERR_CAPACITY for 2^31 points or more, a buffer beyond
+ *    the pool cap, a download capacity below n_voxels.  An empty cloud, or one whose points are all skipped, gives an object with 0 voxels.
+ *    Any output pointer of the download may be NULL: that array is not wanted.  PCL's defaults are min_points 6 and ratio 0.01.
+ *    While profiling is enabled the library marks span 18 around the kernels of the build. */
+typedef uint64_t o3ds_voxel_gaussians;
+typedef struct {
+  double voxel_size;
+  int32_t min_points;
+  int32_t reserved; /* must be 0 */
+  double min_eigenvalue_ratio;
+} o3ds_voxel_gaussian_params; /* 24 bytes */
+typedef struct {
+  uint64_t n_voxels, n_valid, n_skipped_points, n_flat;
+} o3ds_voxel_gaussians_info; /* 32 bytes */
+int o3ds_voxel_gaussians_create(o3ds_handle h, o3ds_cloud cloud, const o3ds_voxel_gaussian_params* params, o3ds_voxel_gaussians* out,
+                                o3ds_voxel_gaussians_info* info /* may be NULL */);
+int o3ds_voxel_gaussians_free(o3ds_handle h, o3ds_voxel_gaussians g);
+int o3ds_voxel_gaussians_info_get(o3ds_handle h, o3ds_voxel_gaussians g, o3ds_voxel_gaussians_info* info, double* voxel_size /* may be NULL */);
+int o3ds_voxel_gaussians_download(o3ds_handle h, o3ds_voxel_gaussians g, int32_t* keys /* n x 3 */, uint32_t* counts, double* mean /* n x 3 */,
+                                  double* cov /* n x 6 upper, row-major */, double* information /* n x 6 */, uint8_t* valid, size_t capacity);
+/* 2. ONE STEP.  QUERY: p_a = ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3] in f64, NOT rounded to storage: no search has to agree with
+ *    it.  Its key is formed as above; a query the build rule would skip matches nothing.
+ *    NEIGHBOURHOOD: the voxels at the offsets (0,0,0), (+1,0,0), (-1,0,0), (0,+1,0), (0,-1,0), (0,0,+1), (0,0,-1) of the query's, in this
+ *    order; `neighbourhood` = 1 takes the first only, 7 all of them.
+ *    PER VALID VOXEL found, with its mean mu and information B: e = p - mu; u_a = (B[a][0] e_0 + B[a][1] e_1) + B[a][2] e_2; m = dot3(e, u);
+ *    r = m > 0 ? sqrt(m) : 0; w = Weight(r) of the robust section (the same six losses, the same validation of `loss`).  J is 3x6, the
+ *    update being applied on the left as everywhere here: its columns are e_0 x p = (0, -p_z, p_y), (p_z, 0, -p_x), (-p_y, p_x, 0), e_0, e_1,
+ *    e_2.  G[a][c] = (B[a][0] J[0][c] + B[a][1] J[1][c]) + B[a][2] J[2][c], zeros included.  The voxel's terms:
+ *    h[r][c] = w * ((J[0][r] G[0][c] + J[1][r] G[1][c]) + J[2][r] G[2][c]) for r <= c; g[r] = w * ((J[0][r] u_0 + J[1][r] u_1) + J[2][r] u_2);
+ *    m; ee = dot3(e, e).
+ *    TERM OF A QUERY: [0..20] and [21..26] the h and g of its voxels added in neighbourhood order onto +0.0; [27] the same sum of m,
+ *    unweighted; [28] 1 if at least one valid voxel was found, else the whole term is +0.0; [29] the smallest ee among them, the first of
+ *    equals; [30..31] 0.
+ *    SUM ORDER over the queries: the coloured section's -- blocks of 256 in index order, the halving tree, the block sums ascending onto +0.0.
+ *    The zero record for an empty source, a target without a valid voxel, and no matched query.  With J as above J^T n = cross(p, n): sign
+ *    and parameter conventions are the point-to-plane record's, and [0..20] x = -[21..26] is the Gauss-Newton / IRLS step of
+ *    sum w e^T B e.  The Gaussian weight of textbook NDT, exp(-d2 m / 2), is deliberately not offered: a device exp is not correctly
+ *    rounded, so the record could not be held bit for bit; Cauchy and GM on r = sqrt(m) have the same bell shape.
+ *    No result depends on how a voxel is looked up.  Errors: O3DS_ERR_INVALID_ARG for a neighbourhood other than 1 or 7, null pointers,
+ *    unknown ids and an invalid loss.  While profiling is enabled the library marks span 19 around the two kernels of the step. */
+int o3ds_ndt_step(o3ds_handle h, o3ds_cloud source, o3ds_voxel_gaussians target, const double T[16], int neighbourhood /* 1 or 7 */,
+                  const o3ds_robust_loss* loss, double record[32]);
+/* 3. THE REGISTRATION: the loop of o3ds_icp_robust_dev around the step above.  fitness = [28] / |source|, inlier_rmse = sqrt([29] / [28]);
+ *    the convergence rule, the solve and the update are unchanged (the point-to-plane treatment of an empty set).  params->method and
+ *    params->max_correspondence_distance are IGNORED: the neighbourhood is the radius.  Errors: O3DS_ERR_EMPTY for a target with 0 voxels;
+ *    O3DS_ERR_INVALID_ARG for a negative max_iteration, null pointers, unknown ids, and the step's.  An empty source gives fitness 0 and the
+ *    initial pose.  Two calls, or two handles, give the same bytes. */
+int o3ds_icp_ndt_dev(o3ds_handle h, o3ds_cloud source, o3ds_voxel_gaussians target, const double init[16], const o3ds_icp_params* params,
+                     int neighbourhood, const o3ds_robust_loss* loss, o3ds_icp_result* out);
 
 #ifdef __cplusplus
 }

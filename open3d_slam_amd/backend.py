@@ -65,6 +65,14 @@ class DegeneracyReport(C.Structure):  # o3ds_degeneracy_report
                 ("n_degenerate", C.c_int32), ("ever_degenerate", C.c_int32 * 6), ("n_passes_constrained", C.c_int32)]
 
 
+class VoxelGaussianParams(C.Structure):  # o3ds_voxel_gaussian_params
+    _fields_ = [("voxel_size", C.c_double), ("min_points", C.c_int32), ("reserved", C.c_int32), ("min_eigenvalue_ratio", C.c_double)]
+
+
+class VoxelGaussiansInfo(C.Structure):  # o3ds_voxel_gaussians_info
+    _fields_ = [("n_voxels", C.c_uint64), ("n_valid", C.c_uint64), ("n_skipped_points", C.c_uint64), ("n_flat", C.c_uint64)]
+
+
 _dp = C.POINTER(C.c_double)
 _H = C.c_void_p
 _CL = C.c_uint64
@@ -244,6 +252,13 @@ SIGNATURES = {
                                           C.POINTER(Localizability)]),
     "o3ds_icp_degeneracy_aware_dev": (C.c_int, [_H, _CL, _CL, _dp, C.POINTER(IcpParams), C.c_int, C.c_double, C.POINTER(RobustLoss),
                                                 C.POINTER(DegeneracyParams), C.POINTER(IcpResult), C.POINTER(DegeneracyReport)]),
+    "o3ds_voxel_gaussians_create": (C.c_int, [_H, _CL, C.POINTER(VoxelGaussianParams), C.POINTER(C.c_uint64), C.POINTER(VoxelGaussiansInfo)]),
+    "o3ds_voxel_gaussians_free": (C.c_int, [_H, C.c_uint64]),
+    "o3ds_voxel_gaussians_info_get": (C.c_int, [_H, C.c_uint64, C.POINTER(VoxelGaussiansInfo), _dp]),
+    "o3ds_voxel_gaussians_download": (C.c_int, [_H, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _dp, _dp, _dp, C.POINTER(C.c_uint8),
+                                                C.c_size_t]),
+    "o3ds_ndt_step": (C.c_int, [_H, _CL, C.c_uint64, _dp, C.c_int, C.POINTER(RobustLoss), _dp]),
+    "o3ds_icp_ndt_dev": (C.c_int, [_H, _CL, C.c_uint64, _dp, C.POINTER(IcpParams), C.c_int, C.POINTER(RobustLoss), C.POINTER(IcpResult)]),
     "o3ds_feature_correspondences": (C.c_int, [_H, _CL, _CL, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_int)]),
     "o3ds_ransac_feature_matching": (C.c_int, [_H, _CL, _CL, C.POINTER(RansacParams), C.c_uint64, C.POINTER(RansacResult),
@@ -744,6 +759,57 @@ class Backend:
             return bytes(out), bytes(rep)
         return self._result(out), dict(self._analysis(rep), ever_degenerate=np.array(rep.ever_degenerate, dtype=np.int32),
                                        n_passes_constrained=int(rep.n_passes_constrained))
+
+    # -- search-free registration against voxel Gaussians (NDT; o3ds_backend.h, the last section)
+    @staticmethod
+    def _gaussians_info(info: VoxelGaussiansInfo) -> dict:
+        return dict(n_voxels=int(info.n_voxels), n_valid=int(info.n_valid), n_skipped_points=int(info.n_skipped_points), n_flat=int(info.n_flat))
+
+    def voxel_gaussians_create(self, cloud: int, voxel_size: float, min_points: int = 6, min_eigenvalue_ratio: float = 0.01, reserved: int = 0):
+        """o3ds_voxel_gaussians_create: (id, info) of the snapshot; the defaults are PCL's"""
+        vp = VoxelGaussianParams(float(voxel_size), int(min_points), int(reserved), float(min_eigenvalue_ratio))
+        gid, info = C.c_uint64(0), VoxelGaussiansInfo()
+        self._ck(self.lib.o3ds_voxel_gaussians_create(self.h, cloud, C.byref(vp), C.byref(gid), C.byref(info)))
+        return int(gid.value), self._gaussians_info(info)
+
+    def voxel_gaussians_free(self, gid: int):
+        self._ck(self.lib.o3ds_voxel_gaussians_free(self.h, gid))
+
+    def voxel_gaussians_info(self, gid: int) -> dict:
+        """the four counters and the voxel size of the object"""
+        info, voxel = VoxelGaussiansInfo(), C.c_double(0.0)
+        self._ck(self.lib.o3ds_voxel_gaussians_info_get(self.h, gid, C.byref(info), C.byref(voxel)))
+        return dict(self._gaussians_info(info), voxel_size=voxel.value)
+
+    def voxel_gaussians_download(self, gid: int, capacity=None) -> dict:
+        """keys (n, 3) int32, counts, mean (n, 3), cov and information (n, 6: the upper triangle, row-major), valid -- in ascending key order"""
+        n = self.voxel_gaussians_info(gid)["n_voxels"]
+        cap = n if capacity is None else int(capacity)
+        m = max(cap, 1)
+        keys, counts = np.zeros((m, 3), np.int32), np.zeros(m, np.uint32)
+        mean, cov, info, valid = np.zeros((m, 3)), np.zeros((m, 6)), np.zeros((m, 6)), np.zeros(m, np.uint8)
+        self._ck(self.lib.o3ds_voxel_gaussians_download(self.h, gid, keys.ctypes.data_as(C.POINTER(C.c_int32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp), info.ctypes.data_as(_dp),
+                                                        valid.ctypes.data_as(C.POINTER(C.c_uint8)), cap))
+        return dict(keys=keys[:n], counts=counts[:n], mean=mean[:n], cov=cov[:n], information=info[:n], valid=valid[:n])
+
+    def ndt_step(self, source: int, gaussians: int, neighbourhood: int = 7, loss=None, T=None) -> np.ndarray:
+        """o3ds_ndt_step: the 32-double record of one pass under T (None: identity)"""
+        T0, ip = (None, _IDENTITY16) if T is None else _d(colmajor(T))
+        rec = np.zeros(32)
+        ls = self._loss(loss)
+        self._ck(self.lib.o3ds_ndt_step(self.h, source, gaussians, ip, int(neighbourhood), C.byref(ls), rec.ctypes.data_as(_dp)))
+        return rec
+
+    def icp_ndt(self, source: int, gaussians: int, neighbourhood: int = 7, loss=None, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                raw: bool = False):
+        """o3ds_icp_ndt_dev; raw=True returns the bytes of o3ds_icp_result instead of the dict"""
+        T0, ip = (None, _IDENTITY16) if init is None else _d(colmajor(init))
+        p = self._params(0.0, max_iter, rel_fitness, rel_rmse)  # (the correspondence distance is ignored: the neighbourhood is the radius)
+        out = IcpResult()
+        ls = self._loss(loss)
+        self._ck(self.lib.o3ds_icp_ndt_dev(self.h, source, gaussians, ip, C.byref(p), int(neighbourhood), C.byref(ls), C.byref(out)))
+        return bytes(out) if raw else self._result(out)
 
     # -- sharded registrations inside the library (RCCL through dlopen; o3ds_backend.h)
     SHARD_SOURCE, SHARD_SUBMAP, SHARD_UNION = 0, 1, 2

@@ -330,6 +330,61 @@ def createDegeneracyAwareIcp(p: CloudRegistrationParameters, estimator: str = "p
     return ret
 
 
+class RegistrationNdt(CloudRegistration):
+    """Search-free registration against the voxel Gaussians of the target (the normal-distributions transform; o3ds_icp_ndt_dev).  Offered
+    beside the reference's three like the classes above and not made by cloudRegistrationFactory.  The Gaussians of the last target it saw
+    are kept and rebuilt only when it is handed another cloud (by handle and id) or other build parameters; they are a snapshot, so after
+    changing that cloud in place call invalidate()."""
+
+    def __init__(self):
+        self.voxelSize_ = 1.0
+        self.minPoints_ = 6             # PCL's NormalDistributionsTransform defaults
+        self.minEigenvalueRatio_ = 0.01
+        self.neighbourhood_ = 7         # 1: the query's own voxel; 7: and its six face neighbours
+        self.kernel_: RobustKernel = CauchyLoss(1.0)  # on r = sqrt(e^T B e), in standard deviations
+        self.icpConvergenceCriteria_ = ICPConvergenceCriteria()
+        self._be, self._key, self._gaussians = None, None, None
+        self.lastInfo = None  # the counters of the Gaussians in use
+
+    def invalidate(self) -> None:
+        if self._gaussians is not None and getattr(self._be, "h", None):
+            self._be.voxel_gaussians_free(self._gaussians)
+        self._be, self._key, self._gaussians = None, None, None
+
+    def __del__(self):
+        try:
+            self.invalidate()
+        except Exception:
+            pass
+
+    def _targetGaussians(self, target: PointCloud) -> int:
+        key = (target.id, self.voxelSize_, self.minPoints_, self.minEigenvalueRatio_)
+        if self._gaussians is None or self._be is not target.be or self._key != key:
+            self.invalidate()
+            self._gaussians, self.lastInfo = target.be.voxel_gaussians_create(target.id, self.voxelSize_, self.minPoints_, self.minEigenvalueRatio_)
+            self._be, self._key = target.be, key
+        return self._gaussians
+
+    def registerClouds(self, source: PointCloud, target: PointCloud, init) -> RegistrationResult:
+        c = self.icpConvergenceCriteria_
+        try:
+            r = source.be.icp_ndt(source.id, self._targetGaussians(target), self.neighbourhood_, self.kernel_.toBackend(), init=init,
+                                  max_iter=c.max_iteration_, rel_fitness=c.relative_fitness_, rel_rmse=c.relative_rmse_)
+        except _b.BackendError as e:
+            raise RuntimeError(str(e)) from e
+        return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"], r["converged"])
+
+    def estimateNormalsOrCovariancesIfNeeded(self, cloud: PointCloud) -> None:  # nothing per point: the covariances are the voxels'
+        return None
+
+
+def createNdt(p: CloudRegistrationParameters, voxelSize: float, neighbourhood: int = 7, kernel: RobustKernel = CauchyLoss(1.0)) -> RegistrationNdt:
+    ret = RegistrationNdt()
+    ret.voxelSize_, ret.neighbourhood_, ret.kernel_ = float(voxelSize), int(neighbourhood), kernel
+    ret.icpConvergenceCriteria_.max_iteration_ = p.icp_.maxNumIter_
+    return ret
+
+
 def createPointToPointIcp(p: CloudRegistrationParameters) -> RegistrationIcpPointToPoint:  # CloudRegistration.cpp:76-81
     ret = RegistrationIcpPointToPoint()
     ret.maxCorrespondenceDistance_ = p.icp_.maxCorrespondenceDistance_

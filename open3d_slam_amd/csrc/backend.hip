@@ -34,6 +34,7 @@
 #include "colored_icp_kernels.hpp"  // (and these the plane's)
 #include "robust_icp_kernels.hpp"   // (and this one the coloured step's)
 #include "degeneracy_kernels.hpp"   // (and this one the robust step's)
+#include "ndt_kernels.hpp"          // (and these the degeneracy tail's)
 
 using namespace o3ds;
 
@@ -205,6 +206,18 @@ struct DenseRec {
                            // looks too full); the load factor of the open-addressing table is about these, not about live voxels
 };
 
+// the voxel Gaussians of a cloud (ndt_kernels.hpp): a snapshot, every array n_vox long and in ascending packed-key order
+struct NdtRec {
+  double voxel = 0.0;
+  size_t n_vox = 0;
+  o3ds_voxel_gaussians_info info{};
+  unsigned long long* keys = nullptr;
+  uint32_t* counts = nullptr;
+  double *mean = nullptr, *cov = nullptr, *information = nullptr;
+  uint8_t* valid = nullptr;
+  o3ds::NdtVoxel* rec = nullptr;  // what a pass reads
+};
+
 struct o3ds_context {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -212,6 +225,7 @@ struct o3ds_context {
   std::string err, deferred_err;
   std::unordered_map<uint64_t, CloudRec> clouds;
   std::unordered_map<uint64_t, DenseRec> dense_maps;
+  std::unordered_map<uint64_t, NdtRec> voxel_gaussians;
   uint64_t next_id = 1;
   // ICP scratch
   double* d_partials = nullptr;     // [kMaxPassBlocks][kRec]
@@ -326,7 +340,7 @@ struct o3ds_context {
   size_t ev_used = 0;
   // ... and tagged spans (o3ds_profile_span): pairs of events around whatever the caller -- or, for the internal tags, a kernel
   // sequence inside a call -- encloses
-  static constexpr int kSpanTags = 18;  // 0..7 the caller's (o3ds_profile_span), 8..17 marked inside the library
+  static constexpr int kSpanTags = 20;  // 0..7 the caller's (o3ds_profile_span), 8..19 marked inside the library
   std::vector<hipEvent_t> span_ev[kSpanTags];
   size_t span_used[kSpanTags] = {0};
 };
@@ -1360,6 +1374,12 @@ void dense_release(o3ds_handle h, DenseRec& d) {
   d.cap = 0;
 }
 
+void ndt_release(o3ds_handle h, NdtRec& g) {
+  for (void* p : {(void*)g.keys, (void*)g.counts, (void*)g.mean, (void*)g.cov, (void*)g.information, (void*)g.valid, (void*)g.rec})
+    if (p) dev_free(h, p);
+  g = NdtRec{};
+}
+
 int dense_alloc(o3ds_handle h, size_t cap, o3ds::DenseDev* out) {
   o3ds::DenseDev d{};
   HIP_TRY(dev_alloc(h, (void**)&d.keys, sizeof(unsigned long long) * cap));
@@ -1931,6 +1951,7 @@ int o3ds_destroy(o3ds_handle h) {
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   for (auto& kv : h->clouds) free_cloud(h, kv.second);
   for (auto& kv : h->dense_maps) dense_release(h, kv.second);
+  for (auto& kv : h->voxel_gaussians) ndt_release(h, kv.second);
   for (auto& b : h->arena_blocks) dev_free(h, b.first);
   (void)hipStreamSynchronize(h->stream);
   dev_release_all(h);
@@ -5630,17 +5651,17 @@ int colored_step_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double T
 // convergence test, 6x6 LDL^T, T <- U T), and the host reads the state it publishes -- the next pose and whether the loop has ended
 // `pass(T, cp)` enqueues one correspondence pass under T and leaves its record in cp.d_record (colored_pass_t, robust_pass_t)
 // `tail(cp)` enqueues the one-workgroup kernel that turns the record into the next state (icp_update_kernel, or the degeneracy-aware one)
-template <typename P4, typename Pass, typename Tail>
-int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass, Tail tail) {
-  const double r = p.max_correspondence_distance;
-  ColoredPass cp;
-  int rc = colored_prepare_t<P4>(h, s, t, r, cp);  // the finite count's read-back and the index check: once, not per pass
-  if (rc) return rc;
+// `cp` arrives prepared (colored_prepare_t for the passes that search, ndt_prepare for the one that does not): the loop itself knows
+// nothing of how a pass finds its pairs
+template <typename Pass, typename Tail>
+int step_loop_run(o3ds_handle h, size_t n_src, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, const ColoredPass& cp, Pass pass,
+                  Tail tail) {
+  int rc = O3DS_OK;
   h->session = false;  // (the handle's one state is taken: a step-wise session that was open is over)
   IcpStateDev st{};
   memcpy(st.T, init, sizeof(double) * 16);
   *h->h_state = st;
-  if (s.n == 0) {  // [O3D]: no correspondence, fitness 0, the initial pose
+  if (n_src == 0) {  // [O3D]: no correspondence, fitness 0, the initial pose
     copy_result(h, out);
     return O3DS_OK;
   }
@@ -5659,12 +5680,22 @@ int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init
   }
   return O3DS_OK;
 }
+// the loop of the passes that search: the search is prepared here, once per call
+template <typename P4, typename Pass, typename Tail>
+int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass, Tail tail) {
+  ColoredPass cp;
+  const int rc = colored_prepare_t<P4>(h, s, t, p.max_correspondence_distance, cp);  // the finite count's read-back and the index check: once, not per pass
+  if (rc) return rc;
+  return step_loop_run(h, s.n, init, p, out, cp, pass, tail);
+}
+// the ordinary tail: the solve and update every step loop runs, with the point-to-plane treatment of an empty set
+void update_tail(o3ds_handle h, const ColoredPass& cp, size_t n_src, const o3ds_icp_params& p) {
+  icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)n_src, p.max_iteration, p.relative_fitness, p.relative_rmse,
+                                             O3DS_ICP_POINT_TO_PLANE, nullptr, 0);
+}
 template <typename P4, typename Pass>
 int step_loop_t(o3ds_handle h, const CloudRec& s, CloudRec& t, const double init[16], const o3ds_icp_params& p, o3ds_icp_result* out, Pass pass) {
-  return step_loop_t<P4>(h, s, t, init, p, out, pass, [&](const ColoredPass& cp) {
-    icp_update_kernel<<<1, 128, 0, h->stream>>>(cp.d_record, h->d_state, (unsigned long long)s.n, p.max_iteration, p.relative_fitness, p.relative_rmse,
-                                               O3DS_ICP_POINT_TO_PLANE, nullptr, 0);
-  });
+  return step_loop_t<P4>(h, s, t, init, p, out, pass, [&](const ColoredPass& cp) { update_tail(h, cp, s.n, p); });
 }
 
 // the target's gradients of (2 r, 30), as [O3D] RegistrationColoredICP initialises it: made if absent or of other parameters, and left
@@ -5754,18 +5785,25 @@ int validate_colored(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cl
   return O3DS_OK;
 }
 
-// the loss and the estimator, then the clouds: COLORED is held to validate_colored, POINT_TO_PLANE to its checks without the colours
-int validate_robust(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cloud target, double r, int estimator, double lambda,
-                    const o3ds_robust_loss* loss, RobustSpec* spec, CloudRec** src, CloudRec** tgt) {
+// a caller's loss in the form the kernels take
+int validate_loss(o3ds_handle h, const char* what, const o3ds_robust_loss* loss, RobustLossDev* out) {
   if (!loss) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": null loss");
   if (loss->kind < O3DS_LOSS_L2 || loss->kind > O3DS_LOSS_TUKEY) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown loss kind");
   if (loss->reserved != 0) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": o3ds_robust_loss.reserved must be 0");
   const bool uses_k = loss->kind != O3DS_LOSS_L2 && loss->kind != O3DS_LOSS_L1;
   if (uses_k && !(std::isfinite(loss->k) && loss->k > 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": the loss's k must be finite and > 0");
+  *out = RobustLossDev{loss->kind, uses_k ? loss->k : 1.0};
+  return O3DS_OK;
+}
+
+// the loss and the estimator, then the clouds: COLORED is held to validate_colored, POINT_TO_PLANE to its checks without the colours
+int validate_robust(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_cloud target, double r, int estimator, double lambda,
+                    const o3ds_robust_loss* loss, RobustSpec* spec, CloudRec** src, CloudRec** tgt) {
+  const int rl = validate_loss(h, what, loss, &spec->loss);
+  if (rl) return rl;
   if (estimator != O3DS_ROBUST_POINT_TO_PLANE && estimator != O3DS_ROBUST_COLORED)
     return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown estimator");
   spec->colored = estimator == O3DS_ROBUST_COLORED;
-  spec->loss = RobustLossDev{loss->kind, uses_k ? loss->k : 1.0};
   if (spec->colored) {
     spec->sg = std::sqrt(lambda);
     spec->sp = std::sqrt(1.0 - lambda);
@@ -5879,6 +5917,139 @@ int validate_degeneracy(o3ds_handle h, const char* what, const o3ds_degeneracy_p
   if (!dp) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": null degeneracy params");
   for (const double v : {dp->min_eigenvalue_rotation, dp->min_eigenvalue_translation})
     if (!(std::isfinite(v) && v >= 0.0)) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": a minimum eigenvalue must be finite and >= 0");
+  return O3DS_OK;
+}
+
+// ---- search-free registration against voxel Gaussians (ndt_kernels.hpp) ---------------------------------------------------------------
+constexpr int kSpanNdtBuild = 18, kSpanNdtStep = 19;
+
+// keys, the stable sort, segment heads, one statistics kernel; two read-backs (the sizes, then the counters)
+template <typename P4>
+int voxel_gaussians_build_t(o3ds_handle h, const CloudRec& c, const o3ds_voxel_gaussian_params& vp, NdtRec& g) {
+  const size_t n = c.n;
+  g.voxel = vp.voxel_size;
+  if (n >= ((size_t)1 << 31)) return fail(h, O3DS_ERR_CAPACITY, "voxel_gaussians_create: clouds of 2^31 points and more are unsupported");
+  if (n * sizeof(NdtVoxel) > pool_cap_bytes())  // (the largest array of the object, had every point a voxel of its own)
+    return fail(h, O3DS_ERR_CAPACITY, "voxel_gaussians_create: a buffer exceeds the pool cap (O3DS_POOL_CAP_MB)");
+  if (n == 0) return O3DS_OK;
+  unsigned long long *k0 = nullptr, *k1 = nullptr, *d_inside = nullptr;
+  uint32_t *v0 = nullptr, *v1 = nullptr;
+  int *head = nullptr, *seg_id = nullptr, *seg_start = nullptr;
+  unsigned int* d_counters = nullptr;
+  TMP_ALLOC(k0, sizeof(unsigned long long) * n);
+  TMP_ALLOC(k1, sizeof(unsigned long long) * n);
+  TMP_ALLOC(v0, sizeof(uint32_t) * n);
+  TMP_ALLOC(v1, sizeof(uint32_t) * n);
+  TMP_ALLOC(head, sizeof(int) * (n + 1));
+  TMP_ALLOC(seg_id, sizeof(int) * (n + 1));
+  TMP_ALLOC(d_inside, sizeof(unsigned long long));
+  TMP_ALLOC(d_counters, sizeof(unsigned int) * 2);
+  span_mark(h, kSpanNdtBuild);
+  ndt_key_kernel<P4><<<grid_for(n), kBlock, 0, h->stream>>>((const P4*)c.pts, n, vp.voxel_size, k0, v0);
+  int rc = sort_pairs(h, k0, k1, v0, v1, n);
+  if (!rc) {
+    ndt_inside_kernel<<<1, 64, 0, h->stream>>>(k1, n, d_inside);
+    rc = key_segments(h, k1, n, head, seg_id, nullptr);
+  }
+  int n_seg = 0;
+  unsigned long long n_inside = 0;
+  if (!rc) rc = read_back(h, {{&n_seg, seg_id + n, sizeof(int)}, {&n_inside, d_inside, sizeof(n_inside)}});
+  if (rc) {
+    span_mark(h, kSpanNdtBuild);
+    return rc;
+  }
+  const size_t n_vox = (size_t)n_seg - (n_inside < n ? 1 : 0);  // the points without a voxel share the last key
+  g.info.n_skipped_points = n - n_inside;
+  if (n_vox == 0) {
+    span_mark(h, kSpanNdtBuild);
+    return O3DS_OK;
+  }
+  TMP_ALLOC(seg_start, sizeof(int) * ((size_t)n_seg + 1));
+  segment_start_kernel<<<grid_for(n), kBlock, 0, h->stream>>>(head, seg_id, n, seg_start);
+  DevGuard guard(h);
+  for (void** q : {(void**)&g.keys, (void**)&g.counts, (void**)&g.mean, (void**)&g.cov, (void**)&g.information, (void**)&g.valid, (void**)&g.rec}) guard.add(q);
+  HIP_TRY(dev_alloc(h, (void**)&g.keys, sizeof(unsigned long long) * n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.counts, sizeof(uint32_t) * n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.mean, sizeof(double) * 3 * n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.cov, sizeof(double) * 6 * n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.information, sizeof(double) * 6 * n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.valid, n_vox));
+  HIP_TRY(dev_alloc(h, (void**)&g.rec, sizeof(NdtVoxel) * n_vox));
+  HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(unsigned int) * 2, h->stream));
+  ndt_stats_kernel<P4><<<(unsigned int)((n_vox + kBlock - 1) / kBlock), kBlock, 0, h->stream>>>((const P4*)c.pts, k1, v1, seg_start, n_vox, (size_t)n_inside,
+                                                                                               vp.min_points, vp.min_eigenvalue_ratio, g.keys, g.counts, g.mean,
+                                                                                               g.cov, g.information, g.valid, g.rec, d_counters);
+  span_mark(h, kSpanNdtBuild);
+  HIP_TRY(hipGetLastError());
+  unsigned int counters[2] = {0, 0};
+  rc = read_back(h, {{counters, d_counters, sizeof(counters)}});
+  if (rc) return rc;
+  guard.release();
+  g.n_vox = n_vox;
+  g.info.n_voxels = n_vox;
+  g.info.n_valid = counters[0];
+  g.info.n_flat = counters[1];
+  return O3DS_OK;
+}
+
+// what the passes of one call share; no search is prepared.  A target without a valid voxel gives the zero record
+int ndt_prepare(o3ds_handle h, const CloudRec& s, const NdtRec& g, ColoredPass& cp) {
+  cp.nblocks = (s.n + kColStepBlock - 1) / kColStepBlock;
+  TMP_ALLOC(cp.d_record, sizeof(double) * kRec);
+  if (s.n == 0) return O3DS_OK;
+  TMP_ALLOC(cp.d_partial, sizeof(double) * kRec * cp.nblocks);
+  cp.empty = g.info.n_valid == 0;
+  return O3DS_OK;
+}
+// one pass under T and its reduction into cp.d_record; nothing waits
+template <typename P4>
+int ndt_pass_t(o3ds_handle h, const CloudRec& s, const NdtRec& g, const double T[16], int neighbourhood, RobustLossDev loss, const ColoredPass& cp) {
+  if (cp.empty) {
+    HIP_TRY(hipMemsetAsync(cp.d_record, 0, sizeof(double) * kRec, h->stream));
+    return O3DS_OK;
+  }
+  span_mark(h, kSpanNdtStep);
+  ndt_step_kernel<P4><<<(unsigned int)cp.nblocks, kColStepBlock, 0, h->stream>>>((const P4*)s.pts, s.n, mat34(T), g.voxel, g.keys, g.rec, g.n_vox, neighbourhood, loss,
+                                                                                 cp.d_partial);
+  colored_finish_kernel<<<1, 64, 0, h->stream>>>(cp.d_partial, cp.nblocks, cp.d_record);
+  span_mark(h, kSpanNdtStep);
+  HIP_TRY(hipGetLastError());
+  return O3DS_OK;
+}
+
+template <typename P4>
+int ndt_step_t(o3ds_handle h, const CloudRec& s, const NdtRec& g, const double T[16], int neighbourhood, RobustLossDev loss, double record[32]) {
+  ColoredPass cp;
+  int rc = ndt_prepare(h, s, g, cp);
+  if (rc) return rc;
+  rc = ndt_pass_t<P4>(h, s, g, T, neighbourhood, loss, cp);
+  if (rc) return rc;
+  return read_back(h, {{record, cp.d_record, sizeof(double) * kRec}});
+}
+
+template <typename P4>
+int ndt_register_t(o3ds_handle h, const CloudRec& s, const NdtRec& g, const double init[16], const o3ds_icp_params& p, int neighbourhood, RobustLossDev loss,
+                   o3ds_icp_result* out) {
+  ColoredPass cp;
+  const int rc = ndt_prepare(h, s, g, cp);
+  if (rc) return rc;
+  return step_loop_run(
+      h, s.n, init, p, out, cp, [&](const double* T, const ColoredPass& c) { return ndt_pass_t<P4>(h, s, g, T, neighbourhood, loss, c); },
+      [&](const ColoredPass& c) { update_tail(h, c, s.n, p); });
+}
+
+// the checks the step and the registration share
+int validate_ndt(o3ds_handle h, const char* what, o3ds_cloud source, o3ds_voxel_gaussians target, int neighbourhood, const o3ds_robust_loss* loss,
+                 RobustLossDev* ld, CloudRec** src, NdtRec** tgt) {
+  const int rc = validate_loss(h, what, loss, ld);
+  if (rc) return rc;
+  if (neighbourhood != 1 && neighbourhood != 7) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": neighbourhood must be 1 or 7");
+  CloudRec* s = find_cloud(h, source);
+  if (!s) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown cloud id");
+  auto it = h->voxel_gaussians.find(target);
+  if (it == h->voxel_gaussians.end()) return fail(h, O3DS_ERR_INVALID_ARG, std::string(what) + ": unknown voxel Gaussians id");
+  *src = s;
+  *tgt = &it->second;
   return O3DS_OK;
 }
 }  // namespace
@@ -5999,6 +6170,99 @@ int o3ds_icp_degeneracy_aware_dev(o3ds_handle h, o3ds_cloud source, o3ds_cloud t
                        &t);
   if (rc) return rc;
   return DISPATCH(t->precision, degeneracy_register_t, h, *s, *t, init, *icp_params, spec, *params, out, report);
+}
+
+int o3ds_voxel_gaussians_create(o3ds_handle h, o3ds_cloud cloud, const o3ds_voxel_gaussian_params* params, o3ds_voxel_gaussians* out,
+                                o3ds_voxel_gaussians_info* info) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!params || !out) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: null argument");
+  if (!(std::isfinite(params->voxel_size) && params->voxel_size > 0.0))
+    return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: voxel_size must be finite and > 0");
+  if (params->min_points < 2) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: min_points must be at least 2");
+  if (!(params->min_eigenvalue_ratio > 0.0 && params->min_eigenvalue_ratio <= 1.0))
+    return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: min_eigenvalue_ratio must be in (0, 1]");
+  if (params->reserved != 0) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: o3ds_voxel_gaussian_params.reserved must be 0");
+  CloudRec* c = find_cloud(h, cloud);  // (with its exact size; a persistent map as its array)
+  if (!c) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_create: unknown cloud id");
+  NdtRec g;
+  const int rc = DISPATCH(c->precision, voxel_gaussians_build_t, h, *c, *params, g);
+  if (rc) return rc;
+  const uint64_t id = h->next_id++;
+  h->voxel_gaussians.emplace(id, g);
+  *out = id;
+  if (info) *info = g.info;
+  return O3DS_OK;
+}
+
+int o3ds_voxel_gaussians_free(o3ds_handle h, o3ds_voxel_gaussians id) {
+  CHECK_HANDLE(h);
+  auto it = h->voxel_gaussians.find(id);
+  if (it == h->voxel_gaussians.end()) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_free: unknown id");
+  ndt_release(h, it->second);  // (whatever still reads the arrays was enqueued earlier on the handle's one stream)
+  h->voxel_gaussians.erase(it);
+  return O3DS_OK;
+}
+
+int o3ds_voxel_gaussians_info_get(o3ds_handle h, o3ds_voxel_gaussians id, o3ds_voxel_gaussians_info* info, double* voxel_size) {
+  CHECK_HANDLE(h);
+  auto it = h->voxel_gaussians.find(id);
+  if (it == h->voxel_gaussians.end() || !info) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_info_get: bad argument");
+  *info = it->second.info;
+  if (voxel_size) *voxel_size = it->second.voxel;
+  return O3DS_OK;
+}
+
+int o3ds_voxel_gaussians_download(o3ds_handle h, o3ds_voxel_gaussians id, int32_t* keys, uint32_t* counts, double* mean, double* cov, double* information,
+                                  uint8_t* valid, size_t capacity) {
+  CHECK_HANDLE(h);
+  auto it = h->voxel_gaussians.find(id);
+  if (it == h->voxel_gaussians.end()) return fail(h, O3DS_ERR_INVALID_ARG, "voxel_gaussians_download: unknown id");
+  const NdtRec& g = it->second;
+  const size_t n = g.n_vox;
+  if (capacity < n) return fail(h, O3DS_ERR_CAPACITY, "voxel_gaussians_download: buffer too small");
+  if (n == 0) return O3DS_OK;
+  int rc = O3DS_OK;
+  if (keys) {
+    std::vector<unsigned long long> packed(n);
+    rc = d2h_copy(h, packed.data(), g.keys, n * sizeof(unsigned long long));
+    for (size_t v = 0; v < n && !rc; ++v)
+      for (int a = 0; a < 3; ++a) keys[3 * v + a] = (int32_t)((long long)((packed[v] >> (21 * a)) & 0x1FFFFFull) - (1ll << 20));
+  }
+  if (!rc && counts) rc = d2h_copy(h, counts, g.counts, n * sizeof(uint32_t));
+  if (!rc && mean) rc = d2h_copy(h, mean, g.mean, n * 3 * sizeof(double));
+  if (!rc && cov) rc = d2h_copy(h, cov, g.cov, n * 6 * sizeof(double));
+  if (!rc && information) rc = d2h_copy(h, information, g.information, n * 6 * sizeof(double));
+  if (!rc && valid) rc = d2h_copy(h, valid, g.valid, n);
+  return rc;
+}
+
+int o3ds_ndt_step(o3ds_handle h, o3ds_cloud source, o3ds_voxel_gaussians target, const double T[16], int neighbourhood, const o3ds_robust_loss* loss,
+                  double record[32]) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!T || !record) return fail(h, O3DS_ERR_INVALID_ARG, "ndt_step: null argument");
+  CloudRec* s = nullptr;
+  NdtRec* g = nullptr;
+  RobustLossDev ld{O3DS_LOSS_L2, 0.0};
+  const int rc = validate_ndt(h, "ndt_step", source, target, neighbourhood, loss, &ld, &s, &g);
+  if (rc) return rc;
+  return DISPATCH(s->precision, ndt_step_t, h, *s, *g, T, neighbourhood, ld, record);
+}
+
+int o3ds_icp_ndt_dev(o3ds_handle h, o3ds_cloud source, o3ds_voxel_gaussians target, const double init[16], const o3ds_icp_params* params, int neighbourhood,
+                     const o3ds_robust_loss* loss, o3ds_icp_result* out) {
+  CHECK_HANDLE(h);
+  ArenaScope arena_scope(h);
+  if (!init || !params || !out) return fail(h, O3DS_ERR_INVALID_ARG, "icp_ndt: null argument");
+  if (params->max_iteration < 0) return fail(h, O3DS_ERR_INVALID_ARG, "icp_ndt: negative max_iteration");
+  CloudRec* s = nullptr;
+  NdtRec* g = nullptr;
+  RobustLossDev ld{O3DS_LOSS_L2, 0.0};
+  const int rc = validate_ndt(h, "icp_ndt", source, target, neighbourhood, loss, &ld, &s, &g);
+  if (rc) return rc;
+  if (g->n_vox == 0) return fail(h, O3DS_ERR_EMPTY, "icp_ndt: the target has no voxel");
+  return DISPATCH(s->precision, ndt_register_t, h, *s, *g, init, *params, neighbourhood, ld, out);
 }
 
 }  // extern "C"
